@@ -1,6 +1,6 @@
 """Benchmark: device-resident XXH3-128 content hashing (the `oxen add` hash stage) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c4] [--dump-outputs DIR] [--full]
 
 One step = one batched K1 launch hashing every buffer of the rank's shard, already resident in HBM
 (plus, for N > 1, the single all-gather of the 16-B digest table over RCCL). Workload (weak
@@ -8,13 +8,16 @@ scaling, per GPU): BASELINE.json configs[1] -- 100 000 x 64 KiB splitmix64 blobs
 N > 1: one process per GPU. Under torch.distributed.run (WORLD_SIZE set) this process is one rank
 and WORLD_SIZE must equal --gpus; without a launcher, `--gpus N` starts the N ranks itself before
 anything touches the GPU and exits with the worst rank's status.
-Prints ONE JSON line on rank 0 (the driver's contract), including:
+Prints ONE JSON line on rank 0 (the driver's contract). A plain run sets up, warms up, times the K
+steps, writes the last step's digest table under --dump-outputs DIR if given, and prints the line
+(metric, value, unit, ms_per_step, ...). --full adds the legs that take runs of their own:
+  checks        N > 1: every rank's shard digests arrived, rank r's first item checked against the oracle.
   roofline      achieved HBM read GB/s of the K1 kernel (algorithmic bytes = buffer lengths) vs the
                 8 TB/s MI355X peak; `traffic` = PMC-measured HBM bytes per launch when a matching
                 profiles/*traffic*.json exists (rocprofv3 FETCH_SIZE, gfx950 x2 correction).
   cpu_baseline  the C oracle (oracle/, a restatement of the reference's XXH3-128) timed on the
                 host cores over a bounded sample of the same workload; the GPU digests of that
-                sample are checked bit-exact against it.
+                sample are checked bit-exact against it (N = 1; --no-cpu-baseline leaves it out).
 """
 from __future__ import annotations
 
@@ -68,11 +71,16 @@ def free_port() -> int:
     return port
 
 
+REFUSAL_GRACE_S = 60.0
+
+
 def launch_ranks(n: int) -> int:
     """`bench.py --gpus N` without a launcher: start N rank processes of this script (one per GPU,
     RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in their environment, as torch.distributed.run sets
     them) before this process touches the GPU, wait for all, and return the worst exit code. The
-    first rank to fail takes the others down (a dead rank would leave the rest in a barrier)."""
+    first rank to fail takes the others down (a dead rank would leave the rest in a barrier). Status 2
+    is a rank's refusal of its arguments or devices, taken before it joins any group and by every
+    rank alike: the others get REFUSAL_GRACE_S to say so themselves before they are stopped."""
     import subprocess
 
     port = free_port()
@@ -83,6 +91,7 @@ def launch_ranks(n: int) -> int:
         procs.append(subprocess.Popen([sys.executable, os.path.abspath(__file__)] + sys.argv[1:], env=env))
     worst = 0
     live = set(range(n))
+    stop_at = None  # when the ranks still running are stopped (set by the first failure)
     while live:
         for r in sorted(live):
             rc = procs[r].poll()
@@ -92,8 +101,12 @@ def launch_ranks(n: int) -> int:
             if rc != 0:
                 log(f"[bench] rank {r} exited with {rc}; stopping the other ranks")
                 worst = worst or rc
-                for q in live:
-                    procs[q].terminate()
+                deadline = time.monotonic() + (REFUSAL_GRACE_S if rc == 2 else 0.0)
+                stop_at = deadline if stop_at is None else min(stop_at, deadline)
+        if stop_at is not None and time.monotonic() >= stop_at:
+            for q in live:
+                procs[q].terminate()
+            stop_at = float("inf")
         time.sleep(0.05)
     for p in procs:
         p.wait()
@@ -213,6 +226,24 @@ def load_profile(workload: str):
     return best
 
 
+DUMP_MAX_ROWS = 1 << 20  # x 4 words x 8 B = 32 MiB of float64 at the most
+
+
+def dump_outputs(dirname: str, table: np.ndarray) -> None:
+    """The digest table of the last timed step ((rows, 2) u64: low word, high word) as
+    DIR/digests.npy, float64 (rows, 4): each digest's four 32-bit words, least significant first, so
+    every value is exact. Above DUMP_MAX_ROWS rows a fixed seeded sample of the rows is written, and
+    their indices beside it as DIR/digest_rows.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    rows = np.arange(table.shape[0], dtype=np.int64)
+    if table.shape[0] > DUMP_MAX_ROWS:
+        rows = np.sort(np.random.default_rng(0).choice(table.shape[0], DUMP_MAX_ROWS, replace=False))
+        table = table[rows]
+    words = np.ascontiguousarray(table, dtype=np.uint64).view(np.uint32).reshape(-1, 4)  # little-endian host
+    np.save(os.path.join(dirname, "digests.npy"), words.astype(np.float64))
+    np.save(os.path.join(dirname, "digest_rows.npy"), rows.astype(np.float64))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -223,7 +254,13 @@ def main() -> None:
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS))
     ap.add_argument("--seed", type=int, default=2024)
     ap.add_argument("--cpu-budget", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: the per-launch kernel "
+                         "timing and roofline record, the CPU baseline with its bit-exact check of the GPU digests, "
+                         "and for N > 1 the check of every rank's shard against the oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the digest table of the last timed step to DIR/digests.npy (see dump_outputs)")
     ap.add_argument("--variant", type=int, default=0)
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL on ROCm); gloo only to rehearse N>1 on one GPU")
     ap.add_argument("--gather", choices=["abi", "torch", "host"], default=None,
@@ -378,36 +415,41 @@ def main() -> None:
         dist.barrier()
     torch.cuda.synchronize()
     gpu_s = ev0.elapsed_time(ev1) / 1e3
-    # per-launch kernel time, from HIP events on the launch stream (no collective in this window):
-    # (a) each launch alone between its own two events, the GPU idle before it -- what a profiler's
-    # per-dispatch duration measures, and the figure the roofline uses; (b) back to back, where one
-    # launch's last waves overlap the next one's first (a throughput figure, reported beside it)
-    kreps = max(5, args.steps)
-    iso = []
-    for _ in range(kreps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        da.hash(out)
-        e1.record()
+    # what a caller of the timed path received from its last step, copied before anything else runs
+    table_host = to_numpy_u64(table).reshape(-1, 2).copy() if (rank == 0 and args.dump_outputs) else None
+    kernel_s = kernel_b2b_s = None
+    if args.full:
+        # per-launch kernel time, from HIP events on the launch stream (no collective in this window):
+        # (a) each launch alone between its own two events, the GPU idle before it -- what a profiler's
+        # per-dispatch duration measures, and the figure the roofline uses; (b) back to back, where one
+        # launch's last waves overlap the next one's first (a throughput figure, reported beside it)
+        kreps = max(5, args.steps)
+        iso = []
+        for _ in range(kreps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            da.hash(out)
+            e1.record()
+            torch.cuda.synchronize()
+            iso.append(e0.elapsed_time(e1) / 1e3)
+        kernel_s = float(np.median(iso))
+        kev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        kev[0].record()
+        for _ in range(kreps):
+            da.hash(out)
+        kev[1].record()
         torch.cuda.synchronize()
-        iso.append(e0.elapsed_time(e1) / 1e3)
-    kernel_s = float(np.median(iso))
-    kev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    kev[0].record()
-    for _ in range(kreps):
-        da.hash(out)
-    kev[1].record()
-    torch.cuda.synchronize()
-    kernel_b2b_s = kev[0].elapsed_time(kev[1]) / 1e3 / kreps
+        kernel_b2b_s = kev[0].elapsed_time(kev[1]) / 1e3 / kreps
 
     elapsed = max(wall, gpu_s)
-    log(f"[bench] rank {rank}: wall {wall * 1e3:.3f} ms, events {gpu_s * 1e3:.3f} ms, enqueue {t_enq * 1e3:.3f} ms, "
-        f"kernel {kernel_s * 1e3:.4f} ms alone (median of {kreps}), {kernel_b2b_s * 1e3:.4f} ms back to back; "
-        f"x {args.steps} = {kernel_b2b_s * args.steps * 1e3:.3f} ms")
-    t = torch.tensor([elapsed, kernel_s], dtype=torch.float64, device=dev)
+    log(f"[bench] rank {rank}: wall {wall * 1e3:.3f} ms, events {gpu_s * 1e3:.3f} ms, enqueue {t_enq * 1e3:.3f} ms")
+    if args.full:
+        log(f"[bench] rank {rank}: kernel {kernel_s * 1e3:.4f} ms alone (median of {kreps}), "
+            f"{kernel_b2b_s * 1e3:.4f} ms back to back; x {args.steps} = {kernel_b2b_s * args.steps * 1e3:.3f} ms")
     if multi:
+        t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-    elapsed, kernel_max = float(t[0]), float(t[1])
+        elapsed = float(t[0])
 
     bytes_per_rank = int(lens.sum())
     total_bytes = bytes_per_rank * world * args.steps
@@ -415,41 +457,44 @@ def main() -> None:
 
     result = None
     if rank == 0:
-        digests = to_numpy_u64(last).reshape(-1, 2)
-        if multi:
-            assert table.shape[0] == n_items * world
-            assert np.array_equal(to_numpy_u64(table[:n_items]).reshape(-1, 2), digests)
-            # every rank's shard digests arrived: rank r's first item is regenerated and checked
-            from oracle import oracle
-            from oxen_amd.workloads import splitmix_bytes
+        if table_host is not None:
+            dump_outputs(args.dump_outputs, table_host)
+        roofline = cpu = None
+        if args.full:
+            digests = to_numpy_u64(last).reshape(-1, 2)
+            if multi:
+                assert table.shape[0] == n_items * world
+                assert np.array_equal(to_numpy_u64(table[:n_items]).reshape(-1, 2), digests)
+                # every rank's shard digests arrived: rank r's first item is regenerated and checked
+                from oracle import oracle
+                from oxen_amd.workloads import splitmix_bytes
 
-            full = to_numpy_u64(table).reshape(-1, 2)
-            for r in range(world):
-                want = oracle.xxh3_128(splitmix_bytes(args.seed + r, int(da.offsets_host[0]), item_len).tobytes())
-                assert (int(full[r * n_items, 0]), int(full[r * n_items, 1])) == want, r
-        achieved = bytes_per_rank / kernel_s / 1e9
-        tr = load_traffic(args.workload)
-        roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(achieved / HBM_PEAK_GBS, 4),
-                    "traffic": (tr["hbm_bytes_per_launch"] if tr else None),
-                    "kernel": "xxh3_wave_kernel (K1)", "kernel_ms": round(kernel_s * 1e3, 4),
-                    "kernel_ms_how": f"HIP events around each launch alone on the launch stream, median of {kreps}",
-                    "kernel_ms_back_to_back": round(kernel_b2b_s * 1e3, 4),
-                    "algorithmic_bytes_per_launch": bytes_per_rank}
-        if tr:
-            roofline["traffic_source"] = tr.get("source")
-        prof = load_profile(args.workload)
-        if prof:  # the rocprofv3 kernel-trace average of this same command, committed under profiles/
-            roofline["profile"] = {"avg_ms": prof["avg_ms"], "calls": prof["calls"], "command": prof["command"],
-                                   "source": prof["source"],
-                                   "frac": round(bytes_per_rank / (prof["avg_ms"] / 1e3) / 1e9 / HBM_PEAK_GBS, 4)}
-            if prof.get("timed_region"):  # the profiled launches of the timed steps alone
-                tr = prof["timed_region"]
-                roofline["profile"]["timed_region"] = {"avg_ms": tr["avg_ms"], "launches": tr["launches"],
-                                                       "frac": round(bytes_per_rank / (tr["avg_ms"] / 1e3) / 1e9 / HBM_PEAK_GBS, 4)}
-        cpu = None
-        if not args.no_cpu_baseline and world == 1:  # the CPU baseline is a rank-0, N = 1 figure
-            cpu = cpu_baseline(da, digests, seed, args.cpu_budget)
+                full = to_numpy_u64(table).reshape(-1, 2)
+                for r in range(world):
+                    want = oracle.xxh3_128(splitmix_bytes(args.seed + r, int(da.offsets_host[0]), item_len).tobytes())
+                    assert (int(full[r * n_items, 0]), int(full[r * n_items, 1])) == want, r
+            achieved = bytes_per_rank / kernel_s / 1e9
+            tr = load_traffic(args.workload)
+            roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(achieved / HBM_PEAK_GBS, 4),
+                        "traffic": (tr["hbm_bytes_per_launch"] if tr else None),
+                        "kernel": "xxh3_wave_kernel (K1)", "kernel_ms": round(kernel_s * 1e3, 4),
+                        "kernel_ms_how": f"HIP events around each launch alone on the launch stream, median of {kreps}",
+                        "kernel_ms_back_to_back": round(kernel_b2b_s * 1e3, 4),
+                        "algorithmic_bytes_per_launch": bytes_per_rank}
+            if tr:
+                roofline["traffic_source"] = tr.get("source")
+            prof = load_profile(args.workload)
+            if prof:  # the rocprofv3 kernel-trace average of this same command, committed under profiles/
+                roofline["profile"] = {"avg_ms": prof["avg_ms"], "calls": prof["calls"], "command": prof["command"],
+                                       "source": prof["source"],
+                                       "frac": round(bytes_per_rank / (prof["avg_ms"] / 1e3) / 1e9 / HBM_PEAK_GBS, 4)}
+                if prof.get("timed_region"):  # the profiled launches of the timed steps alone
+                    tr = prof["timed_region"]
+                    roofline["profile"]["timed_region"] = {"avg_ms": tr["avg_ms"], "launches": tr["launches"],
+                                                           "frac": round(bytes_per_rank / (tr["avg_ms"] / 1e3) / 1e9 / HBM_PEAK_GBS, 4)}
+            if not args.no_cpu_baseline and world == 1:  # the CPU baseline is a rank-0, N = 1 figure
+                cpu = cpu_baseline(da, digests, seed, args.cpu_budget)
         result = {
             "metric": METRIC, "value": round(value, 2), "unit": "GiB/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
@@ -460,6 +505,7 @@ def main() -> None:
                                                f"({gather_via if gather_via != 'none' else 'torch gloo rehearsal'})")
                        if multi else "single GPU",
                        "kernel_variant": args.variant or "auto (8: 2-round ring, items > 16 KiB)"},
+            "full": args.full,
             "roofline": roofline,
             "prewarm": {"seconds": round(prewarm_s, 3), "launches": prewarm_launches,
                         "what": "untimed K1 launches over the same tables before the warmup steps (clock ramp)"},

@@ -46,7 +46,7 @@ def test_bench_two_ranks_gloo_one_gpu(cuda):
     """`bench.py --gpus 2` spawns two ranks itself (gloo rehearsal on the one GPU of the test box):
     the JSON line reports n_gpus 2 and rank 0 checked both ranks' digests against the oracle."""
     r = _run(["--gpus", "2", "--backend", "gloo", "--workload", "t", "--steps", "3", "--warmup", "1",
-              "--no-cpu-baseline"])
+              "--full", "--no-cpu-baseline"])
     assert r.returncode == 0, r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(line) == 1, r.stdout
@@ -65,7 +65,7 @@ def test_bench_ranks_abi_gather_fake_rccl(cuda, ranks):
     from oxen_amd import build
 
     r = _run(["--gpus", str(ranks), "--backend", "gloo", "--gather", "abi", "--workload", "t", "--steps", "3",
-              "--warmup", "1", "--no-cpu-baseline", "--prewarm-s", "0"],
+              "--warmup", "1", "--full", "--no-cpu-baseline", "--prewarm-s", "0"],
              env={"OXH_RCCL_LIB": build.FAKE_RCCL, "OXH_FAKE_RCCL_SLOT_BYTES": str(8 << 20)})
     assert r.returncode == 0, r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -73,6 +73,31 @@ def test_bench_ranks_abi_gather_fake_rccl(cuda, ranks):
     d = json.loads(line[0])
     assert d["n_gpus"] == ranks and d["steps"] == 3
     assert "oxh_gather_digests" in d["config"]["parallelism"], d["config"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_last_step_digests(cuda, oracle_lib, tmp_path):
+    """A plain run (no --full) times its steps and prints the line without the roofline / CPU legs;
+    --dump-outputs writes the last step's digest table as exact 32-bit words in float64, equal to the
+    oracle's digests of the regenerated items."""
+    from oxen_amd.workloads import splitmix_bytes
+
+    r = _run(["--gpus", "1", "--workload", "t", "--steps", "2", "--warmup", "1", "--prewarm-s", "0",
+              "--dump-outputs", str(tmp_path / "dump")])
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(line) == 1, r.stdout
+    d = json.loads(line[0])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["full"] is False
+    assert d["roofline"] is None and d["cpu_baseline"] is None
+    words = np.load(tmp_path / "dump" / "digests.npy")
+    rows = np.load(tmp_path / "dump" / "digest_rows.npy")
+    assert words.dtype == np.float64 and words.shape == (2048, 4)
+    assert np.array_equal(rows, np.arange(2048))
+    for i in (0, 1, 1000, 2047):
+        lo, hi = oracle_lib.xxh3_128(splitmix_bytes(2024, i * 65536, 65536).tobytes())
+        want = [lo & 0xFFFFFFFF, lo >> 32, hi & 0xFFFFFFFF, hi >> 32]
+        assert [int(w) for w in words[i]] == want, i
 
 
 def _free_port():

@@ -4,6 +4,8 @@
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp
+# the bench step reports the roofline record and the CPU baseline, which bench.py runs only under --full
+BENCH_ARGS=${BENCH_ARGS:---full --steps 20 --warmup 3}
 mkdir -p gpurun_out
 echo "== pytest -m gpu" && \
 timeout -k 10 900 python -u -m pytest tests -x -v -m gpu --timeout 300 --timeout-method thread > gpurun_out/pytest_gpu.log 2>&1; rc=$?

@@ -17,8 +17,8 @@ step() {  # name, limit, command...
 }
 step pytest 600 python -u -m pytest tests -x -q -m gpu --timeout 300 --timeout-method thread
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-step bench_c2 300 python bench.py --steps 20 --warmup 3
-step bench_c4 300 python bench.py --workload c4 --steps 20 --warmup 3 --no-cpu-baseline
+step bench_c2 300 python bench.py --full --steps 20 --warmup 3
+step bench_c4 300 python bench.py --full --workload c4 --steps 20 --warmup 3 --no-cpu-baseline
 step fastcdc_64k 300 python tools/bench_fastcdc.py --chunk 65536 --reps 5
 step fastcdc_8k 300 python tools/bench_fastcdc.py --chunk 8192 --reps 5
 step c5 600 python tools/bench_c5.py --reps 3

@@ -1,5 +1,5 @@
 #!/bin/bash
-# The driver's own bench command, profiled: one plain run, then the SAME command under
+# The driver's bench command with --full (the roofline and CPU legs), profiled: one run, then the SAME command under
 # rocprofv3 --kernel-trace --stats, summarised by tools/prof_summary.py into
 # profiles/<TAG>_profile_<WORKLOAD>.json (bench.py reports that file's average beside its HIP-event
 # kernel time). With PMC=1 two more passes of a short run of the workload collect FETCH_SIZE and
@@ -17,7 +17,7 @@ case $W in
   c4) ALG=32768000000 ;;    # 125 000 x 262 144 B per launch (one rank's shard of configs[3])
   *) echo "unknown workload $W"; exit 2 ;;
 esac
-CMD="bench.py --gpus 1 --steps 20 --warmup 5"
+CMD="bench.py --gpus 1 --steps 20 --warmup 5 --full"
 [ "$W" != c2 ] && CMD="$CMD --workload $W"
 mkdir -p gpurun_out
 echo "== bench $W"

@@ -1,7 +1,7 @@
 """Summarise a rocprofv3 `--kernel-trace --stats` run of bench.py for the roofline:
 
     python tools/prof_summary.py --stats <dir>/..._kernel_stats.csv --bench <bench json of the same run>
-        --command "python3 bench.py --gpus 1 --steps 20 --warmup 5" --workload c2 --out profiles/r03_profile_c2.json
+        --command "python3 bench.py --gpus 1 --steps 20 --warmup 5 --full" --workload c2 --out profiles/r03_profile_c2.json
 
 Writes the K1 kernel's call count and average duration over EVERY call of the profiled command (no
 call dropped), the bench line that same profiled process printed (its ms_per_step includes the

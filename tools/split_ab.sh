@@ -7,7 +7,7 @@ set -o pipefail
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp
 mkdir -p gpurun_out
-CMD="bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline"
+CMD="bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline"
 for rep in 1 2 3; do
   for v in split presplit; do
     if [ $v = split ]; then RUN="python3 $CMD"; else RUN="python3 tools/with_lib.py tools/ab/presplit/liboxen_hash.so $CMD"; fi
