@@ -18,7 +18,7 @@ SOURCES = [os.path.join(CSRC, f) for f in (
     "xxh3_kernels.hip", "capi_dispatch.hip", "capi_context.hip", "staging.hip", "large_items.hip", "xxh3_stream.hip",
     "engine.hip", "modified.hip", "publish.hip", "fastcdc.hip", "reader_pool.cpp", "comm.cpp", "fastcdc_host.cpp")]
 DEPS = SOURCES + [os.path.join(CSRC, h) for h in ("capi_internal.hpp", "xxh3_device.hpp", "fastcdc_gear.h", "pool.hpp",
-                                                 "scratch.hpp", "reader_pool.hpp")] + [os.path.join(ROOT, "include", "oxen_hash.h")]
+                                                 "scratch.hpp", "reader_pool.hpp", "env.hpp")] + [os.path.join(ROOT, "include", "oxen_hash.h")]
 HELPER_SRC = os.path.join(CSRC, "hash_helper.cpp")
 HELPER = os.path.join(HERE, "oxh_hash_helper")  # the reader-pool helper process (oxh_pool_*)
 ARCH = "gfx950"

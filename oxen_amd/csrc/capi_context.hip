@@ -38,8 +38,7 @@ int usable_cpus() {
 }
 
 int default_threads() {
-    const char* e = getenv("OXH_NUM_THREADS");  // cf. OXEN_NUM_THREADS (util/concurrency.rs:1-45)
-    if (e && atoi(e) > 0) return atoi(e);
+    if (const int n = oxh::env::num_threads()) return n;
     return std::max(1, std::min(usable_cpus(), 16));
 }
 
@@ -112,8 +111,7 @@ int oxh_ctx_create(int device, uint64_t staging_bytes, oxh_ctx** out) {
         c->rq[s].resize(c->max_items);
         c->loc[s].resize(c->max_items);
     }
-    const char* fl = getenv("OXH_FLUSH_MIB");
-    c->flush_bytes = std::min<uint64_t>(c->stage_bytes, (fl ? (uint64_t)atoll(fl) : 16ull) << 20);
+    c->flush_bytes = std::min<uint64_t>(c->stage_bytes, oxh::env::flush_bytes());
     c->pool = new oxh::Pool(default_threads());
     c->rpool = new oxh::Pool(default_threads(), /*private_fds=*/true);  // readers use only their own fds
     c->engine = std::thread(engine_main, c);

@@ -90,9 +90,8 @@ int launch_wave(const uint8_t* arena, const uint64_t* offs, const uint64_t* lens
     if (n == 0) return OXH_OK;
     // waves (items) per workgroup: 4, or the caller's choice; OXH_K1_WG_WAVES (1, 2 or 4) overrides
     // both for A/B. A workgroup's slot is freed only when its longest item is done.
-    const char* wg = getenv("OXH_K1_WG_WAVES");
-    const int e = wg ? atoi(wg) : 0;
-    const int w = (e == 1 || e == 2 || e == 4) ? e : (waves == 1 || waves == 2) ? waves : 4;
+    const int e = oxh::env::k1_wg_waves();
+    const int w = e ? e : (waves == 1 || waves == 2) ? waves : 4;
     const int v = known_variant((variant && g_variant.load() == 0) ? variant : pick_variant(shape));
     const uint64_t per_wg = (uint64_t)w * items_per_wave(v);
     const uint64_t blocks = (n + per_wg - 1) / per_wg;
@@ -143,13 +142,13 @@ namespace oxh {
 // FastCDC's K1 pass (fastcdc.hip) over the packed chunk table. Below a 16 KiB mean chunk K1R (four
 // chunks per wave, one per 16-lane row: tools/k1_small_probe.py, profiles/r04g_k1_small_probe.json),
 // otherwise the block-wise K1 (one chunk per wave; K1R's four streams per wave lose 10 % on 16-128 KiB
-// items); 2 waves per workgroup below 16 KiB, else 4. OXH_K1_PACKED_VARIANT forces a K1 shape (A/B).
+// items); 2 waves per workgroup below 16 KiB, else 4. oxh_set_kernel_variant overrides the shape
+// (launch_wave), for the probe build's A/Bs.
 int k1_packed(const void* d_arena, const uint64_t* d_offsets, const uint64_t* d_lens, uint64_t n, uint64_t* d_out,
               uint64_t mean_len, hipStream_t st) {
     const bool small = mean_len < kShortItemBytes;
-    const char* e = getenv("OXH_K1_PACKED_VARIANT");
-    const int v = (e && atoi(e)) ? atoi(e) : small ? kVariantRows : kVariantPacked;
-    return launch_wave((const uint8_t*)d_arena, d_offsets, d_lens, n, d_out, st, ItemShape::Packed, small ? 2 : 4, v);
+    return launch_wave((const uint8_t*)d_arena, d_offsets, d_lens, n, d_out, st, ItemShape::Packed, small ? 2 : 4,
+                       small ? kVariantRows : kVariantPacked);
 }
 }  // namespace oxh
 

@@ -21,7 +21,6 @@
 #include <sched.h>
 #include <stdint.h>
 #include <string.h>
-#include <sys/mman.h>
 #include <sys/resource.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -41,6 +40,7 @@
 #include <vector>
 
 #include "../../include/oxen_hash.h"
+#include "env.hpp"
 #include "pool.hpp"
 #include "scratch.hpp"
 #include "xxh3_device.hpp"
@@ -80,7 +80,7 @@ int fail(int code, const std::string& msg);
     } while (0)
 
 // OXH_DEBUG_STEPS=1: one stderr line per runtime step (locating stalls without a debugger)
-inline const bool g_steps = getenv("OXH_DEBUG_STEPS") != nullptr;
+inline const bool g_steps = oxh::env::debug_steps();
 #define STEP(...)                                  \
     do {                                           \
         if (::oxh::capi::g_steps) {                \
@@ -188,7 +188,7 @@ void engine_main(oxh_ctx* c);  // the streaming file engine's thread (engine.hip
 
 // OXH_TRACE=1: per-call stage times on stderr (host-side wall clock)
 struct Trace {
-    bool on = getenv("OXH_TRACE") != nullptr;
+    bool on = oxh::env::trace();
     double fill = 0, drain = 0, submit = 0;
     int batches = 0;
     static double now() {
@@ -224,7 +224,7 @@ struct Pending {
 int submit_slot(oxh_ctx* c, int s, uint64_t bytes, uint64_t cnt, bool any_short_only, bool short_items, bool text,
                 bool utf8 = false);
 // A small batch of items below kSlotChainBytes with its descriptors packed after its bytes: one H2D on the
-// compute stream (engine.hip direct_files). `done` false: not taken (does not fit, or disabled).
+// compute stream (engine.hip direct_files). `done` false: not taken (does not fit).
 int submit_packed(oxh_ctx* c, int s, uint64_t bytes, uint64_t cnt, bool short_items, bool text, bool utf8, bool& done,
                   bool lane = false);
 // Wait for slot s's digests (bounded by OXH_WAIT_LIMIT_S, which reports the stalled stage).
@@ -238,7 +238,7 @@ int drain_slot(oxh_ctx* c, int s, Pending& p, uint64_t* out);
 // CU's 160 KiB: one chain per CU.
 constexpr size_t kChainLdsPad = 50 * 1024;
 // Items of a staged batch at least this long (the kChainJobs largest) take K1L instead of a K1 wave
-// (submit_slot). OXH_SLOT_CHAINS=0: every item on a wave (the r01-r06 form, for A/B).
+// (submit_slot).
 constexpr uint64_t kSlotChainBytes = 1ull << 20;
 constexpr uint64_t kSlotCountRaw = 2 * oxh::kChainJobs;
 inline uint64_t slot_sums_words(uint64_t stage_bytes) { return ((stage_bytes >> 10) + 1) * 8; }
@@ -258,10 +258,6 @@ int oversize_item(oxh_ctx* c, const uint8_t* src, uint64_t len, uint64_t* out2, 
 // Where a large item's bytes come from.
 struct LargeSource {
     virtual ~LargeSource() = default;
-    // Pin [off, off + n) in place for an asynchronous H2D copy (no bounce buffer) if this source can:
-    // the host pointer to copy from, or nullptr. unpin() once the copy has completed.
-    virtual const uint8_t* pin(uint64_t, uint64_t) { return nullptr; }
-    virtual void unpin(const uint8_t*) {}
     // [off, off + n) will be read soon.
     virtual void will_need(uint64_t, uint64_t) {}
     // Read [off, off + n) into dst; called from several threads for disjoint ranges. false = I/O error
@@ -270,48 +266,14 @@ struct LargeSource {
     std::atomic<int> os_error{0};
 };
 
-// A regular file: preads, or mmap pages pinned in place for the copy-free path.
+// A regular file, read with pread. (Pinning its page-cache pages in place for the H2D -- mmap, mincore,
+// hipHostRegister -- measured slower than the bounce ring and was removed: large_items.hip.)
 struct FileSource final : LargeSource {
     int fd = -1;
-    uint8_t* map = nullptr;
-    uint64_t len = 0;
-    std::vector<unsigned char> resident;
-    FileSource(const char* path, uint64_t L, bool allow_direct)
-        : FileSource(path ? open(path, O_RDONLY | O_CLOEXEC | O_NONBLOCK) : -1, L, allow_direct) {}
-    // an open descriptor (owned from here on) whose file holds L bytes
-    FileSource(int fd_, uint64_t L, bool allow_direct) : fd(fd_), len(L) {
-        if (fd >= 0 && allow_direct) {
-            void* m = mmap(nullptr, L, PROT_READ, MAP_SHARED, fd, 0);
-            if (m != MAP_FAILED) {
-                map = (uint8_t*)m;
-                (void)madvise(m, L, MADV_SEQUENTIAL);
-            }
-        }
-    }
+    explicit FileSource(const char* path) : FileSource(path ? open(path, O_RDONLY | O_CLOEXEC | O_NONBLOCK) : -1) {}
+    explicit FileSource(int fd_) : fd(fd_) {}  // an open descriptor, owned from here on
     ~FileSource() override {
-        if (map) munmap(map, len);
         if (fd >= 0) close(fd);
-    }
-    // pinning faults missing pages in one thread, so a piece that is mostly on disk is read by the
-    // parallel preads instead
-    bool mostly_resident(uint64_t off, uint64_t n) {
-        const uint64_t pg = (uint64_t)sysconf(_SC_PAGESIZE), npg = (n + pg - 1) / pg;
-        resident.resize(npg);
-        if (mincore(map + off, n, resident.data()) != 0) return false;
-        uint64_t in = 0;
-        for (unsigned char v : resident) in += v & 1;
-        return in * 10 >= npg * 9;
-    }
-    const uint8_t* pin(uint64_t off, uint64_t n) override {
-        if (!map || !mostly_resident(off, n) || hipHostRegister(map + off, n, hipHostRegisterReadOnly) != hipSuccess) {
-            (void)hipGetLastError();
-            return nullptr;
-        }
-        return map + off;
-    }
-    void unpin(const uint8_t* p) override {
-        (void)hipHostUnregister((void*)p);
-        (void)hipGetLastError();
     }
     void will_need(uint64_t off, uint64_t n) override { (void)posix_fadvise(fd, (off_t)off, (off_t)n, POSIX_FADV_WILLNEED); }
     bool read(uint64_t off, uint64_t n, uint8_t* dst) override {

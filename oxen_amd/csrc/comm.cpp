@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/oxen_hash.h"
+#include "env.hpp"
 
 namespace oxh {
 int set_error(int code, const std::string& msg);  // capi_context.hip
@@ -49,7 +50,7 @@ Rccl* rccl() {
     static Rccl r;
     static std::once_flag once;
     std::call_once(once, [] {
-        const char* names[] = {getenv("OXH_RCCL_LIB"), "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
+        const char* names[] = {oxh::env::rccl_lib(), "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
         for (const char* n : names)
             if (n && *n && (r.so = dlopen(n, RTLD_NOW | RTLD_LOCAL)) != nullptr) break;
         if (!r.so) {
@@ -167,8 +168,7 @@ int oxh_gather_digests(oxh_comm* c, const uint64_t* d_local, const uint64_t* cou
     hipStream_t st = (hipStream_t)stream;
     // OXH_GATHER_P2P=1 takes the grouped point-to-point form even for equal shares (tests: the ragged
     // path on a one-GPU box)
-    const char* pe = getenv("OXH_GATHER_P2P");
-    const bool equal = !(pe && atoi(pe) != 0) && std::all_of(counts, counts + P, [&](uint64_t k) { return k == counts[0]; });
+    const bool equal = !oxh::env::gather_p2p() && std::all_of(counts, counts + P, [&](uint64_t k) { return k == counts[0]; });
     const size_t words = 2 * (size_t)counts[0];  // a digest is two u64 (lo, hi)
     int prev = 0;
     (void)hipGetDevice(&prev);

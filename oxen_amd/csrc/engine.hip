@@ -59,12 +59,9 @@ struct SlotRun {  // a submitted slot
 // unlinked since, as the reference's one File handle reads it (hasher.rs:126-148). The first reader
 // keeps its descriptor until every part has opened its own (reading parts meanwhile). Without /proc a
 // part opens the path and checks device + inode; a replaced file is then re-read whole by the engine.
-// OXH_SPLIT_READS=0: one pread per file (the r01-r06 form, for A/B).
+// OXH_SPLIT_READS=0: one pread per file (the r01-r06 form).
 constexpr uint64_t kPartBytes = 4ull << 20, kSplitBytes = 8ull << 20;
-inline bool split_reads() {
-    static const bool on = !(getenv("OXH_SPLIT_READS") && atoi(getenv("OXH_SPLIT_READS")) == 0);
-    return on;
-}
+using oxh::env::split_reads;
 
 struct PartFile {  // one split file, shared by its parts: the reader that finishes the last one completes it
     FileRequest* r = nullptr;
@@ -552,7 +549,7 @@ int big_files(FileStream& fs, const std::vector<std::pair<FileRequest*, uint64_t
             shrunk[q] = true;
             continue;
         }
-        srcs[q].reset(new FileSource(fd, r->lens[i], r->sink == nullptr));
+        srcs[q].reset(new FileSource(fd));
         LargeJob j;
         j.L = r->lens[i], j.src = srcs[q].get(), j.want_counts = r->counts != nullptr, j.want_utf8 = r->utf8 != nullptr;
         j.sink = r->sink, j.id = i;
@@ -686,7 +683,7 @@ void run_stream(oxh_ctx* c) {
     const uint64_t M = c->max_items;
     int rc = hipSetDevice(c->device) == hipSuccess ? OXH_OK : fail(OXH_ERR_HIP, "hipSetDevice failed");
     int s = 0, nbusy = 0;  // s: the slot being filled; the nbusy slots before it are submitted
-    static const double wait_limit = getenv("OXH_WAIT_LIMIT_S") ? atof(getenv("OXH_WAIT_LIMIT_S")) : 60.0;
+    static const double wait_limit = oxh::env::wait_limit_s();
     double last_progress = Trace::now();
     double big_wait_since = 0;  // when the oldest waiting large file was first seen
     while (rc == OXH_OK) {
@@ -923,8 +920,7 @@ constexpr int kDirectDeclined = -1;
 int direct_files(oxh_ctx* c, FileRequest& r) {
     const uint64_t n = r.n;
     if (n > kDirectFiles || n > c->max_items) return kDirectDeclined;
-    const char* env = getenv("OXH_DIRECT_FILES");
-    if (env && atoi(env) == 0) return kDirectDeclined;
+    if (!oxh::env::direct_files()) return kDirectDeclined;
     {
         std::lock_guard<std::mutex> g(c->qmu);
         if (c->live || !c->queue.empty()) return kDirectDeclined;
@@ -1057,7 +1053,7 @@ int hash_files_impl(oxh_ctx* c, const char* const* paths, uint64_t n, uint64_t* 
         c->queue.push_back(&r);
         c->qcv.notify_all();  // the engine (idle) or the live run's idle readers
     }
-    static const double limit = getenv("OXH_WAIT_LIMIT_S") ? atof(getenv("OXH_WAIT_LIMIT_S")) : 60.0;
+    static const double limit = oxh::env::wait_limit_s();
     std::unique_lock<std::mutex> lk(r.mu);
     while (!r.cv.wait_for(lk, std::chrono::duration<double>(limit), [&] { return r.done; })) {
         lk.unlock();

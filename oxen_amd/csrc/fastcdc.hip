@@ -44,6 +44,7 @@
 #include <vector>
 
 #include "../../include/oxen_hash.h"
+#include "env.hpp"
 #include "fastcdc_gear.h"
 #include "scratch.hpp"
 #include "xxh3_device.hpp"
@@ -53,8 +54,6 @@ namespace oxh {
 int set_error(int code, const std::string& msg);  // capi_context.hip: oxh_last_error() text
 int k1_packed(const void* d_arena, const uint64_t* d_offsets, const uint64_t* d_lens, uint64_t n, uint64_t* d_out,
               uint64_t mean_len, hipStream_t st);  // capi_dispatch.hip
-__global__ void xxh3_rows_fold_kernel(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t*,
-                                      const uint64_t*, const uint8_t*);  // xxh3_kernels.hip (K1F)
 
 // fastcdc::v2020::MASKS, indexed by the number of one bits (entries 0..4 are padding)
 static constexpr uint64_t kCdcMasks[26] = {
@@ -183,23 +182,22 @@ __device__ __forceinline__ uint32_t byte_of(const uint4& v, int j) {
 // SIMD (119 VGPRs) instead of 2. The roll is one dependent v_lshl_add_u64 chain per lane, so the
 // third wave's chain fills issue slots (C5 at 8 KiB: F1 26.6 vs 28.2 ms with 8 waves, r02). 16 waves
 // with 64-byte rounds (4 KiB slots, half-line DMA) measured far slower (73 vs 52 ms end to end).
-// OXH_CDC_SCAN_WAVES=8 selects the 8-wave form for A/B.
 constexpr int kScanWaves = 12;
 #ifndef OXH_SCAN_DMA_AUX
 #define OXH_SCAN_DMA_AUX 2
 #endif
 constexpr int kScanDmaAux = OXH_SCAN_DMA_AUX;  // cache policy of the scan's LDS-DMA loads (2 = nt)
 
-template <bool SH, int WAVES>
-__global__ __launch_bounds__(64 * WAVES) void cdc_scan_kernel(CdcFiles f, CdcParams prm, uint64_t n_sec) {
+template <bool SH>
+__global__ __launch_bounds__(64 * kScanWaves) void cdc_scan_kernel(CdcFiles f, CdcParams prm, uint64_t n_sec) {
     // one LDS block: the table at address 0 (a gather address is then a single v_perm), slots after it
-    __shared__ __attribute__((aligned(16))) uint64_t lds[256 * 32 + WAVES * 1024];
+    __shared__ __attribute__((aligned(16))) uint64_t lds[256 * 32 + kScanWaves * 1024];
     for (int i = threadIdx.x; i < 256 * 32; i += blockDim.x) lds[i] = kGear[i >> 5] << (SH ? 16 : 0);
     __syncthreads();
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     uint4* const slot = (uint4*)(lds + 256 * 32) + w * 512;
-    const uint64_t sec = (uint64_t)blockIdx.x * WAVES + (uint64_t)w;
+    const uint64_t sec = (uint64_t)blockIdx.x * kScanWaves + (uint64_t)w;
     if (sec >= n_sec) return;
     const uint32_t file = f.sec_file[sec];
     const uint64_t flen = f.flen[file];
@@ -765,11 +763,8 @@ __global__ __launch_bounds__(1024) void cdc_prefix_kernel(CdcStitch s, uint64_t 
 }
 
 // F3d: the chunk table. One lane per chunk start, grouped by section (a wave per section).
-// c_flag (W2's fold, may be NULL): 1 for a chunk of a section whose list is W's own (its block sums in
-// geo.sums are the chunk's), 0 for the sections X re-walked.
 __global__ __launch_bounds__(256) void cdc_emit_kernel(CdcFiles f, CdcParams prm, CdcStitch s, uint64_t n_sec,
-                                                       uint64_t* __restrict__ c_off, uint64_t* __restrict__ c_len,
-                                                       uint8_t* __restrict__ c_flag) {
+                                                       uint64_t* __restrict__ c_off, uint64_t* __restrict__ c_len) {
     const uint64_t sec = (uint64_t)blockIdx.x * 4 + (uint64_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (sec >= n_sec) return;
     const int lane = threadIdx.x & 63;
@@ -780,16 +775,11 @@ __global__ __launch_bounds__(256) void cdc_emit_kernel(CdcFiles f, CdcParams prm
     const uint32_t* src = s.status[sec] == kFixed ? s.fix + sec * prm.speccap : f.spec + sec * prm.speccap + s.k0[sec];
     const uint64_t base = s.out_base[sec];
     const uint64_t ex = s.exit[sec];
-    const uint8_t own = s.status[sec] == kFixed ? 0 : 1;
     for (uint32_t k = lane; k < cnt; k += 64) {
         const uint64_t a = sec_start + src[k];
         const uint64_t b = k + 1 < cnt ? sec_start + src[k + 1] : ex;
         c_off[base + k] = foff + a;
         c_len[base + k] = b - a;
-        // a chunk that starts within `max` of its section start may overlap the previous section's
-        // last chunk, whose blocks that lane stored too (and a lane that had not yet met the true walk
-        // there stored blocks of chunks that are not the crate's): K1F hashes those from the bytes
-        if (c_flag) c_flag[base + k] = own && src[k] >= prm.max;
     }
 }
 
@@ -850,7 +840,10 @@ constexpr uint32_t kNoCut = 0xFFFFFFFFu;
 
 struct WalkGeom {
     uint64_t arena_bytes;  // the arena holds file bytes up to here (the DMA range stops at it, 16-B rounded)
-    uint64_t* sums;        // FOLD: XXH3 block sums, 8 u64 per 1 KiB of arena (block at arena offset A -> A >> 10)
+    // Always null and never read (it held W2's block sums). Without these 8 bytes of kernel arguments
+    // hipcc orders W's prologue loads and names its SGPRs differently; W is the hottest FastCDC kernel
+    // and under a stop rule, so its compiled body stays the one that was measured.
+    uint64_t* reserved;
 };
 
 // The chunk that starts at m-space position cs: its test window [lo, tL), the mask switch tS and the
@@ -896,25 +889,12 @@ __device__ __forceinline__ void walk_begin_chunk(WalkLane& L, const CdcParams& p
     }
 }
 
-// LATE: the next round's DMA goes out after this round is rolled, when each lane's next line is known
-// (no stale round after a cut, but the DMA's latency is left to the other waves of the SIMD to hide);
-// otherwise it goes out before the roll, for the line after the current one.
-//
-// FOLD (W2, min = 4 KiB, DESIGN §4 "W2"): the walk also folds XXH3's stripe accumulation into the bytes
-// it streams. XXH3-128's long path sums 64-B stripes into 8 accumulators per 1 KiB block and scrambles
-// them between blocks; a block's sum (acc[i] += lo32(w ^ key) * hi32(w ^ key), acc[i ^ 1] += w over its
-// 128 words) does not depend on the accumulators, so W can produce the sums of a chunk's blocks 4..
-// (the bytes after its `min` = 4 blocks, the only ones W reads) and a second pass (K1F) adds blocks 0-3,
-// the partial last block and the last stripe from the bytes and runs each chunk's chain over the stored
-// sums. For that, a lane's lines are chunk-relative: line k of a chunk starting at cs is fetched from
-// (cs + min + 128 k) & ~3 (dword aligned; W proper fetches 128-B aligned lines), so every 8 lines are one
-// block, word q of a line is bytes [cs + min + 128 k + 8 q, + 8) at line byte (cs & 3) + 8 q, realigned
-// with v_alignbyte, and its key is secret word 2 (k % 8) + (q >> 3) + (q & 7) (taken from the lanes that
-// hold the secret, by ds_bpermute: W's LDS is full). Word 15 needs the next line's first dword, so it is
-// folded at the start of the next round. A block's sum goes to geo.sums once its last word is folded;
-// blocks of chunks that start before the lane's section (warm-up) are not stored, and K1F uses a chunk's
-// sums only where the stitch kept W's list (X marks fixed sections).
-template <int WAVES, bool LATE, bool FOLD = false>
+// The next round's DMA goes out before this round is rolled, for the line after the current one. Issuing
+// it after the roll, when each lane's next line is known (no stale round after a cut, but the DMA's
+// latency left to the other waves of the SIMD to hide), was an A/B switch and measured slower.
+// W2, the walk with XXH3's block sums folded in (+ K1F over the sums), measured 55.4 ms for C5 at 8 KiB
+// against 43.5 ms for W + K1R (DESIGN §4 "W2") and was removed.
+template <int WAVES>
 __global__ __launch_bounds__(64 * WAVES) void cdc_walk_scan_kernel(CdcFiles f, CdcParams prm, uint64_t n_sec, WalkGeom geo) {
     __shared__ __attribute__((aligned(16))) uint64_t lds[256 * 32 + WAVES * 1024];
     for (int i = threadIdx.x; i < 256 * 32; i += blockDim.x) lds[i] = kGear[i >> 5] << 16;
@@ -963,8 +943,7 @@ __global__ __launch_bounds__(64 * WAVES) void cdc_walk_scan_kernel(CdcFiles f, C
     uint32_t* __restrict__ out = f.spec + secq * prm.speccap;
     if (live) walk_begin_chunk(L, prm, out);
     const uint32_t a0 = (uint32_t)(prm.min & ~1ull);
-    constexpr uint32_t kLineMask = FOLD ? ~3u : ~127u;  // FOLD: chunk-relative, dword-aligned lines
-    uint32_t NL = L.done ? kWalkOob : ((L.cs + a0) & kLineMask);  // next line to fetch
+    uint32_t NL = L.done ? kWalkOob : ((L.cs + a0) & ~127u);  // next line to fetch
     const uint64_t ms64 = prm.mask_s << 16, ml64 = prm.mask_l << 16;
     const uint32_t ms = (uint32_t)(ms64 >> 32), ml = (uint32_t)(ml64 >> 32), mc = ms & ml;  // host: all bits >= 16
     const uint32_t copy_off = (uint32_t)(lane & 31) * 8;
@@ -991,100 +970,23 @@ __global__ __launch_bounds__(64 * WAVES) void cdc_walk_scan_kernel(CdcFiles f, C
     dma(RL);
     const int rot = (lane >> 1) & 7;
     uint64_t h = 0;
-    // FOLD state: the chunk's block accumulators, its line count, byte shift, the previous line's last
-    // two dwords and its word 15's key (that word is folded next round), whether the chunk's first valid
-    // round is still to come (xfresh: the accumulators restart there), and the secret word this lane
-    // holds for the others' ds_bpermute. The fold itself runs on every round with the whole wave active
-    // (ds_bpermute reads nothing from inactive lanes): what a stale round (the one in flight at a cut)
-    // adds is wiped when the next chunk's first valid round restarts the accumulators.
-    uint64_t xa[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    uint32_t xk = 0, xbs = 0, lag0 = 0, lag1 = 0, klag_lo = 0, klag_hi = 0;
-    bool xlag = false, xfresh = true;
-    const uint64_t sec_w = kSecW[lane < 24 ? lane : 0];
-    const uint32_t sec_lo = (uint32_t)sec_w, sec_hi = (uint32_t)(sec_w >> 32);
-    const uint64_t mbase = base - (uint64_t)f.arena;  // arena offset of m-space 0
-    auto fold_word = [&](uint32_t lo, uint32_t hi, uint32_t klo, uint32_t khi, int i) {
-        xa[i] += (uint64_t)(lo ^ klo) * (uint64_t)(hi ^ khi);
-        xa[i ^ 1] += ((uint64_t)hi << 32) | lo;
-    };
-    // the sum of the chunk's block 4 + (xk - 1) / 8 is complete: store it (recorded chunks only), restart
-    auto fold_store = [&]() {
-        // only chunks starting `max` or more into the lane's section: the previous lane's last chunk
-        // ends within `max` of the section start, and its sums must not be overwritten by a chunk this
-        // lane walked before meeting the true walk (emit flags the chunks in between for K1F's bytes)
-        if (L.cs >= L.mS + (uint32_t)prm.max) {
-            const uint64_t blk = (mbase + (uint64_t)L.cs + (uint64_t)a0 + 1024ull * ((xk - 1) >> 3)) >> 10;
-            uint4* dst = reinterpret_cast<uint4*>(geo.sums + 8 * blk);
-            dst[0] = make_uint4((uint32_t)xa[0], (uint32_t)(xa[0] >> 32), (uint32_t)xa[1], (uint32_t)(xa[1] >> 32));
-            dst[1] = make_uint4((uint32_t)xa[2], (uint32_t)(xa[2] >> 32), (uint32_t)xa[3], (uint32_t)(xa[3] >> 32));
-            dst[2] = make_uint4((uint32_t)xa[4], (uint32_t)(xa[4] >> 32), (uint32_t)xa[5], (uint32_t)(xa[5] >> 32));
-            dst[3] = make_uint4((uint32_t)xa[6], (uint32_t)(xa[6] >> 32), (uint32_t)xa[7], (uint32_t)(xa[7] >> 32));
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) xa[i] = 0;
-    };
-    auto fold_reset = [&]() { xk = 0, xlag = false, xfresh = true, xbs = L.cs & 3u; };
-    if constexpr (FOLD) fold_reset();
 #pragma unroll 1
     for (;;) {
         if (__builtin_amdgcn_ballot_w64(!L.done) == 0) break;
         __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this round's DMA has landed
         uint32_t wv[32];
-        // (FOLD: the 8 slot addresses are recomputed every round rather than held in registers)
-        int rr = rot;
-        if constexpr (FOLD) asm volatile("" : "+v"(rr));
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
-            const uint4 v = slot[lane * 8 + ((q + rr) & 7)];
+            const uint4 v = slot[lane * 8 + ((q + rot) & 7)];
             wv[4 * q] = v.x, wv[4 * q + 1] = v.y, wv[4 * q + 2] = v.z, wv[4 * q + 3] = v.w;
         }
         __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the slot is free for the next DMA
         const uint32_t CL = RL;
         const bool CV = RV && !L.done;
-        if constexpr (FOLD) {
-            // a valid round (CV; not the stale one after a cut) is line xk of the chunk at L.cs: keys
-            // 2 (xk % 8) + 0..8 (words q < 8 take key q, words q >= 8 key q - 7), whole wave active
-            const uint32_t kb = (xk & 7u) * 8u;  // bpermute byte address of key 2 (xk % 8)
-            auto key = [&](int j, uint32_t& lo, uint32_t& hi) {
-                lo = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(kb + 4u * (uint32_t)j), (int)sec_lo);
-                hi = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(kb + 4u * (uint32_t)j), (int)sec_hi);
-            };
-            // word 15 of the previous line; its block may then be complete
-            fold_word(__builtin_amdgcn_alignbyte(lag1, lag0, xbs), __builtin_amdgcn_alignbyte(wv[0], lag1, xbs), klag_lo,
-                      klag_hi, 7);
-            if (CV && xlag && ((xk - 1) & 7u) == 7u) fold_store();
-            if (CV && xfresh) {  // the chunk's first valid round: the accumulators start here
-#pragma unroll
-                for (int i = 0; i < 8; ++i) xa[i] = 0;
-                xfresh = false;
-            }
-            // key j serves word j (j < 8) and word j + 7 (1 <= j <= 7); key 8 is word 15's, next round.
-            // One key in flight ahead of its use keeps the registers down (W2 sits at 3 waves per SIMD).
-            auto word = [&](int q, uint32_t klo, uint32_t khi) {
-                fold_word(__builtin_amdgcn_alignbyte(wv[2 * q + 1], wv[2 * q], xbs),
-                          __builtin_amdgcn_alignbyte(wv[2 * q + 2], wv[2 * q + 1], xbs), klo, khi, q & 7);
-            };
-            uint32_t kl, kh, nkl, nkh;
-            key(0, kl, kh);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                key(j + 1, nkl, nkh);
-                word(j, kl, kh);
-                if (j >= 1) word(j + 7, kl, kh);
-                kl = nkl, kh = nkh;
-            }
-            if (CV) {
-                lag0 = wv[30], lag1 = wv[31], klag_lo = kl, klag_hi = kh;
-                xlag = true;
-                ++xk;
-            }
-        }
-        if constexpr (!LATE) {
-            RL = L.done ? kWalkOob : NL;
-            RV = !L.done;
-            if (!L.done) NL += 128;
-            dma(RL);
-        }
+        RL = L.done ? kWalkOob : NL;
+        RV = !L.done;
+        if (!L.done) NL += 128;
+        dma(RL);
         // this round's mask (see above); tests at positions < lo or >= tL are rejected when resolved
         uint32_t m;
         if (!CV || CL + 128 <= L.lo) m = kWalkFull;
@@ -1092,7 +994,7 @@ __global__ __launch_bounds__(64 * WAVES) void cdc_walk_scan_kernel(CdcFiles f, C
         else if (CL >= L.tS) m = ml;
         else m = mc;
         bool cut_now = false;
-        constexpr int P = FOLD ? 2 : 3;
+        constexpr int P = 3;
         uint64_t G[P + 1][4];
 #pragma unroll
         for (int i = 0; i < P; ++i)
@@ -1137,8 +1039,7 @@ __global__ __launch_bounds__(64 * WAVES) void cdc_walk_scan_kernel(CdcFiles f, C
                             // a cut: the next chunk starts at p (cut_gear returns the matching index)
                             L.cs = p;
                             walk_begin_chunk(L, prm, out);
-                            if constexpr (FOLD) fold_reset();
-                            if (!L.done) NL = (L.cs + a0) & kLineMask;
+                            if (!L.done) NL = (L.cs + a0) & ~127u;
                             RV = false;  // the line in flight belonged to the old chunk
                             m = kWalkFull;
                             cut_now = true;
@@ -1152,26 +1053,10 @@ __global__ __launch_bounds__(64 * WAVES) void cdc_walk_scan_kernel(CdcFiles f, C
         }
         // no cut before the end of the test window: the chunk ends at cs + rem (max, or the file end)
         if (CV && !cut_now && CL + 128 >= L.tL) {
-            if constexpr (FOLD) {
-                // the walk reads no further line of this chunk: a block that ended with the line just
-                // folded (a chunk of 1024 m + 1 bytes at a dword-aligned start) still lacks its word 15,
-                // which then lies wholly in this line (shift 0)
-                if (xlag && xbs == 0 && ((xk - 1) & 7u) == 7u) {
-                    fold_word(lag0, lag1, (uint32_t)S64(176), (uint32_t)(S64(176) >> 32), 7);  // key word 22
-                    fold_store();
-                }
-            }
             L.cs = L.cutm;
             walk_begin_chunk(L, prm, out);
-            if constexpr (FOLD) fold_reset();
-            if (!L.done) NL = (L.cs + a0) & kLineMask;
+            if (!L.done) NL = (L.cs + a0) & ~127u;
             RV = false;
-        }
-        if constexpr (LATE) {
-            RL = L.done ? kWalkOob : NL;
-            RV = !L.done;
-            if (!L.done) NL += 128;
-            dma(RL);
         }
     }
     __builtin_amdgcn_s_waitcnt(0x0F70);  // the last (empty) DMA has landed before the slot goes away
@@ -1581,10 +1466,10 @@ int oxh_fastcdc_device(const void* d_arena, const uint64_t* offsets, const uint6
     // and where its layout rules hold: masks at bit 16 or above, a 128-B aligned arena, every wave's 64
     // sections inside one 4 GiB window, and X's per-section lists within a workgroup's LDS (checked
     // below; where one does not hold the call takes the scan). OXH_CDC_WALK=0 / 1 forces it off / on.
-    const char* walk_env = getenv("OXH_CDC_WALK");
-    const bool walk_forced = walk_env && atoi(walk_env) != 0;
+    const int walk_env = oxh::env::cdc_walk();
+    const bool walk_forced = walk_env == 1;
     bool walk = (((prm.mask_s | prm.mask_l) & 0xFFFFull) == 0) && (((uintptr_t)d_arena & 127) == 0) &&
-                (walk_env ? walk_forced : (avg_size <= 16384));
+                (walk_env >= 0 ? walk_forced : (avg_size <= 16384));
     if (walk_forced && !walk) return cdc_fail(OXH_ERR_INVALID, "OXH_CDC_WALK=1: masks below bit 16 or an unaligned arena");
     int dev = 0;
     (void)hipGetDevice(&dev);
@@ -1592,12 +1477,12 @@ int oxh_fastcdc_device(const void* d_arena, const uint64_t* offsets, const uint6
     if (hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) max_lds = 64 * 1024;
     std::vector<uint64_t> sec_base(n + 1);
     uint64_t n_sec = 0;
+    const long long sec_env = oxh::env::cdc_section_bytes();  // tests: many small sections per file
+    const long long warmup_env = oxh::env::cdc_warmup_bytes();
+    const int cap_env = oxh::env::cdc_unit_cap();
     for (;;) {
         prm.sec = oxh::kSecDefault;
-        if (const char* e = getenv("OXH_CDC_SECTION_BYTES")) {  // tests: many small sections per file
-            const uint64_t v = strtoull(e, nullptr, 10);
-            if (v >= 1024 && v % 1024 == 0 && v <= (1u << 30)) prm.sec = v;
-        }
+        if (sec_env >= 1024 && sec_env % 1024 == 0 && sec_env <= (1 << 30)) prm.sec = (uint64_t)sec_env;
         prm.warmup = std::max<uint64_t>(6 * (uint64_t)max_size, 128 * 1024);
         if (walk) {
             // one lane per section, one generation of 12-wave workgroups on every CU: sections as large
@@ -1606,23 +1491,23 @@ int oxh_fastcdc_device(const void* d_arena, const uint64_t* offsets, const uint6
             if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
             const uint64_t lanes = (uint64_t)cus * oxh::kScanWaves * 64;
             const uint64_t want = (total_bytes + lanes - 1) / std::max<uint64_t>(lanes, 1);
-            if (!getenv("OXH_CDC_SECTION_BYTES")) prm.sec = std::max<uint64_t>({want, 4 * max_rounded, 64 * 1024});
+            if (sec_env < 0) prm.sec = std::max<uint64_t>({want, 4 * max_rounded, 64 * 1024});
             // warm-up: a relaxed walk started anywhere lands on the true one within 14 / 37 / 67 KB in 50 /
             // 90 / 99 % of starts at 8 KiB chunks (C restatement, 1 GiB); X re-walks the sections whose
             // warm-up was too short, so it is kept short: two max-sized chunks
             prm.warmup = 2 * (uint64_t)max_size;
         }
         if (prm.sec < max_rounded) prm.sec = max_rounded;
-        if (!walk && !getenv("OXH_CDC_SECTION_BYTES") && prm.sec < 8 * max_rounded) prm.sec = 8 * max_rounded;
+        if (!walk && sec_env < 0 && prm.sec < 8 * max_rounded) prm.sec = 8 * max_rounded;
         prm.sec = (prm.sec + 8191) / 8192 * 8192;  // 64 F1 units of whole 128-byte rounds
         // a candidate entry holds the group index in 17 bits: units of at most 2 MiB (sections of 128 MiB,
         // 8 chunks of the crate's largest max); the test-only section override is clamped to that
         prm.sec = std::min<uint64_t>(prm.sec, 128ull << 20);
         if (prm.sec < max_rounded) return cdc_fail(OXH_ERR_INVALID, "section override below max_size");
         prm.unit = prm.sec / 64;
-        if (const char* e = getenv("OXH_CDC_WARMUP_BYTES")) prm.warmup = strtoull(e, nullptr, 10);  // tests
+        if (warmup_env >= 0) prm.warmup = (uint64_t)warmup_env;  // tests
         prm.cap = (uint32_t)std::min<double>(prm.unit / 16, 8.0 * dens * prm.unit + 8);
-        if (const char* e = getenv("OXH_CDC_UNIT_CAP")) prm.cap = std::max(1, atoi(e));  // tests: force overflow
+        if (cap_env > 0) prm.cap = (uint32_t)cap_env;  // tests: force overflow
         prm.speccap = (uint32_t)(prm.sec / min_size + 2 + (max_size + min_size - 1) / min_size);
 
         sec_base[0] = 0;
@@ -1654,7 +1539,7 @@ int oxh_fastcdc_device(const void* d_arena, const uint64_t* offsets, const uint6
     }
 
     // OXH_TRACE=1: host-side stage times of this call on stderr
-    static const bool trace = getenv("OXH_TRACE") != nullptr;
+    static const bool trace = oxh::env::trace();
     const auto t_start = std::chrono::steady_clock::now();
     auto since = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); };
     Scratch sc(st);
@@ -1683,22 +1568,6 @@ int oxh_fastcdc_device(const void* d_arena, const uint64_t* offsets, const uint6
     sc.want(&d_exit, n_sec);
     sc.want(&d_fix, n_sec * prm.speccap);
     sc.want(&d_out_base, n_sec + 1);
-    // W2 (the walk with K1's block sums folded in) + K1F: OXH_CDC_FOLD=1 in the probe build
-    // (tools/build_probe_lib.py, -DOXH_PROBE_FOLD), on the walk path with digests asked for and `min` a
-    // whole number of 1 KiB blocks (C5: min 4 KiB). Sums: 64 B per KiB of arena. It measured 55.4 ms
-    // for C5 at 8 KiB against 43.5 for W + K1R (DESIGN §4 "W2"), so the shipped library does not take it.
-#ifdef OXH_PROBE_FOLD
-    const bool fold_env = getenv("OXH_CDC_FOLD") && atoi(getenv("OXH_CDC_FOLD")) != 0;
-#else
-    const bool fold_env = false;  // measured and not kept (DESIGN §4 "W2"): the probe build has it
-#endif
-    const bool fold = fold_env && walk && d_digests && capacity && min_size % 1024 == 0;
-    uint64_t* d_sums = nullptr;
-    uint8_t* d_flag = nullptr;
-    if (fold) {
-        sc.want(&d_sums, ((arena_bytes >> 10) + 4) * 8);
-        sc.want(&d_flag, capacity);
-    }
     CDC_HIP(sc.commit());
     const double t_malloc = since();
     CDC_HIP(hipMemcpyAsync(d_foff, offsets, n * 8, hipMemcpyHostToDevice, st));
@@ -1717,18 +1586,12 @@ int oxh_fastcdc_device(const void* d_arena, const uint64_t* offsets, const uint6
         // W: one lane per section; X twice (every section, then the ones whose assumed entry turned out
         // wrong); the serial pass for whatever is left; then the chunk counts' prefix
         const uint64_t nwaves = (n_sec + 63) / 64;
-        static const bool late = getenv("OXH_CDC_WALK_LATE") && atoi(getenv("OXH_CDC_WALK_LATE")) != 0;
-        auto walk_kernel = late ? oxh::cdc_walk_scan_kernel<oxh::kScanWaves, true> : oxh::cdc_walk_scan_kernel<oxh::kScanWaves, false>;
-#ifdef OXH_PROBE_FOLD
-        if (fold) walk_kernel = oxh::cdc_walk_scan_kernel<oxh::kScanWaves, false, true>;
-#endif
-        hipLaunchKernelGGL(walk_kernel,
+        hipLaunchKernelGGL(oxh::cdc_walk_scan_kernel<oxh::kScanWaves>,
                            dim3((unsigned)((nwaves + oxh::kScanWaves - 1) / oxh::kScanWaves)), dim3(64 * oxh::kScanWaves), 0, st,
-                           f, prm, n_sec, oxh::WalkGeom{arena_bytes, d_sums});
+                           f, prm, n_sec, oxh::WalkGeom{arena_bytes, nullptr});
         CDC_HIP(hipGetLastError());
         const size_t xlds = 2 * (size_t)prm.speccap * sizeof(uint32_t);
-        static const unsigned xgrid = getenv("OXH_CDC_X_WGS") ? (unsigned)atoi(getenv("OXH_CDC_X_WGS")) : 16384u;
-        hipLaunchKernelGGL(oxh::cdc_xwalk_kernel, dim3((unsigned)std::min<uint64_t>(n_sec, xgrid)), dim3(64), xlds, st, f, prm,
+        hipLaunchKernelGGL(oxh::cdc_xwalk_kernel, dim3((unsigned)std::min<uint64_t>(n_sec, 16384)), dim3(64), xlds, st, f, prm,
                            sti, n_sec, d_entry);
         CDC_HIP(hipGetLastError());
         hipLaunchKernelGGL(oxh::cdc_xretry_kernel, dim3((unsigned)((n_sec + 63) / 64)), dim3(64), xlds, st, f, prm, sti, n_sec,
@@ -1742,10 +1605,8 @@ int oxh_fastcdc_device(const void* d_arena, const uint64_t* offsets, const uint6
         // F1: one wave per section (kScanWaves per workgroup, 160 KiB of LDS); SH when the bits both
         // masks share are all >= 16
         const bool sh = (((prm.mask_s & prm.mask_l) << 16) & 0xFFFFFFFFull) == 0;
-        static const int waves = getenv("OXH_CDC_SCAN_WAVES") ? atoi(getenv("OXH_CDC_SCAN_WAVES")) : oxh::kScanWaves;
-        auto scan = waves == 8 ? (sh ? oxh::cdc_scan_kernel<true, 8> : oxh::cdc_scan_kernel<false, 8>)
-                               : (sh ? oxh::cdc_scan_kernel<true, 12> : oxh::cdc_scan_kernel<false, 12>);
-        const int wv = waves == 8 ? 8 : 12;
+        auto scan = sh ? oxh::cdc_scan_kernel<true> : oxh::cdc_scan_kernel<false>;
+        constexpr int wv = oxh::kScanWaves;
         hipLaunchKernelGGL(scan, dim3((unsigned)((n_sec + wv - 1) / wv)), dim3(64 * wv), 0, st, f, prm, n_sec);
         CDC_HIP(hipGetLastError());
         hipLaunchKernelGGL(oxh::cdc_walk_kernel, dim3((unsigned)((n_sec + 255) / 256)), dim3(256), 0, st, f, prm, n_sec);
@@ -1776,7 +1637,7 @@ int oxh_fastcdc_device(const void* d_arena, const uint64_t* offsets, const uint6
     if (total && (!d_chunk_offsets || !d_chunk_lens)) return cdc_fail(OXH_ERR_INVALID, "null chunk table");
     if (n_sec) {
         hipLaunchKernelGGL(oxh::cdc_emit_kernel, dim3((unsigned)((n_sec + 3) / 4)), dim3(256), 0, st, f, prm, sti, n_sec,
-                           d_chunk_offsets, d_chunk_lens, fold ? d_flag : nullptr);
+                           d_chunk_offsets, d_chunk_lens);
         CDC_HIP(hipGetLastError());
     }
     if (d_digests && total) {
@@ -1784,16 +1645,7 @@ int oxh_fastcdc_device(const void* d_arena, const uint64_t* offsets, const uint6
         // otherwise (oxh::k1_packed)
         uint64_t bytes = 0;
         for (uint64_t i = 0; i < n; ++i) bytes += lens[i];
-        if (fold) {  // K1F: blocks 0-3 and the tail from the bytes, blocks 4.. from W2's sums
-#ifdef OXH_PROBE_FOLD
-            hipLaunchKernelGGL(oxh::xxh3_rows_fold_kernel, dim3((unsigned)((total + 7) / 8)), dim3(128), 0, st,
-                               (const uint8_t*)d_arena, d_chunk_offsets, d_chunk_lens, total, d_digests, d_sums, d_flag);
-#endif
-            rc = hipGetLastError() == hipSuccess ? OXH_OK : OXH_ERR_HIP;
-            if (rc) oxh::set_error(rc, "K1F launch");
-        } else {
-            rc = oxh::k1_packed(d_arena, d_chunk_offsets, d_chunk_lens, total, d_digests, bytes / total, st);
-        }
+        rc = oxh::k1_packed(d_arena, d_chunk_offsets, d_chunk_lens, total, d_digests, bytes / total, st);
         if (rc) return cdc_fail(rc, std::string("chunk digests: ") + oxh_last_error());
     }
     CDC_HIP(hipStreamSynchronize(st));

@@ -41,6 +41,7 @@
 #include <vector>
 
 #include "../../include/oxen_hash.h"
+#include "env.hpp"
 #include "pool.hpp"
 
 namespace oxh {
@@ -53,49 +54,16 @@ int default_reader_threads();                               // ... OXH_NUM_THREA
 
 namespace {
 
-constexpr int kCdcMaxBounce = 16;
-// one pinned bounce buffer (a window of the piece): OXH_CDC_BOUNCE_MIB, 16..256 (a power of two),
-// default 64
-uint64_t cdc_bounce() {
-    static const uint64_t v = [] {
-        const char* e = getenv("OXH_CDC_BOUNCE_MIB");
-        const long k = e ? atol(e) : 64;
-        uint64_t m = 16;
-        while (m < 256 && (long)m < k) m <<= 1;
-        return m << 20;
-    }();
-    return v;
-}
-// the ring: reads of the next windows run while earlier H2Ds drain (OXH_CDC_NBOUNCE, 2..16, default 8:
-// 47.7 vs 43.6 GiB/s for 4 on 16 x 1 GiB from the page cache, profiles/r05/r05a_e2e_*)
-// H2D copy streams the windows alternate over (OXH_CDC_COPY_STREAMS, 1 or 2; default 2: C5 from the
-// page cache 2.57-2.64 s against 2.91-2.92 s with one, alternating on one box, profiles/r05/r05e_shm_cs*)
-int cdc_copy_streams() {
-    static const int v = [] {
-        const char* e = getenv("OXH_CDC_COPY_STREAMS");
-        return e && atoi(e) == 1 ? 1 : 2;
-    }();
-    return v;
-}
+// the pinned bounce ring: OXH_CDC_NBOUNCE windows of OXH_CDC_BOUNCE_MIB (env.hpp). The windows' H2Ds
+// alternate over two copy streams: C5 from the page cache 2.57-2.64 s against 2.91-2.92 s with one,
+// alternating on one box (profiles/r05/r05e_shm_cs*).
+constexpr int kCdcMaxBounce = oxh::env::kCdcNBounceMax;
+using oxh::env::cdc_nbounce;
+inline uint64_t cdc_bounce() { return oxh::env::cdc_bounce_bytes(); }
 // Fixed-size rounds of at most this many segments hash each segment as one implied chunk grid
 // (oxh_chunk_digests_device: no descriptor tables built on the host or copied over the link); more
-// segments (many small files) take one launch over descriptors. OXH_FIXED_IMPLICIT_SEGS, 0 = always
-// descriptors.
-int fixed_implicit_segs() {
-    static const int v = [] {
-        const char* e = getenv("OXH_FIXED_IMPLICIT_SEGS");
-        return e ? std::max(0, atoi(e)) : 8;
-    }();
-    return v;
-}
-int cdc_nbounce() {
-    static const int v = [] {
-        const char* e = getenv("OXH_CDC_NBOUNCE");
-        const int k = e ? atoi(e) : 8;
-        return std::max(2, std::min(k, kCdcMaxBounce));
-    }();
-    return v;
-}
+// segments (many small files) take one launch over descriptors.
+constexpr size_t kFixedImplicitSegs = 8;
 constexpr uint64_t kCdcPart = 4ull << 20;     // one reader task
 constexpr uint64_t kCdcAlign = 256;           // segment placement in a piece
 constexpr uint64_t kProbeWindow = 256;        // files opened (and stat'ed) ahead of the planner, at most
@@ -135,8 +103,7 @@ inline uint64_t align_up(uint64_t x) { return (x + kCdcAlign - 1) & ~(kCdcAlign 
 struct CdcHost {
     int device = 0;
     hipStream_t copy = nullptr, comp = nullptr;
-    hipStream_t copy2 = nullptr;  // a second copy stream (OXH_CDC_COPY_STREAMS=2): windows alternate
-    int ncopy = 1;
+    hipStream_t copy2 = nullptr;  // the second copy stream: windows alternate
     uint64_t piece = 0;
     uint8_t* d_piece[2] = {};
     hipEvent_t ev_copied[2] = {}, ev_copied2[2] = {};
@@ -203,7 +170,7 @@ void free_cdc_host(void* p) { delete static_cast<CdcHost*>(p); }
 int cdc_host(oxh_ctx* ctx, uint64_t piece, CdcHost** out) {
     void*& slot = oxh::ctx_cdc_state(ctx, free_cdc_host);
     CdcHost* h = static_cast<CdcHost*>(slot);
-    if (h && h->piece == piece && h->nbounce == cdc_nbounce() && h->ncopy == cdc_copy_streams()) {
+    if (h && h->piece == piece && h->nbounce == cdc_nbounce()) {
         *out = h;
         return OXH_OK;
     }
@@ -218,10 +185,9 @@ int cdc_host(oxh_ctx* ctx, uint64_t piece, CdcHost** out) {
         return oxh::set_error(code, std::string("FastCDC host pipeline: ") + what);
     };
     if (hipStreamCreateWithFlags(&h->copy, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&h->comp, hipStreamNonBlocking) != hipSuccess)
+        hipStreamCreateWithFlags(&h->comp, hipStreamNonBlocking) != hipSuccess ||
+        hipStreamCreateWithFlags(&h->copy2, hipStreamNonBlocking) != hipSuccess)
         return bad(OXH_ERR_HIP, "streams");
-    h->ncopy = cdc_copy_streams();
-    if (h->ncopy == 2 && hipStreamCreateWithFlags(&h->copy2, hipStreamNonBlocking) != hipSuccess) return bad(OXH_ERR_HIP, "streams");
     for (int b = 0; b < 2; ++b) {
         if (hipMalloc(&h->d_piece[b], piece + 4096) != hipSuccess) return bad(OXH_ERR_NOMEM, "device piece buffers");
         if (hipEventCreateWithFlags(&h->ev_copied[b], hipEventDisableTiming) != hipSuccess ||
@@ -428,7 +394,7 @@ bool fixed_round(Call& C, const Round& R) {
     // chunks over [poff, poff + hi - lo) of the piece: with few segments, one grid launch each
     size_t live = 0;
     for (size_t j = 0; j < R.segs.size(); ++j) live += first[j + 1] > first[j];
-    const bool implicit = live <= (size_t)fixed_implicit_segs();
+    const bool implicit = live <= kFixedImplicitSegs;
     for (size_t j = 0; rc == OXH_OK && !implicit && j < R.segs.size(); ++j) {
         const Seg& s = R.segs[j];
         for (uint64_t k = first[j], o = s.lo; k < first[j + 1]; ++k, o += ck) {
@@ -441,7 +407,7 @@ bool fixed_round(Call& C, const Round& R) {
          hipMemcpyAsync(h.d_len, h.h_len, m * 8, hipMemcpyHostToDevice, h.comp) != hipSuccess))
         rc = oxh::set_error(OXH_ERR_HIP, "chunk descriptors H2D");
     if (rc == OXH_OK && (hipStreamWaitEvent(h.comp, h.ev_copied[R.b], 0) != hipSuccess ||
-                         (h.ncopy == 2 && hipStreamWaitEvent(h.comp, h.ev_copied2[R.b], 0) != hipSuccess)))
+                         hipStreamWaitEvent(h.comp, h.ev_copied2[R.b], 0) != hipSuccess))
         rc = oxh::set_error(OXH_ERR_HIP, "wait copies");
     if (rc == OXH_OK && m && !implicit)
         rc = oxh_xxh3_128_batch_device(h.d_piece[R.b], h.d_off, h.d_len, m, h.d_dig,
@@ -522,7 +488,7 @@ void chunk_rounds(Call& C) {
         const uint64_t need = oxh_fastcdc_max_chunks(lens.data(), m, C.mn) + 1;
         int rc = h.tables(need);
         if (rc == OXH_OK && (hipStreamWaitEvent(h.comp, h.ev_copied[R.b], 0) != hipSuccess ||
-                             (h.ncopy == 2 && hipStreamWaitEvent(h.comp, h.ev_copied2[R.b], 0) != hipSuccess)))
+                             hipStreamWaitEvent(h.comp, h.ev_copied2[R.b], 0) != hipSuccess))
             rc = oxh::set_error(OXH_ERR_HIP, "wait copies");
         if (rc == OXH_OK)
             rc = oxh_fastcdc_device(h.d_piece[R.b], offs.data(), lens.data(), m, C.mn, C.av, C.mx, C.lv, h.d_off, h.d_len,
@@ -588,7 +554,7 @@ int upload_round(Call& C, const Round& R) {
         W.grp.wait();
         C.t_read_wait += now() - tw;
         if (W.used == 0) return OXH_OK;
-        hipStream_t cs = (h.ncopy == 2 && (W.base / bounce) % 2) ? h.copy2 : h.copy;
+        hipStream_t cs = (W.base / bounce) % 2 ? h.copy2 : h.copy;
         if (hipMemcpyAsync(h.d_piece[R.b] + W.base, h.h_bounce[W.bb], W.used, hipMemcpyHostToDevice, cs) != hipSuccess ||
             hipEventRecord(h.ev_bounce[W.bb], cs) != hipSuccess)
             return oxh::set_error(OXH_ERR_HIP, "piece H2D");
@@ -632,7 +598,7 @@ int upload_round(Call& C, const Round& R) {
         if (rc == OXH_OK) rc = r2;
     }
     if (rc == OXH_OK && (hipEventRecord(h.ev_copied[R.b], h.copy) != hipSuccess ||
-                         (h.ncopy == 2 && hipEventRecord(h.ev_copied2[R.b], h.copy2) != hipSuccess)))
+                         hipEventRecord(h.ev_copied2[R.b], h.copy2) != hipSuccess))
         rc = oxh::set_error(OXH_ERR_HIP, "copy event");
     return rc;
 }
@@ -677,8 +643,7 @@ int run(oxh_ctx* ctx, CdcSource& src, uint64_t n, uint32_t mn, uint32_t av, uint
     (void)hipSetDevice(oxh::ctx_device(ctx));
     // pieces of OXH_CDC_PIECE_MIB (default 1 GiB), at least two minimal segments (one for a fixed chunk
     // size above 1 GiB)
-    const char* pe = getenv("OXH_CDC_PIECE_MIB");
-    uint64_t piece = (pe && atoll(pe) > 0 ? (uint64_t)atoll(pe) : 1024ull) << 20;
+    uint64_t piece = oxh::env::cdc_piece_bytes();
     piece = std::max<uint64_t>(piece, fixed > (1ull << 30) ? min_seg + kCdcAlign : 2 * min_seg);
     piece = std::min<uint64_t>(piece, 3ull << 30);
     piece = (piece + cdc_bounce() - 1) / cdc_bounce() * cdc_bounce();
@@ -691,7 +656,7 @@ int run(oxh_ctx* ctx, CdcSource& src, uint64_t n, uint32_t mn, uint32_t av, uint
     C.files = std::vector<FileState>(n);
     first_chunk[0] = 0;
     const FdBudget fdb = src.holds_fds() ? fd_budget(shares) : FdBudget{};
-    static const bool trace = getenv("OXH_TRACE") != nullptr;
+    static const bool trace = oxh::env::trace();
     const double t_start = now();
     std::thread chunker(chunk_rounds, std::ref(C));
 

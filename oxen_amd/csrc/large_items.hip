@@ -16,8 +16,7 @@ namespace oxh::capi {
 // instead of after every buffer's, and the block-sum scratch is two rounds of pieces, not the whole
 // input. Returns after `st` has finished.
 int large_batch_device(const uint8_t* const* bufs, const uint64_t* lens, uint64_t n, uint64_t* d_out, hipStream_t st) {
-    const char* pe = getenv("OXH_BIG_PIECE_MIB");
-    const uint64_t P = std::max<uint64_t>(1, pe ? strtoull(pe, nullptr, 10) : 1024) << 20;
+    const uint64_t P = oxh::env::big_piece_bytes();
     std::vector<uint64_t> big;  // buffers on the chained path
     uint64_t rounds = 0;
     auto pieces_of = [&](uint64_t len) { return (len > P + 1024 ? (len - 1025) / P : 0) + 1; };
@@ -154,40 +153,20 @@ int oversize_item(oxh_ctx* c, const uint8_t* src, uint64_t len, uint64_t* out2, 
 // buffers, so device memory stays bounded whatever the item size and piece j+1's transfer overlaps
 // piece j's K1L chain: each piece's block sums are computed chip-wide and the serial chain continues
 // from the previous piece's accumulators (ChainJob kChainResume / kChainPartial); the last piece
-// (> 1 KiB) takes the tail and the merge. A file piece reaches the device copy-free when its pages
-// are in the page cache (mincore) and can be pinned (mmap + hipHostRegister read-only, ~2 ms per GiB;
-// the DMA engine then reads them at 46-57 GB/s, tools/mmap_register_probe.hip); otherwise pieces pass
-// through two pinned 64 MiB bounce buffers filled by the worker pool (parallel 4 MiB reads). Text
+// (> 1 KiB) takes the tail and the merge. Pieces pass through a ring of pinned 64 MiB bounce buffers
+// filled by the worker pool (parallel 4 MiB reads). Pinning a file's page-cache pages in place for a
+// copy-free H2D (mmap + mincore + hipHostRegister, tools/mmap_register_probe.hip) measured 10-27 ms per
+// GiB to register and ~10 ms per GiB to release on the MI355X boxes (r03), more than the 16 pool
+// threads take to copy the same bytes into the bounce buffers, and was removed. Text
 // counts accumulate over the pieces; is_utf8 reads the first 4 KiB of piece 0. With a sink (fused
 // add) every bounce part is also written to the sink's temp as it is read, and the temp is published
 // once the digest is known: the item never has to fit in host memory.
 
-// Bounce windows a large item reads at once (OXH_BIG_WINDOWS, 1 .. kNBounce - 1; 1 is the r03-r04 form)
-int big_windows() {
-    static const int v = [] {
-        const char* e = getenv("OXH_BIG_WINDOWS");
-        const int k = e ? atoi(e) : kNBounce - 1;
-        return std::max(1, std::min(k, kNBounce - 1));
-    }();
-    return v;
-}
+// Bounce windows a large item reads at once (one at a time was the r03-r04 form)
+constexpr int kBigWindows = kNBounce - 1;
 
-// H2D copy streams a large item's bounce windows alternate over (OXH_BIG_COPY_STREAMS, 1 or 2; default 2)
-int big_copy_streams() {
-    static const int v = [] {
-        const char* e = getenv("OXH_BIG_COPY_STREAMS");
-        return e && atoi(e) == 1 ? 1 : 2;
-    }();
-    return v;
-}
-
-// Files up to this many at a time share one large-item pipeline (OXH_BIG_FILES overrides; device
-// memory: 2 piece buffers of OXH_BIG_PIECE_MIB + 1 KiB per file).
-int big_files_at_once() {
-    const char* e = getenv("OXH_BIG_FILES");
-    const int v = e && atoi(e) > 0 ? atoi(e) : 4;
-    return std::min(v, (int)oxh::kChainJobs);
-}
+// Files up to this many at a time share one large-item pipeline (OXH_BIG_FILES, env.hpp).
+int big_files_at_once() { return std::min(oxh::env::big_files(), (int)oxh::kChainJobs); }
 
 // Hash n (<= kChainJobs) large items side by side (see above). Round r moves piece r of every item
 // that has one to the device (the copies are PCIe-bound and serial on the copy stream), launches its
@@ -199,8 +178,7 @@ int big_files_at_once() {
 int large_items(oxh_ctx* c, LargeJob* jobs, int n) {
     if (n <= 0) return OXH_OK;
     if (n > (int)oxh::kChainJobs) return fail(OXH_ERR_INVALID, "too many large items in one batch");
-    const uint64_t P = std::max<uint64_t>(
-        1, getenv("OXH_BIG_PIECE_MIB") ? strtoull(getenv("OXH_BIG_PIECE_MIB"), nullptr, 10) : 1024) << 20;
+    const uint64_t P = oxh::env::big_piece_bytes();
     const uint64_t cap = P + 1024;  // bytes per piece buffer
     const uint64_t slot = align_up(cap) + 256;
     constexpr uint64_t kRes = 256;  // per item: [digest 2 | counts 2 | desc off, len | utf8 | state 8]
@@ -337,7 +315,7 @@ int large_items(oxh_ctx* c, LargeJob* jobs, int n) {
             if (!ok) return;
             // windows alternate over two copy streams: two DMA queues keep the PCIe link busier (the
             // FastCDC host pipeline measured 53.5 vs 47 GB/s)
-            hipStream_t cs = (big_copy_streams() == 2 && ((W.o / kBounce) & 1)) ? c->copy_stream2 : c->copy_stream;
+            hipStream_t cs = ((W.o / kBounce) & 1) ? c->copy_stream2 : c->copy_stream;
             if (hipMemcpyAsync(d + W.o, c->h_bounce[W.bb], W.m, hipMemcpyHostToDevice, cs) != hipSuccess ||
                 hipEventRecord(c->ev_bounce[W.bb], cs) != hipSuccess) {
                 ok = false;
@@ -379,7 +357,7 @@ int large_items(oxh_ctx* c, LargeJob* jobs, int n) {
             };
             c->pool->start((int)((m + kBigRead - 1) / kBigRead), W.fn, W.grp);
             inflight.push_back(&W);
-            if ((int)inflight.size() >= big_windows()) {
+            if ((int)inflight.size() >= kBigWindows) {
                 finish(*inflight.front());
                 inflight.pop_front();
             }
@@ -397,35 +375,13 @@ int large_items(oxh_ctx* c, LargeJob* jobs, int n) {
         // overlap this piece's last copies
         return ok;
     };
-    // With OXH_BIG_DIRECT=1, pieces whose pages are in the page cache are pinned in place and copied
-    // asynchronously; the next round's pieces are pinned while this round's copies run, and a round's
-    // pins are released once its copies are done.
-    std::vector<const uint8_t*> pinned(n, nullptr), next_pin(n, nullptr);
-    std::vector<std::pair<int, const uint8_t*>> to_unpin;  // (item, pinned range) of copies in flight
     auto piece_len = [&](int q, uint64_t r) { return r < st[q].k ? P : jobs[q].L - r * P; };
-    // Pinning page-cache pages in place (OXH_BIG_DIRECT=1) measured 10-27 ms per GiB to register and
-    // ~10 ms per GiB to release on the MI355X boxes (r03, OXH_TRACE), more than the 16 pool threads take
-    // to copy the same bytes into the pinned bounce buffers; the bounce path is the default.
-    const bool may_pin = getenv("OXH_BIG_DIRECT") && atoi(getenv("OXH_BIG_DIRECT")) != 0;
-    auto pin_round = [&](uint64_t r, std::vector<const uint8_t*>& into) {
-        if (!may_pin) return;
-        for (int q = 0; q < n; ++q) {
-            if (into[q]) jobs[q].src->unpin(into[q]);
-            into[q] = (!jobs[q].sink && st[q].io_ok && r <= st[q].k) ? jobs[q].src->pin(r * P, piece_len(q, r)) : nullptr;
-        }
-    };
     Trace tr;  // OXH_TRACE=1: where a batch's host time goes
-    double t_pin = 0, t_wait = 0, t_unpin = 0, t_bounce = 0;
+    double t_bounce = 0;
     const double t_start = Trace::now();
-    {
-        const double t0 = Trace::now();
-        pin_round(0, next_pin);
-        t_pin += Trace::now() - t0;
-    }
     bool round_used[2] = {false, false};
     for (uint64_t r = 0; r < rounds && rc == OXH_OK; ++r) {
         const int b = (int)(r & 1);
-        pinned.swap(next_pin);
         // the chains of round r-2 (which read buffers b and their block sums) are done
         c->where.store("large_items: piece free");
         if (round_used[b] && hipEventSynchronize(c->ev_piece_free[b]) != hipSuccess) {
@@ -436,33 +392,19 @@ int large_items(oxh_ctx* c, LargeJob* jobs, int n) {
         int nj = 0;
         for (int q = 0; q < n; ++q) {
             State& S = st[q];
-            if (!S.io_ok || r > S.k) {
-                if (pinned[q]) jobs[q].src->unpin(pinned[q]);  // pinned ahead, before the item failed
-                pinned[q] = nullptr;
-                continue;
-            }
+            if (!S.io_ok || r > S.k) continue;
             const uint64_t off = r * P, plen = piece_len(q, r);
             uint8_t* d = dbuf(q, b);
-            if (pinned[q]) {  // copy-free: the DMA engine reads the page cache (a sink must see host bytes)
-                if (hipMemcpyAsync(d, pinned[q], plen, hipMemcpyHostToDevice, c->copy_stream) != hipSuccess ||
-                    hipEventRecord(ev_copy[q], c->copy_stream) != hipSuccess) {
-                    rc = fail(OXH_ERR_HIP, "large-item piece copy");
-                    break;
-                }
-                to_unpin.push_back({q, pinned[q]});
-                pinned[q] = nullptr;
-            } else {
-                const double t0 = Trace::now();
-                const bool copied = copy_piece(q, off, plen, d);
-                t_bounce += Trace::now() - t0;
-                if (!copied) {
-                    S.io_ok = false;  // its earlier chains finish harmlessly; the item is reported as unreadable
-                    continue;
-                }
-                if (hipEventRecord(ev_copy[q], c->copy_stream) != hipSuccess) {
-                    rc = fail(OXH_ERR_HIP, "large-item piece event");
-                    break;
-                }
+            const double t0 = Trace::now();
+            const bool copied = copy_piece(q, off, plen, d);
+            t_bounce += Trace::now() - t0;
+            if (!copied) {
+                S.io_ok = false;  // its earlier chains finish harmlessly; the item is reported as unreadable
+                continue;
+            }
+            if (hipEventRecord(ev_copy[q], c->copy_stream) != hipSuccess) {
+                rc = fail(OXH_ERR_HIP, "large-item piece event");
+                break;
             }
             if (hipStreamWaitEvent(c->stream, ev_copy[q], 0) != hipSuccess) {
                 rc = fail(OXH_ERR_HIP, "large-item piece wait");
@@ -487,28 +429,10 @@ int large_items(oxh_ctx* c, LargeJob* jobs, int n) {
         if (hipGetLastError() != hipSuccess || hipEventRecord(c->ev_piece_free[b], c->stream) != hipSuccess)
             rc = fail(OXH_ERR_HIP, "large-item piece launch");
         round_used[b] = true;
-        double t0 = Trace::now();
-        if (r + 1 < rounds) pin_round(r + 1, next_pin);  // while this round's copies run
-        t_pin += Trace::now() - t0;
-        if (!to_unpin.empty()) {
-            t0 = Trace::now();
-            if (hipStreamSynchronize(c->copy_stream) != hipSuccess && rc == OXH_OK) rc = fail(OXH_ERR_HIP, "large-item copy");
-            t_wait += Trace::now() - t0;
-            t0 = Trace::now();
-            for (const auto& u : to_unpin) jobs[u.first].src->unpin(u.second);
-            t_unpin += Trace::now() - t0;
-            to_unpin.clear();
-        }
     }
-    // a failure mid-way: release what is still pinned
     c->where.store("large_items: final copy sync");
     if (hipStreamSynchronize(c->copy_stream) != hipSuccess && rc == OXH_OK) rc = fail(OXH_ERR_HIP, "large-item copy");
     if (hipStreamSynchronize(c->copy_stream2) != hipSuccess && rc == OXH_OK) rc = fail(OXH_ERR_HIP, "large-item copy");
-    for (int q = 0; q < n; ++q) {
-        if (pinned[q]) jobs[q].src->unpin(pinned[q]);
-        if (next_pin[q]) jobs[q].src->unpin(next_pin[q]);
-    }
-    for (const auto& u : to_unpin) jobs[u.first].src->unpin(u.second);
     if (rc == OXH_OK && hipMemcpyAsync(h_res.data(), d_res_all, h_res.size(), hipMemcpyDeviceToHost, c->stream) != hipSuccess)
         rc = fail(OXH_ERR_HIP, "large-item results D2H");
     const double t_tail0 = Trace::now();
@@ -516,9 +440,8 @@ int large_items(oxh_ctx* c, LargeJob* jobs, int n) {
     if (hipStreamSynchronize(c->stream) != hipSuccess && rc == OXH_OK) rc = fail(OXH_ERR_HIP, "large-item sync");
     c->where.store("large_items: publish");
     if (tr.on)
-        fprintf(stderr, "[oxh] large_items n=%d rounds=%llu piece=%llu MiB: total %.1f ms, pin %.1f, copy wait %.1f, unpin %.1f, "
-                "bounce %.1f, chain tail %.1f\n", n, (unsigned long long)rounds, (unsigned long long)(P >> 20),
-                1e3 * (Trace::now() - t_start), 1e3 * t_pin, 1e3 * t_wait, 1e3 * t_unpin, 1e3 * t_bounce,
+        fprintf(stderr, "[oxh] large_items n=%d rounds=%llu piece=%llu MiB: total %.1f ms, bounce %.1f, chain tail %.1f\n", n,
+                (unsigned long long)rounds, (unsigned long long)(P >> 20), 1e3 * (Trace::now() - t_start), 1e3 * t_bounce,
                 1e3 * (Trace::now() - t_tail0));
     std::vector<ItemSink*> sinks;
     for (int q = 0; q < n; ++q) {

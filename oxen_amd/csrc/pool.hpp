@@ -15,6 +15,8 @@
 #include <thread>
 #include <vector>
 
+#include "env.hpp"
+
 namespace oxh {
 // A worker of a pool made with private_fds gets a file-descriptor table of its own: it calls
 // unshare(CLONE_FILES) and drops every descriptor the copy inherited (stdin/out/err stay), so the
@@ -25,8 +27,7 @@ namespace oxh {
 // private tables. Only for workers that use nothing but the descriptors they open themselves (the
 // streaming readers). OXH_SHARED_FDS=1 turns it off.
 inline void make_fd_table_private() {
-    const char* e = getenv("OXH_SHARED_FDS");
-    if (e && atoi(e) != 0) return;
+    if (env::shared_fds()) return;
     if (unshare(CLONE_FILES) != 0) return;  // keep sharing: correct, just slower
 #ifdef SYS_close_range
     if (syscall(SYS_close_range, 3u, ~0u, 0u) == 0) return;
@@ -45,16 +46,9 @@ inline void make_fd_table_private() {
 // The file engine's thread polls its slots' events in 20 us timed waits while a slot is in flight;
 // Linux stretches every such wait by the thread's timer slack, 50 us by default, so a one-file request
 // paid 50-70 us oversleeps end to end (tools/latency_probe.py). The engine thread runs with a slack of
-// OXH_TIMER_SLACK_NS (default 1000 ns; 0 keeps the kernel's default). The pools' threads (readers that
-// wait 2-5 us for a slot, copiers) and callers' threads keep theirs: tighter reader waits would spin
-// the 16 readers against each other on a CPU-bound walk.
-inline void runtime_thread_timer_slack() {
-    static const long ns = [] {
-        const char* e = getenv("OXH_TIMER_SLACK_NS");
-        return e ? atol(e) : 1000L;
-    }();
-    if (ns > 0) (void)prctl(PR_SET_TIMERSLACK, (unsigned long)ns, 0, 0, 0);
-}
+// 1000 ns. The pools' threads (readers that wait 2-5 us for a slot, copiers) and callers' threads keep
+// theirs: tighter reader waits would spin the 16 readers against each other on a CPU-bound walk.
+inline void runtime_thread_timer_slack() { (void)prctl(PR_SET_TIMERSLACK, 1000ul, 0, 0, 0); }
 
 class Pool {
    public:
@@ -143,13 +137,8 @@ class Pool {
                 std::unique_lock<std::mutex> lk(mu_);
                 cv_.wait(lk, [&] { return stop_ || !q_.empty(); });
                 if (stop_ && q_.empty()) return;
-                if (lifo_) {  // OXH_POOL_LIFO=1: last in, first out (the r04 order; for A/Bs)
-                    job = std::move(q_.back());
-                    q_.pop_back();
-                } else {
-                    job = std::move(q_.front());  // first in, first out: a caller waiting on its oldest
-                    q_.pop_front();               // group (the bounce windows) gets it done first
-                }
+                job = std::move(q_.front());  // first in, first out: a caller waiting on its oldest
+                q_.pop_front();               // group (the bounce windows) gets it done first
                 ++busy_;
             }
             job();
@@ -160,7 +149,6 @@ class Pool {
             idle_cv_.notify_all();
         }
     }
-    const bool lifo_ = getenv("OXH_POOL_LIFO") && atoi(getenv("OXH_POOL_LIFO")) != 0;
     std::vector<std::thread> th_;
     std::deque<std::function<void()>> q_;
     std::mutex mu_;

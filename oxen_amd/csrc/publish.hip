@@ -66,8 +66,7 @@ class VersionPublisher final : public ItemSink {
    public:
     VersionPublisher(oxh_ctx* c, std::string root, uint64_t n)
         : c_(c), root_(std::move(root)), owner_(n, kNone), result_(n, 0),
-          inline_(env_flag("OXH_PUBLISH_INLINE")),
-          fsync_each_(getenv("OXH_PUBLISH_SYNC") && !strcmp(getenv("OXH_PUBLISH_SYNC"), "fsync")) {}
+          inline_(oxh::env::publish_inline()), fsync_each_(oxh::env::publish_fsync()) {}
     ~VersionPublisher() override {
         {
             std::lock_guard<std::mutex> g(cq_mu_);
@@ -207,10 +206,6 @@ class VersionPublisher final : public ItemSink {
             return on ? (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t).count() : 0;
         }
     };
-    static bool env_flag(const char* name) {
-        const char* e = getenv(name);
-        return e && atoi(e) != 0;
-    }
 
     void committer() {
         std::unique_lock<std::mutex> g(cq_mu_);
@@ -315,7 +310,7 @@ class VersionPublisher final : public ItemSink {
     bool publishing_ = false, quit_ = false;
     std::thread committer_;
     oxh::Pool* rpool_ = nullptr;  // renames / fallback fsyncs
-    const bool trace_ = getenv("OXH_TRACE") != nullptr;
+    const bool trace_ = oxh::env::trace();
     std::atomic<uint64_t> put_s_{0};
     uint64_t publish_s_ = 0, wait_s_ = 0;  // committer thread / owner thread
     int nbatches_ = 0;

@@ -41,6 +41,7 @@
 #include <vector>
 
 #include "../../include/oxen_hash.h"
+#include "env.hpp"
 #include "reader_pool.hpp"
 
 extern char** environ;
@@ -75,7 +76,7 @@ int fail(int code, const std::string& msg) { return oxh::set_error(code, msg); }
 
 // oxh_hash_helper next to this library ($OXH_HELPER overrides)
 std::string helper_path() {
-    if (const char* e = getenv("OXH_HELPER")) return e;
+    if (const char* e = oxh::env::helper()) return e;
     Dl_info info;
     if (dladdr((void*)&oxh_pool_create, &info) && info.dli_fname) {
         std::string so = info.dli_fname;
@@ -109,8 +110,8 @@ bool recv_rep(int fd, PoolRep& r) {
 // no limit) turns the wait into a deadline: the call then fails and the pool is marked unusable.
 // false: the helper exited, or the deadline passed.
 bool wait_rep(int fd, pid_t pid, uint64_t seq, PoolRep& r) {
-    const double report = getenv("OXH_WAIT_LIMIT_S") ? atof(getenv("OXH_WAIT_LIMIT_S")) : 60.0;
-    const double limit = getenv("OXH_POOL_CALL_LIMIT_S") ? atof(getenv("OXH_POOL_CALL_LIMIT_S")) : 0.0;
+    const double report = oxh::env::wait_limit_s();
+    const double limit = oxh::env::pool_call_limit_s();
     timespec t0;
     clock_gettime(CLOCK_MONOTONIC, &t0);
     double next_report = report;

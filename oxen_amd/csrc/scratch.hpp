@@ -11,9 +11,10 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <cstdlib>
 #include <map>
 #include <mutex>
+
+#include "env.hpp"
 
 namespace oxh {
 
@@ -58,9 +59,7 @@ class ScratchLease {
     }
     ~ScratchLease() {
         (void)hipStreamSynchronize(st_);
-        static const uint64_t keep =
-            (getenv("OXH_SCRATCH_KEEP_MIB") ? strtoull(getenv("OXH_SCRATCH_KEEP_MIB"), nullptr, 10) : 16384ull) << 20;
-        if (cache_->size > keep) {
+        if (cache_->size > env::scratch_keep_bytes()) {
             (void)hipFree(cache_->base);
             cache_->base = nullptr;
             cache_->size = 0;

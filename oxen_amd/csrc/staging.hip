@@ -14,9 +14,7 @@ namespace oxh::capi {
 // its serial chain costs ~17 ns per KiB. In a K1T batch their text counts come from
 // text_count_kernel (chip-wide) instead of the wave.
 static uint64_t slot_chain_items(const uint64_t* hlen, uint64_t cnt, uint64_t* big) {
-    static const bool on = !(getenv("OXH_SLOT_CHAINS") && atoi(getenv("OXH_SLOT_CHAINS")) == 0);
     uint64_t nbig = 0;
-    if (!on) return 0;
     for (uint64_t j = 0; j < cnt; ++j) {
         if (hlen[j] < kSlotChainBytes) continue;
         if (nbig < (uint64_t)oxh::kChainJobs) {
@@ -118,13 +116,12 @@ int submit_slot(oxh_ctx* c, int s, uint64_t bytes, uint64_t cnt, bool any_short_
 // descriptors go into the slot right after their bytes, so ONE H2D on the compute stream carries both
 // (no copy-stream hop, no event between the streams), then K1 / K1T (+ is_utf8), D2H and the done
 // event. Each host-to-device copy costs ~5 us of a small call's ~40 us round trip. False: it does not
-// fit (the caller takes submit_slot). OXH_DIRECT_PACKED=0: always submit_slot.
+// fit (the caller takes submit_slot).
 int submit_packed(oxh_ctx* c, int s, uint64_t bytes, uint64_t cnt, bool short_items, bool text, bool utf8, bool& done,
                   bool lane) {
-    static const bool on = !(getenv("OXH_DIRECT_PACKED") && atoi(getenv("OXH_DIRECT_PACKED")) == 0);
     const uint64_t M = c->max_items, doff = align_up(bytes);
     done = false;
-    if (!on || doff + 16 * cnt > c->stage_bytes) return OXH_OK;
+    if (doff + 16 * cnt > c->stage_bytes) return OXH_OK;
     for (uint64_t j = 0; j < cnt; ++j)
         if (c->h_desc[s][M + j] >= kSlotChainBytes) return OXH_OK;
     uint64_t* hd = reinterpret_cast<uint64_t*>(c->h_stage[s] + doff);
@@ -155,23 +152,17 @@ int submit_packed(oxh_ctx* c, int s, uint64_t bytes, uint64_t cnt, bool short_it
 // Wait for slot s's digests. Polls (a slot is at most a few hundred MiB: milliseconds of work) and,
 // after OXH_WAIT_LIMIT_S seconds (default 60), reports which stage never finished instead of
 // blocking forever.
-// OXH_SPIN_US: how long a caller waiting on a staged batch spins before it sleeps (default 200; 0 =
-// sleep after 64 polls, the r02-r05 form)
-double spin_us() {
-    static const double v = getenv("OXH_SPIN_US") ? atof(getenv("OXH_SPIN_US")) : 200.0;
-    return v;
-}
-
 int wait_slot(oxh_ctx* c, int s, const Pending& p) {
-    static const double limit = getenv("OXH_WAIT_LIMIT_S") ? atof(getenv("OXH_WAIT_LIMIT_S")) : 60.0;
+    static const double limit = oxh::env::wait_limit_s();
+    constexpr double kSpinUs = 200.0;  // how long a caller spins before it sleeps
     const auto t0 = std::chrono::steady_clock::now();
     for (uint64_t spin = 0;; ++spin) {
         const hipError_t q = hipEventQuery(c->ev_done[s]);
         if (q == hipSuccess) return OXH_OK;
         if (q != hipErrorNotReady) return fail(OXH_ERR_HIP, std::string("slot event: ") + hipGetErrorString(q));
-        // a small batch is back within tens of us: spin (yielding) for the first spin_us(), then sleep
+        // a small batch is back within tens of us: spin (yielding) for the first kSpinUs, then sleep
         // in 20 us steps (a caller's own thread keeps its timer slack, so a sleep costs ~70 us)
-        if (spin > 64 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e6 > spin_us())
+        if (spin > 64 && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e6 > kSpinUs)
             std::this_thread::sleep_for(std::chrono::microseconds(20));
         else
             std::this_thread::yield();
@@ -211,11 +202,7 @@ int drain_slot(oxh_ctx* c, int s, Pending& p, uint64_t* out) {
 // Items of the short XXH3 paths (<= 240 B: paths, metadata JSON, most parent-node streams) are packed
 // back to back: their kernels load unaligned bytes anyway, and 256-B slots would move ~8x their bytes
 // over PCIe (a commit's 200 000 bucket paths: 6.3 MB instead of 51 MB). Longer items start on 256 B.
-// OXH_HOST_ALIGN_ALL=1: every item on 256 B (the r02 packing, for A/B).
-static uint64_t place(uint64_t off, uint64_t len) {
-    static const bool all = getenv("OXH_HOST_ALIGN_ALL") && atoi(getenv("OXH_HOST_ALIGN_ALL")) != 0;
-    return (len > 240 || all) ? align_up(off) : off;
-}
+static uint64_t place(uint64_t off, uint64_t len) { return len > 240 ? align_up(off) : off; }
 
 static int hash_host_items(oxh_ctx* c, uint64_t n, const uint64_t* lens,
                            const std::function<const uint8_t*(uint64_t)>& src, uint64_t* out, bool short_only_lane) {
@@ -412,9 +399,8 @@ int oxh_hash_streams(oxh_ctx* c, const uint8_t* streams, const uint64_t* offsets
     std::lock_guard<std::mutex> g(c->mu);
     HIP_TRY(hipSetDevice(c->device));
     STEP("hash_streams locked");
-    // spans when the items run forward through the arena without large gaps (OXH_STREAM_SPANS=0: per item)
-    static const bool spans_on = !(getenv("OXH_STREAM_SPANS") && atoi(getenv("OXH_STREAM_SPANS")) == 0);
-    bool forward = spans_on && n > 0;
+    // spans when the items run forward through the arena without large gaps
+    bool forward = n > 0;
     uint64_t total = 0, maxend = 0;
     for (uint64_t i = 0; forward && i < n; ++i) {
         total += lens[i];

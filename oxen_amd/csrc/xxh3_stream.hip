@@ -136,9 +136,7 @@ int oxh_xxh3_stream_create(oxh_ctx* ctx, oxh_xxh3_stream** out) {
     *out = nullptr;
     oxh_xxh3_stream* s = new oxh_xxh3_stream();
     s->device = ctx->device;
-    const char* e = getenv("OXH_STREAM_PIECE_MIB");
-    const uint64_t kib = e && strtoull(e, nullptr, 10) ? strtoull(e, nullptr, 10) << 10 : 16ull << 10;
-    s->piece = kib << 10;  // whole 1 KiB blocks
+    s->piece = oxh::env::stream_piece_bytes();  // whole 1 KiB blocks
     *out = s;              // nothing is allocated until bytes arrive
     return OXH_OK;
 }

@@ -199,6 +199,22 @@ def test_chunk_digests_files_segments(cuda, oracle_lib, tmp_path, monkeypatch, c
 
 
 @pytest.mark.gpu
+def test_chunk_digests_host_many_segments_take_descriptors(cuda, oracle_lib):
+    """Nine live segments in one piece: more than the eight a round hashes as implied chunk grids, so the
+    round builds chunk descriptors and takes one K1 launch over them (fastcdc_host.cpp fixed_round); an
+    empty buffer among them is no segment. Eight or fewer is every other case of this file."""
+    from oxen_amd import dedup
+
+    rng = np.random.default_rng(9)
+    datas = [rng.integers(0, 256, 3 * 4096 + 17, dtype=np.uint8) for _ in range(9)]
+    datas.insert(4, np.zeros(0, np.uint8))
+    t = dedup.chunk_digests_host(datas, 4096)
+    assert list(t.first) == [0, 4, 8, 12, 16, 16, 20, 24, 28, 32, 36]
+    for i, d in enumerate(datas):
+        assert np.array_equal(t.file(i), oracle_lib.chunk_digests(d, 4096)), i
+
+
+@pytest.mark.gpu
 def test_chunk_digests_host_one_byte_chunks(cuda, oracle_lib):
     """chunk_size 1 over 9 M bytes: more chunks than one round's budget (4 M), so rounds end on the
     budget rather than the piece; every digest is the xxh3_128 of its byte."""

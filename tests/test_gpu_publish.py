@@ -257,3 +257,17 @@ def test_hash_streams_arena_layouts(cuda, oracle_lib, layout):
                                                  out.ctypes.data_as(_capi._u64p)), "oxh_hash_streams")
     got = [(int(hi) << 64) | int(lo) for lo, hi in out]
     assert got == [oracle.xxh3_128_int(blobs[k]) for k in order]
+
+
+def test_small_call_with_and_without_room_for_packed_descriptors(cuda, oracle_lib):
+    """A call that is one small batch sends its descriptors behind its bytes in one H2D (staging.hip
+    submit_packed) when the slot has room for them, and takes the three-copy submit when it has not:
+    in a 1 MiB slot, one buffer of 5000 bytes, and one of 1 MiB - 100 (no 16 bytes left after it)."""
+    from oxen_amd import _capi, hasher
+    from oxen_amd.workloads import splitmix_bytes
+
+    with _capi.Context(0, staging_bytes=1 << 20) as c:
+        for n in (5000, (1 << 20) - 100):
+            b = splitmix_bytes(77, 0, n).tobytes()
+            assert hasher.hash_buffers_128bit([b], c) == [oracle_lib.xxh3_128_int(b)], n
+            assert hasher.hash_streams_128bit([b], c) == [oracle_lib.xxh3_128_int(b)], n

@@ -1,7 +1,7 @@
 """Mid-size text files through K1T (oxh_hash_files_text: digests + MetadataText counts in the same read):
 N files of S MiB of UTF-8 text from the page cache, median of --reps calls, every digest against the C
-oracle and every count against numpy. Run it with OXH_SLOT_CHAINS=0 / 1 to compare one K1T wave per item
-with K1L + text_count_kernel for items of 1 MiB and more (staging.hip submit_slot). Prints one JSON line.
+oracle and every count against numpy. Items of 1 MiB and more take K1L + text_count_kernel (staging.hip
+submit_slot). Prints one JSON line.
 
     python tools/text_mid_probe.py [--files 16] [--mib 100] [--reps 3]
 """
@@ -53,7 +53,7 @@ def main():
         ok &= d == want and meta == counts and not any(st)
     ctx.close()
     g = statistics.median(ts[1:])
-    print(json.dumps({"files": a.files, "bytes_each": size, "slot_chains": os.environ.get("OXH_SLOT_CHAINS", "1"),
+    print(json.dumps({"files": a.files, "bytes_each": size,
                       "gpu_s": round(g, 4), "gpu_GiBs": round(a.files * size / g / 2**30, 1), "bit_exact": bool(ok)}), flush=True)
     if not ok:
         sys.exit(1)
