@@ -410,8 +410,9 @@ int oxh_fill_splitmix(void* d_buf, uint64_t nbytes, uint64_t seed, void* stream)
 int oxh_set_kernel_variant(int variant);
 /* Diagnostic counters of a context, out[0..n): [0] device allocations of the large-file piece buffers
  * (files above a staging slot; each one synchronises the device), [1] their current bytes, [2] file
- * requests served on the caller's thread (small requests on an idle context), [3] file-engine runs;
- * further entries 0. */
+ * requests served on the caller's thread (small requests on an idle context), [3] file-engine runs,
+ * [4] staged slots submitted (host batches of files, buffers or streams), [5] the most items of 1 MiB
+ * and more that one of those slots held (K1L takes the 32 largest of a slot); further entries 0. */
 int oxh_ctx_counters(oxh_ctx* ctx, uint64_t* out, int n);
 
 #ifdef __cplusplus

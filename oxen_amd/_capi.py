@@ -172,11 +172,12 @@ class Context:
 
     def counters(self) -> dict:
         """oxh_ctx_counters: large-file piece-buffer allocations and their current bytes, file requests
-        served on the caller's thread, file-engine runs."""
-        out = (ctypes.c_uint64 * 4)()
-        check(lib().oxh_ctx_counters(self.handle, out, 4), "oxh_ctx_counters")
+        served on the caller's thread, file-engine runs, staged slots submitted, and the most items of
+        1 MiB and more one slot held."""
+        out = (ctypes.c_uint64 * 6)()
+        check(lib().oxh_ctx_counters(self.handle, out, 6), "oxh_ctx_counters")
         return {"big_allocs": int(out[0]), "big_bytes": int(out[1]), "direct_requests": int(out[2]),
-                "engine_runs": int(out[3])}
+                "engine_runs": int(out[3]), "slots": int(out[4]), "slot_large_max": int(out[5])}
 
     def close(self) -> None:
         if getattr(self, "handle", None):

@@ -61,8 +61,9 @@ extern "C" {
 
 int oxh_ctx_counters(oxh_ctx* c, uint64_t* out, int n) {
     if (!c || (n > 0 && !out)) return fail(OXH_ERR_INVALID, "null argument");
-    const uint64_t v[4] = {c->d_big_allocs, c->d_big_size, c->n_direct.load(), c->n_runs.load()};
-    for (int i = 0; i < n; ++i) out[i] = i < 4 ? v[i] : 0;
+    const uint64_t v[6] = {c->d_big_allocs,  c->d_big_size,    c->n_direct.load(),
+                           c->n_runs.load(), c->n_slots.load(), c->slot_large_max.load()};
+    for (int i = 0; i < n; ++i) out[i] = i < 6 ? v[i] : 0;
     return OXH_OK;
 }
 

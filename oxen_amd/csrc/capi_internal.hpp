@@ -159,6 +159,8 @@ struct oxh_ctx {
     uint64_t d_big_size = 0;
     uint64_t d_big_allocs = 0;   // times d_big was (re)allocated (oxh_ctx_counters)
     std::atomic<uint64_t> n_direct{0}, n_runs{0};  // file requests on the caller's thread / engine runs
+    // staged slots submitted (submit_slot), and the most items of kSlotChainBytes and more one of them held
+    std::atomic<uint64_t> n_slots{0}, slot_large_max{0};
     uint8_t* h_bounce[8] = {};   // kNBounce pinned bounce buffers, used as a ring
     hipEvent_t ev_bounce[8] = {};
     bool bounce_used[8] = {};

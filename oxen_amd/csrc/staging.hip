@@ -13,10 +13,12 @@ namespace oxh::capi {
 // it over PCIe, and one 1 MiB file ~100 us of a single-file call. K1L's block sums run chip-wide and
 // its serial chain costs ~17 ns per KiB. In a K1T batch their text counts come from
 // text_count_kernel (chip-wide) instead of the wave.
-static uint64_t slot_chain_items(const uint64_t* hlen, uint64_t cnt, uint64_t* big) {
+static uint64_t slot_chain_items(const uint64_t* hlen, uint64_t cnt, uint64_t* big, uint64_t& nlarge) {
     uint64_t nbig = 0;
+    nlarge = 0;
     for (uint64_t j = 0; j < cnt; ++j) {
         if (hlen[j] < kSlotChainBytes) continue;
+        ++nlarge;
         if (nbig < (uint64_t)oxh::kChainJobs) {
             big[nbig++] = j;
             continue;
@@ -34,7 +36,12 @@ int submit_slot(oxh_ctx* c, int s, uint64_t bytes, uint64_t cnt, bool any_short_
                 bool utf8) {
     const uint64_t M = c->max_items;
     uint64_t big[oxh::kChainJobs];
-    const uint64_t nbig = any_short_only ? 0 : slot_chain_items(c->h_desc[s] + M, cnt, big);
+    uint64_t nlarge = 0;
+    const uint64_t nbig = any_short_only ? 0 : slot_chain_items(c->h_desc[s] + M, cnt, big, nlarge);
+    c->n_slots.fetch_add(1, std::memory_order_relaxed);
+    for (uint64_t seen = c->slot_large_max.load(std::memory_order_relaxed);
+         nlarge > seen && !c->slot_large_max.compare_exchange_weak(seen, nlarge, std::memory_order_relaxed);) {
+    }
     STEP("submit s=%d bytes=%llu cnt=%llu lane=%d short=%d", s, (unsigned long long)bytes, (unsigned long long)cnt,
          (int)any_short_only, (int)short_items);
     c->where.store("submit_slot: H2D stage");

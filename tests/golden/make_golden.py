@@ -10,8 +10,10 @@ hold (/root/reference/data/test, copied under tests/golden/data_test/ when <= 64
   data_test.json   XXH3-128 of every file under reference data/test (48 files)
   text_repo.json   config 1: the 1 000-file text repo of benchmark/generate_text_repo.py + README
   streams.json     K2 parent-node streams (vnode / dir / commit / combined / metadata JSON)
+  lattice.json     the length-by-alignment lattice of tests/_lattice.py (53 046 items): its definition
+                   and, per shift, the SHA-256 of libxxhash's packed little-endian (lo, hi) digests
 
-Usage: python tests/golden/make_golden.py [--reference /root/reference]
+Usage: python tests/golden/make_golden.py [--reference /root/reference] [--only lattice]
 """
 from __future__ import annotations
 
@@ -24,6 +26,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(HERE))  # tests/_lattice.py
 
 import xxhash  # noqa: E402
 
@@ -52,12 +55,43 @@ def text_metadata(data: bytes) -> dict:
     return {"text": {"num_lines": 1 + data.count(b"\n"), "num_chars": sum(1 for b in data if (b & 0xC0) != 0x80)}}
 
 
+def lattice_table():
+    """libxxhash's digest of every lattice item, uint64 (n, 2) = (lo, hi), in the lattice's order."""
+    import numpy as np
+
+    import _lattice
+
+    arena = _lattice.host_arena().tobytes()
+    offs, lens = _lattice.items()
+    mask = 2**64 - 1
+    out = np.zeros((len(lens), 2), dtype=np.uint64)
+    for i, (o, n) in enumerate(zip(offs.tolist(), lens.tolist())):
+        v = xxhash.xxh3_128_intdigest(arena[o:o + n])
+        out[i] = (v & mask, v >> 64)
+    return out
+
+
+def write_lattice(meta: dict) -> int:
+    import _lattice
+
+    table = lattice_table()
+    json.dump({**meta, **_lattice.definition(),
+               "sha256": "of each shift's digests, packed little-endian (lo, hi) in the order of the lengths",
+               "sha256_by_shift": dict(zip(map(str, _lattice.SHIFTS), _lattice.table_sha256(table)))},
+              open(os.path.join(HERE, "lattice.json"), "w"), indent=1)
+    return len(table)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--reference", default="/root/reference")
+    ap.add_argument("--only", choices=["lattice"], help="regenerate this file alone")
     args = ap.parse_args()
     meta = {"generator": f"python-xxhash {xxhash.VERSION} / libxxhash {xxhash.XXHASH_VERSION}",
             "algorithm": "XXH3-128, seed 0, default secret (== xxhash-rust 0.8.15 xxh3_128)"}
+    if args.only == "lattice":
+        print(f"wrote {write_lattice(meta)} lattice items")
+        return
 
     # 1. lengths
     lengths = sorted(set(list(range(0, 2049)) + BOUNDARY))
@@ -141,8 +175,10 @@ def main() -> None:
     out = [{"name": k, "bytes_hex": v.hex(), **digest(v)} for k, v in streams.items()]
     json.dump({**meta, "source": "commit_writer.rs:686-720, 757-766, 995-1147; hasher.rs:67-100",
                "streams": out}, open(os.path.join(HERE, "streams.json"), "w"), indent=1)
+    # 6. the length-by-alignment lattice
+    n_lattice = write_lattice(meta)
     print(f"wrote {len(vecs)} length vectors, {len(kat)} KATs, {len(files)} data/test files, "
-          f"{len(recs)} text-repo files, {len(out)} streams")
+          f"{len(recs)} text-repo files, {len(out)} streams, {n_lattice} lattice items")
 
 
 if __name__ == "__main__":

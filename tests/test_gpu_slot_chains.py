@@ -7,7 +7,8 @@ Every digest here is checked against the oracle (the published XXH3-128, oracle/
 lengths around the 1 MiB threshold and the 1 KiB block edges, more large items in one slot than one
 chain launch takes, items just below a slot, unaligned items in a stream arena, and every staged
 entry (the file engine, the small-request path, host buffers, streams, the fused add); in K1T
-batches the large items' text counts come from text_count_kernel, checked against a direct count.
+batches the large items' text counts come from text_count_kernel, checked against a direct count,
+at every tail length of that kernel and with more large items in a slot than K1L takes.
 """
 import numpy as np
 import pytest
@@ -117,6 +118,62 @@ def test_text_request_with_large_files(ctx, oracle_lib, tmp_path):
         assert st == [0] and m == [_counts(b)]
 
 
+def test_text_count_kernel_tail(ctx, oracle_lib, tmp_path):
+    """text_count_kernel counts 16 bytes per lane and the last len % 16 bytes one by one: files of
+    1 MiB + r, r in 0..16, of b"\n\x80" repeated, so a missed or extra byte changes num_lines or
+    num_chars whichever it is. As one request (its large items share staging slots; how many slots is
+    the engine's choice) and each file alone."""
+    from oxen_amd import hasher
+
+    blobs = [(b"\n\x80" * (MIB // 2 + 9))[:MIB + r] for r in range(17)]
+    want = [oracle_lib.xxh3_128_int(b) for b in blobs]
+    want_meta = [_counts(b) for b in blobs]
+    assert want_meta == [{"text": {"num_lines": 1 + (len(b) + 1) // 2, "num_chars": len(b) - len(b) // 2}} for b in blobs]
+    paths = _write(tmp_path, blobs)
+    d, sizes, st, meta = hasher.hash_files_text_128bit(paths, ctx=ctx)
+    assert not any(st) and sizes == [len(b) for b in blobs]
+    assert meta == want_meta
+    assert d == want
+    for p, w, m in zip(paths, want, want_meta):
+        d1, _, st1, m1 = hasher.hash_files_text_128bit([p], ctx=ctx)
+        assert st1 == [0] and m1 == [m] and d1 == [w]
+
+
+def test_text_more_large_items_than_one_chain_launch(cuda, oracle_lib, tmp_path, monkeypatch):
+    """40 files of 1 MiB + k in one text slot (a 96 MiB staging context), small files between them:
+    slot_chain_items keeps the 32 largest for K1L + text_count_kernel + CountFix, the other 8 stay on
+    the K1T wave with their counts. The files come in an order that is not by size, so the kept set is
+    not a prefix. Every digest, count and is_utf8 against the oracle and a direct count.
+
+    The engine seals a slot early at OXH_FLUSH_MIB (16 MiB) once every file of a request is claimed,
+    which would spread these 41 MiB over several slots; the context is created with the flush size at
+    the slot size, and its counters must show one slot that held all 40 large items."""
+    from oxen_amd import _capi, hasher
+
+    monkeypatch.setenv("OXH_FLUSH_MIB", "96")  # read when the context is created
+
+    line = "row,é,中,\U0001f600\n".encode()
+    order = np.random.default_rng(81).permutation(40)
+    rnd = _blobs([MIB + int(k) for k in order], 82)
+    blobs = []
+    for i, k in enumerate(order):
+        n = MIB + int(k)
+        blobs.append(rnd[i] if k % 2 else (line * (n // len(line) + 1))[:n])
+        if i % 9 == 4:
+            blobs += [b"a\nb", rnd[i][:70_001], b""]
+    assert sum(1 for b in blobs if len(b) >= MIB) == 40
+    paths = _write(tmp_path, blobs)
+    want = [oracle_lib.xxh3_128_int(b) for b in blobs]
+    with _capi.Context(0, staging_bytes=96 * MIB) as c:
+        d, sizes, st, meta, u8 = hasher.hash_files_text_utf8_128bit(paths, ctx=c)
+        seen = c.counters()
+    assert seen["slot_large_max"] == 40, seen  # else the path this test is about did not run
+    assert not any(st) and sizes == [len(b) for b in blobs]
+    assert meta == [_counts(b) for b in blobs]
+    assert d == want
+    assert u8 == [oracle_lib.is_utf8_prefix(b[:4096]) for b in blobs]
+
+
 # Files of 8 MiB and more in a slot are read in 4 MiB parts by several readers (engine.hip run_part);
 # the parts cover [0, L + 1) so a size that changed since the stat (or the caller's metadata) still
 # sends the file to the engine's re-read.
@@ -133,6 +190,7 @@ def test_split_reads(ctx, oracle_lib, tmp_path):
     assert d == want and sizes == SPLIT and not any(st)
     d, _, st, meta = hasher.hash_files_text_128bit(paths, ctx=ctx)  # K1T over split reads
     assert d == want and not any(st)
+    assert meta == [_counts(b) for b in blobs]
     digests, _, st, _ = hasher.add_files(paths, str(tmp_path / "versions"), ctx=ctx)
     assert digests == want and not any(st)
     for b, dg in zip(blobs, digests):

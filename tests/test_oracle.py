@@ -33,6 +33,35 @@ def test_every_length_golden(oracle_lib, golden):
     assert not bad, f"oracle mismatch at lengths {bad[:10]}"
 
 
+def test_lattice_golden(oracle_lib, golden):
+    """The oracle on the whole length-by-alignment lattice (tests/_lattice.py, 53 046 items), against
+    libxxhash's digests: lattice.json holds their SHA-256 per shift (tests/golden/make_golden.py). With
+    python `xxhash` present a mismatch is also narrowed to its lengths; the test needs only the JSON."""
+    import _lattice
+
+    g = golden("lattice.json")
+    assert {k: g[k] for k in _lattice.definition()} == _lattice.definition(), "lattice.json is stale: regenerate it"
+    offs, lens = _lattice.items()
+    got = oracle_lib.batch(_lattice.host_arena(), offs, lens, threads=16)
+    want = [g["sha256_by_shift"][str(s)] for s in _lattice.SHIFTS]
+    bad_shifts = [s for s, a, b in zip(_lattice.SHIFTS, _lattice.table_sha256(got), want) if a != b]
+    try:
+        import xxhash
+    except ImportError:
+        detail = " (python xxhash not installed: no per-length detail)"
+    else:  # ~0.1 s: libxxhash item by item, checked against the JSON first
+        arena = _lattice.host_arena().tobytes()
+        ref = np.zeros_like(got)
+        for i, (o, n) in enumerate(zip(offs.tolist(), lens.tolist())):
+            v = xxhash.xxh3_128_intdigest(arena[o:o + n])
+            ref[i] = (v & (2**64 - 1), v >> 64)
+        assert _lattice.table_sha256(ref) == want, "libxxhash here disagrees with lattice.json"
+        total, first = _lattice.mismatches(got, ref, offs, lens)
+        detail = f": {total} items differ from libxxhash, first (shift, len) {first}"
+        assert total == 0, "oracle" + detail
+    assert not bad_shifts, f"oracle differs from libxxhash on the lattice at shifts {bad_shifts}{detail}"
+
+
 def test_data_test_fixture_files(oracle_lib, golden):
     g = golden("data_test.json")
     paths, want = [], []
