@@ -100,13 +100,13 @@ def build_host(force: bool = False, verbose: bool = False) -> str:
     return HOST_LIB
 
 
-def compile_lib(out: str, defines: tuple[str, ...] = (), verbose: bool = False) -> str:
+def compile_lib(out: str, verbose: bool = False) -> str:
     """hipcc every source to its own object in parallel (one hipcc per source), then link `out`."""
     from concurrent.futures import ThreadPoolExecutor
 
     objdir = os.path.join(HERE, "build", os.path.basename(out).replace(".so", ""))
     os.makedirs(objdir, exist_ok=True)
-    flags = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall"] + [f"-D{d}" for d in defines]
+    flags = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall"]
 
     def one(src: str) -> str:
         obj = os.path.join(objdir, os.path.basename(src) + ".o")

@@ -18,42 +18,24 @@ int fail(int code, const std::string& msg) {
 // ---------------------------------------------------------------- kernel launch helpers
 using WaveKernel = void (*)(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
 
-// The shipped library instantiates the shapes the dispatch below picks (8, 72, 104, 264) and the
-// 4-round ring (0) as the fallback for any other forced variant. The experiments that lost their A/Bs
-//  are compiled only into the probe build (tools/build_probe_lib.sh, -DOXH_PROBE_VARIANTS).
+// The shapes the dispatch below picks; any other forced variant runs the 4-round ring (Cfg<0>) with
+// the launch geometry of one item per wave (known_variant). What each number is: Cfg, xxh3_kernels.hip.
 template <bool DESC>
 WaveKernel wave_kernel_for(int variant) {
     switch (variant) {
-        case 8: return oxh::xxh3_wave_kernel<DESC, 8>;
-        case 72: return oxh::xxh3_wave_kernel<DESC, 72>;
-        case 104: return oxh::xxh3_wave_kernel<DESC, 104>;
-        case 264: return oxh::xxh3_wave_kernel<DESC, 264>;
-#ifdef OXH_PROBE_VARIANTS
-        case 1: return oxh::xxh3_wave_kernel<DESC, 1>;
-        case 2: return oxh::xxh3_wave_kernel<DESC, 2>;
-        case 4: return oxh::xxh3_wave_kernel<DESC, 4>;
-        case 12: return oxh::xxh3_wave_kernel<DESC, 12>;
-        case 64: return oxh::xxh3_wave_kernel<DESC, 64>;
-        case 74: return oxh::xxh3_wave_kernel<DESC, 74>;
-        case 40: return oxh::xxh3_wave_kernel<DESC, 40>;
-        case 256: return oxh::xxh3_wave_kernel<DESC, 256>;
-        case 260: return oxh::xxh3_wave_kernel<DESC, 260>;
-        case 768: return oxh::xxh3_wave_kernel<DESC, 768>;
-        case 772: return oxh::xxh3_wave_kernel<DESC, 772>;
-        case 776: return oxh::xxh3_wave_kernel<DESC, 776>;
-        case 1032: return oxh::xxh3_wave_kernel<DESC, 1032>;
-        case 1024: return oxh::xxh3_wave_kernel<DESC, 1024>;
-#endif
+        case kVariantShort: return oxh::xxh3_wave_kernel<DESC, kVariantShort>;
+        case kVariantLong: return oxh::xxh3_wave_kernel<DESC, kVariantLong>;
+        case kVariantPacked: return oxh::xxh3_wave_kernel<DESC, kVariantPacked>;
+        case kVariantRows: return oxh::xxh3_wave_kernel<DESC, kVariantRows>;
         default: return oxh::xxh3_wave_kernel<DESC, 0>;
     }
 }
 
 // K1 register/pipeline shape by item size (measured): items of a few KiB want many
-// resident waves (2-round ring, keys in LDS: 77 VGPRs, 6 waves/SIMD, every load issued up front);
-// larger items a 2-round ring with the keys in registers (variant 8). The 4-round ring (variant 0,
-// 201 VGPRs, 2 waves/SIMD) matches it on equal 64 KiB items but loses 13 % on ragged, packed items
-// (FastCDC chunks: tools/k1_align_probe.py) and 4 % of the C2 step rate. An explicit
-// oxh_set_kernel_variant() overrides the choice.
+// resident waves (2-round ring, keys in LDS, every load issued up front); larger items a 2-round ring
+// with the keys in registers (variant 8). The 4-round ring (variant 0) matches it on equal 64 KiB
+// items but loses 13 % on ragged, packed items (FastCDC chunks: tools/k1_align_probe.py) and 4 % of
+// the C2 step rate. An explicit oxh_set_kernel_variant() overrides the choice.
 //
 // Items packed back to back (FastCDC chunks) start at arbitrary byte offsets: a row-wise
 // instruction (256 B per row) then touches 3 lines where an aligned one touches 2, 12 lines per KiB
@@ -68,21 +50,13 @@ int pick_variant(ItemShape shape) {
     return shape == ItemShape::Packed ? kVariantPacked : shape == ItemShape::Short ? kVariantShort : kVariantLong;
 }
 int pick_variant(bool short_items) { return pick_variant(short_items ? ItemShape::Short : ItemShape::Long); }
-// K1R variants (bit 8) hash four items per wave, one per 16-lane row; K1H (bits 8 and 9) two, one per
-// pair of rows
-uint64_t items_per_wave(int variant) { return (variant & 256) ? ((variant & 512) ? 2 : 4) : 1; }
-// a variant wave_kernel_for instantiates, else 0 (its default kernel), so the launch geometry always
+// a variant wave_kernel_for has a case for, else 0 (its default kernel), so the launch geometry always
 // matches the kernel that runs
 int known_variant(int v) {
-    switch (v) {
-        case 8: case 72: case 104: case 264: return v;
-#ifdef OXH_PROBE_VARIANTS
-        case 1: case 2: case 4: case 12: case 40: case 64: case 74:
-        case 256: case 260: case 768: case 772: case 776: case 1024: case 1032: return v;
-#endif
-        default: return 0;
-    }
+    return (v == kVariantShort || v == kVariantLong || v == kVariantPacked || v == kVariantRows) ? v : 0;
 }
+// K1R hashes four items per wave, one per 16-lane row
+uint64_t items_per_wave(int variant) { return variant == kVariantRows ? 4 : 1; }
 
 // K1 over a descriptor table: one 64-lane wave per item, 4 waves per 256-thread workgroup.
 int launch_wave(const uint8_t* arena, const uint64_t* offs, const uint64_t* lens, uint64_t n, uint64_t* out,
@@ -103,13 +77,12 @@ int launch_wave(const uint8_t* arena, const uint64_t* offs, const uint64_t* lens
 
 // K1T: K1 plus text counts in the same pass.
 int launch_text(const uint8_t* arena, const uint64_t* offs, const uint64_t* lens, uint64_t n, uint64_t* out,
-                uint64_t* counts, hipStream_t st, bool short_items) {
+                uint64_t* counts, hipStream_t st) {
     if (n == 0) return OXH_OK;
     const uint64_t blocks = (n + 3) / 4;
     // K1T keeps the 2-round ring with the keys in LDS at every item size: the counting needs the
     // registers (tools/k1t_probe.py: 6.41 TB/s on C2 and 5.55 on ragged items, against 5.42 / 4.40
     // with variant 8 and 4.32 / 2.56 with the 4-round ring); only that shape ships
-    (void)short_items;
     hipLaunchKernelGGL(oxh::xxh3_text_wave_kernel<kVariantShort>, dim3((unsigned)blocks), dim3(256), 0, st, arena, offs, lens,
                        n, out, counts);
     HIP_TRY(hipGetLastError());
@@ -143,7 +116,7 @@ namespace oxh {
 // chunks per wave, one per 16-lane row: tools/k1_small_probe.py, profiles/r04g_k1_small_probe.json),
 // otherwise the block-wise K1 (one chunk per wave; K1R's four streams per wave lose 10 % on 16-128 KiB
 // items); 2 waves per workgroup below 16 KiB, else 4. oxh_set_kernel_variant overrides the shape
-// (launch_wave), for the probe build's A/Bs.
+// (launch_wave).
 int k1_packed(const void* d_arena, const uint64_t* d_offsets, const uint64_t* d_lens, uint64_t n, uint64_t* d_out,
               uint64_t mean_len, hipStream_t st) {
     const bool small = mean_len < kShortItemBytes;

@@ -94,12 +94,13 @@ constexpr int NSLOT = 3;
 inline uint64_t align_up(uint64_t x) { return (x + kAlign - 1) & ~(kAlign - 1); }
 
 // ---------------------------------------------------------------- K1 launches (capi_dispatch.hip)
-// K1 register/pipeline shape by item size (the measurements are at the definitions)
+// K1 register/pipeline shape by item size (the measurements are at pick_variant, what
+// each number is at Cfg in xxh3_kernels.hip)
 constexpr uint64_t kShortItemBytes = 16384;
-constexpr int kVariantShort = 72;    // Cfg: row-wise, depth 2, keys in LDS
-constexpr int kVariantLong = 8;      // Cfg: row-wise, depth 2, keys from the constant table
-constexpr int kVariantPacked = 104;  // Cfg: block-wise, depth 2, keys in LDS
-constexpr int kVariantRows = 264;    // Cfg: K1R (a 16-lane row per item), depth 2
+constexpr int kVariantShort = 72;
+constexpr int kVariantLong = 8;
+constexpr int kVariantPacked = 104;
+constexpr int kVariantRows = 264;
 
 enum class ItemShape { Long, Short, Packed };
 
@@ -108,7 +109,7 @@ int launch_wave(const uint8_t* arena, const uint64_t* offs, const uint64_t* lens
                 hipStream_t st, ItemShape shape = ItemShape::Long, int waves = 4, int variant = 0);
 // K1T: K1 plus text counts in the same pass.
 int launch_text(const uint8_t* arena, const uint64_t* offs, const uint64_t* lens, uint64_t n, uint64_t* out,
-                uint64_t* counts, hipStream_t st, bool short_items = false);
+                uint64_t* counts, hipStream_t st);
 // Fixed-size chunks of one buffer (no descriptor table): chunk i = [i*chunk, min((i+1)*chunk, total)).
 int launch_chunks(const uint8_t* buf, uint64_t n, uint64_t chunk, uint64_t total, uint64_t* out, hipStream_t st);
 int launch_lane(const uint8_t* arena, const uint64_t* offs, const uint64_t* lens, uint64_t n, uint64_t* out,

@@ -183,10 +183,7 @@ __device__ __forceinline__ uint32_t byte_of(const uint4& v, int j) {
 // third wave's chain fills issue slots (C5 at 8 KiB: F1 26.6 vs 28.2 ms with 8 waves, r02). 16 waves
 // with 64-byte rounds (4 KiB slots, half-line DMA) measured far slower (73 vs 52 ms end to end).
 constexpr int kScanWaves = 12;
-#ifndef OXH_SCAN_DMA_AUX
-#define OXH_SCAN_DMA_AUX 2
-#endif
-constexpr int kScanDmaAux = OXH_SCAN_DMA_AUX;  // cache policy of the scan's LDS-DMA loads (2 = nt)
+constexpr int kScanDmaAux = 2;  // cache policy of the scan's LDS-DMA loads (2 = nt)
 
 template <bool SH>
 __global__ __launch_bounds__(64 * kScanWaves) void cdc_scan_kernel(CdcFiles f, CdcParams prm, uint64_t n_sec) {
@@ -323,12 +320,10 @@ __global__ __launch_bounds__(64 * kScanWaves) void cdc_scan_kernel(CdcFiles f, C
                 if (__builtin_amdgcn_ballot_w64(anyz == 0)) {
                     const uint32_t g = rb + 16 * (uint32_t)(i >> 2);  // the group, section-relative
                     if (anyz == 0 && g < sec_len) {
-#ifndef OXH_F1_NOSTORE  // diagnostic builds only: the cost of the candidate stores (output invalid)
                         if (count < prm.cap) {
                             out_c[count].e = ((uint64_t)((g - us) >> 4) << kEntryShift) | ((SH ? (hb >> 16) : hb) & kEntryHash);
                             out_c[count].b = make_uint4(wv[i - 3], wv[i - 2], wv[i - 1], wv[i]);
                         }
-#endif
                         ++count;
                     }
                 }

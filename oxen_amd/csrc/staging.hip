@@ -61,8 +61,7 @@ int submit_slot(oxh_ctx* c, int s, uint64_t bytes, uint64_t cnt, bool any_short_
     HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_copied[s], 0));
     STEP("copies queued s=%d", s);
     c->where.store("submit_slot: launch");
-    int rc = text ? launch_text(c->d_stage[s], c->d_desc[s], d_wave_lens, cnt, c->d_out[s], c->d_cnt[s], c->stream,
-                                short_items)
+    int rc = text ? launch_text(c->d_stage[s], c->d_desc[s], d_wave_lens, cnt, c->d_out[s], c->d_cnt[s], c->stream)
              : any_short_only ? launch_lane(c->d_stage[s], c->d_desc[s], c->d_desc[s] + M, cnt, c->d_out[s], c->stream)
                               : launch_wave(c->d_stage[s], c->d_desc[s], d_wave_lens, cnt, c->d_out[s], c->stream,
                                             short_items ? ItemShape::Short : ItemShape::Long);
@@ -138,7 +137,7 @@ int submit_packed(oxh_ctx* c, int s, uint64_t bytes, uint64_t cnt, bool short_it
     const uint64_t* d_lens = d_offs + cnt;
     c->where.store("submit_packed: H2D");
     HIP_TRY(hipMemcpyAsync(c->d_stage[s], c->h_stage[s], doff + 16 * cnt, hipMemcpyHostToDevice, c->stream));
-    int rc = text   ? launch_text(c->d_stage[s], d_offs, d_lens, cnt, c->d_out[s], c->d_cnt[s], c->stream, short_items)
+    int rc = text   ? launch_text(c->d_stage[s], d_offs, d_lens, cnt, c->d_out[s], c->d_cnt[s], c->stream)
              : lane ? launch_lane(c->d_stage[s], d_offs, d_lens, cnt, c->d_out[s], c->stream)
                     : launch_wave(c->d_stage[s], d_offs, d_lens, cnt, c->d_out[s], c->stream,
                                   short_items ? ItemShape::Short : ItemShape::Long);

@@ -46,85 +46,65 @@ __device__ __forceinline__ uint64_t dpp64(uint64_t x) {
     return ((uint64_t)hi << 32) | lo;
 }
 
-// Broadcast the value held by each 16-lane row r (x_r) so that every lane gets x_0..x_3.
-// VARIANT 0: v_permlane16_swap + v_permlane32_swap (gfx950 VALU cross-row moves).
-// VARIANT 1: ds_bpermute through __shfl (LDS crossbar) -- reference formulation for A/B.
-template <int VARIANT>
-__device__ __forceinline__ void bcast_rows32(uint32_t x, uint32_t& b0, uint32_t& b1, uint32_t& b2,
-                                             uint32_t& b3, int lane) {
-    if constexpr (VARIANT == 0) {
-        // permlane16_swap(a, b): swaps odd rows of a with even rows of b.
-        //   with a = b = x:  r[0] = (x0, x0, x2, x2), r[1] = (x1, x1, x3, x3)
-        // permlane32_swap(a, b): swaps the upper half of a with the lower half of b.
-        //   with a = b = y:  r[0] = (y_lo, y_lo),    r[1] = (y_hi, y_hi)
-        const auto p16 = __builtin_amdgcn_permlane16_swap(x, x, false, false);
-        const auto pa = __builtin_amdgcn_permlane32_swap(p16[0], p16[0], false, false);
-        const auto pb = __builtin_amdgcn_permlane32_swap(p16[1], p16[1], false, false);
-        b0 = pa[0];
-        b2 = pa[1];
-        b1 = pb[0];
-        b3 = pb[1];
-    } else {
-        const int c = lane & 15;
-        b0 = __shfl((int)x, c, 64);
-        b1 = __shfl((int)x, 16 + c, 64);
-        b2 = __shfl((int)x, 32 + c, 64);
-        b3 = __shfl((int)x, 48 + c, 64);
-    }
+// Broadcast the value held by each 16-lane row r (x_r) so that every lane gets x_0..x_3, with
+// v_permlane16_swap + v_permlane32_swap (gfx950 VALU cross-row moves).
+__device__ __forceinline__ void bcast_rows32(uint32_t x, uint32_t& b0, uint32_t& b1, uint32_t& b2, uint32_t& b3) {
+    // permlane16_swap(a, b): swaps odd rows of a with even rows of b.
+    //   with a = b = x:  r[0] = (x0, x0, x2, x2), r[1] = (x1, x1, x3, x3)
+    // permlane32_swap(a, b): swaps the upper half of a with the lower half of b.
+    //   with a = b = y:  r[0] = (y_lo, y_lo),    r[1] = (y_hi, y_hi)
+    const auto p16 = __builtin_amdgcn_permlane16_swap(x, x, false, false);
+    const auto pa = __builtin_amdgcn_permlane32_swap(p16[0], p16[0], false, false);
+    const auto pb = __builtin_amdgcn_permlane32_swap(p16[1], p16[1], false, false);
+    b0 = pa[0];
+    b2 = pa[1];
+    b1 = pb[0];
+    b3 = pb[1];
 }
 
-template <int VARIANT>
-__device__ __forceinline__ void bcast_rows64(uint64_t x, uint64_t t[4], int lane) {
+__device__ __forceinline__ void bcast_rows64(uint64_t x, uint64_t t[4]) {
     uint32_t l0, l1, l2, l3, h0, h1, h2, h3;
-    bcast_rows32<VARIANT>((uint32_t)x, l0, l1, l2, l3, lane);
-    bcast_rows32<VARIANT>((uint32_t)(x >> 32), h0, h1, h2, h3, lane);
+    bcast_rows32((uint32_t)x, l0, l1, l2, l3);
+    bcast_rows32((uint32_t)(x >> 32), h0, h1, h2, h3);
     t[0] = ((uint64_t)h0 << 32) | l0;
     t[1] = ((uint64_t)h1 << 32) | l1;
     t[2] = ((uint64_t)h2 << 32) | l2;
     t[3] = ((uint64_t)h3 << 32) | l3;
 }
 
-// Kernel variant knobs (diagnostic A/B through oxh_set_kernel_variant; 0 is the shipped path):
-//   bit 0     cross-row broadcast: 0 = permlane16/32 swaps, 1 = ds_bpermute (__shfl)
-//   bit 1     0 = non-temporal (nt) loads for the once-read input stream, 1 = default-policy loads
-//   bits 2-3  rounds in flight per wave (software pipeline depth): 0 -> 4, 1 -> 3, 2 -> 2, 3 -> 5
-//   bit 4     1 = stagger: waves of the first resident generation start 0..15 x ~1 us apart
-//   bit 5     1 = block-wise layout: load j of a round reads block j whole (1 KiB contiguous per
-//             wave-instruction; lane l holds stripe l/4, piece l%4 of every block, so its keys are
-//             fixed), and a reduce-scatter across rows (permlane32/16 swaps) hands row g block g's
-//             partial sums before the usual in-row fold. 0 = row-wise: row g reads block g, 256 B per
-//             instruction. At a start that is not 128-B aligned a row-wise instruction touches 12
-//             lines per KiB, a block-wise one 9 (tools/k1_small_probe.py).
-//   bit 6     1 = stripe keys read from an LDS copy of the secret at each use (fewer VGPRs)
-//   bit 8     1 = K1R, one 16-lane row per item and four items per wave (rows_item below; bits 1-3
-//             as above, the others unused)
-//   bit 9     K1R only: 1 = K1H, two rows per item and two items per wave
-//   bit 10    1 = rotated start (K1 only): item i visits its first min(nr, 16) full rounds starting at
-//             round i % 16, stashing the block sums of the rounds it reads before round 0 in LDS and
-//             replaying them into the chain in order -- so the waves in flight, whose items all start
-//             on 64 KiB boundaries in C2's arena, read at addresses 4 KiB apart instead of in lockstep
-// Measured on MI355X (C2, tools/readbw.py, profiles/r01_readbw*.json): nt loads ~+11 % over
-// default-policy loads; 4 rounds in flight (2 waves/SIMD at 180 VGPRs) ~+4 % over 2 rounds (5 waves/SIMD).
+// The K1 shapes, by the variant number the dispatch (capi_dispatch.hip), oxh_set_kernel_variant, the
+// benchmark and the profile records know them by. Every shape loads the once-read input non-temporal
+// (~+11 % over default-policy loads on C2: tools/readbw.py, profiles/r01_readbw*.json). VGPRs and
+// waves per SIMD are those of the descriptor-table kernel (.vgpr_count in the .s).
+//     0  4-round ring, row-wise, keys in registers (210 VGPRs, 2 waves): the fallback that any other
+//        forced number runs
+//     8  2-round ring, row-wise, keys in registers (142, 3 waves): long items (kVariantLong)
+//    72  2-round ring, row-wise, keys in LDS (91, 5 waves): items of a few KiB (kVariantShort); K1T
+//        runs this shape at every size (154 with the counting)
+//   104  2-round ring, block-wise, keys in LDS (86, 5 waves): items packed back to back, one per wave
+//        (kVariantPacked)
+//   264  K1R, 2-deep ring (84, 5 waves): one 16-lane row per item, four packed items per wave
+//        (rows_item below; kVariantRows)
+// DEPTH      rounds in flight per wave (software pipeline depth).
+// BLOCKWISE  load j of a round reads block j whole (1 KiB contiguous per wave-instruction; lane l
+//            holds stripe l/4, piece l%4 of every block, so its keys are fixed), and a reduce-scatter
+//            across rows (permlane32/16 swaps) hands row g block g's partial sums before the usual
+//            in-row fold. Row-wise: row g reads block g, 256 B per instruction. At a start that is not
+//            128-B aligned a row-wise instruction touches 12 lines per KiB, a block-wise one 9
+//            (tools/k1_small_probe.py).
+// KEYS_LDS   stripe keys read from an LDS copy of the secret at each use (fewer VGPRs).
 template <int V>
 struct Cfg {
-    static constexpr int BCAST = V & 1;
-    static constexpr bool NT = ((V >> 1) & 1) == 0;
-    static constexpr int DEPTH = ((V >> 2) & 3) == 0 ? 4 : ((V >> 2) & 3) == 1 ? 3 : ((V >> 2) & 3) == 2 ? 2 : 5;
-    static constexpr bool KEYS_LDS = ((V >> 6) & 1) != 0;
-    static constexpr bool STAGGER = ((V >> 4) & 1) != 0;
+    static_assert(V == 0 || V == 8 || V == 72 || V == 104 || V == 264, "not a shipped K1 shape");
+    static constexpr int DEPTH = V == 0 ? 4 : 2;
     static constexpr bool BLOCKWISE = ((V >> 5) & 1) != 0;
+    static constexpr bool KEYS_LDS = ((V >> 6) & 1) != 0;
     static constexpr bool ROWS = ((V >> 8) & 1) != 0;
-    static constexpr bool ROWS2 = ((V >> 9) & 1) != 0;
-    static constexpr bool ROT = ((V >> 10) & 1) != 0;
 };
 
-template <bool ALIGNED, bool NT = false>
+template <bool ALIGNED>
 __device__ __forceinline__ uint4 load16(const uint8_t* p) {
-    if constexpr (ALIGNED && NT) {
-        typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-        const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
-        return make_uint4(v.x, v.y, v.z, v.w);
-    } else if constexpr (ALIGNED) {
+    if constexpr (ALIGNED) {
         return *reinterpret_cast<const uint4*>(p);
     } else {
         uint4 v;
@@ -160,18 +140,34 @@ __device__ __forceinline__ void count16(const uint4 d, uint32_t& nl, uint32_t& c
     cont += count_cont32(d.x) + count_cont32(d.y) + count_cont32(d.z) + count_cont32(d.w);
 }
 
-// Fold a round: in-row stripe reduction, cross-row broadcast, 4 chain steps.
-// nfull: how many of the 4 blocks are full (scrambled); block nfull (if < 4) is the partial one.
-template <int VARIANT>
-__device__ __forceinline__ void fold_round(uint64_t s0, uint64_t s1, uint64_t& a0, uint64_t& a1,
-                                           uint64_t sk0, uint64_t sk1, int nfull, int lane) {
+// Finish a block sum inside each 16-lane row: lanes (q, k) of a row hold the sums of stripes
+// {q, q+4, q+8, q+12} for accumulators (2k, 2k+1); afterwards every lane holds the 16-stripe sum.
+// (xxh3_blocksum_kernel spells the same four adds out: through this helper hipcc allocates its
+// registers differently.)
+__device__ __forceinline__ void row_fold(uint64_t& s0, uint64_t& s1) {
     s0 += dpp64<DPP_ROW_ROR4>(s0);
     s1 += dpp64<DPP_ROW_ROR4>(s1);
     s0 += dpp64<DPP_ROW_ROR8>(s0);
     s1 += dpp64<DPP_ROW_ROR8>(s1);
+}
+
+// The last stripe, at len - 64, with the secret shifted to offset 121: `last` is the lane's 16 B of
+// it (words 2k, 2k+1), accumulated into (a0, a1).
+__device__ __forceinline__ void last_stripe(const uint4 last, int k, uint64_t& a0, uint64_t& a1) {
+    const uint64_t w0 = ((uint64_t)last.y << 32) | last.x, w1 = ((uint64_t)last.w << 32) | last.z;
+    const uint64_t k0 = w0 ^ kLastW[2 * k], k1 = w1 ^ kLastW[2 * k + 1];
+    a0 += mul32x32(k0) + w1;
+    a1 += mul32x32(k1) + w0;
+}
+
+// Fold a round: in-row stripe reduction, cross-row broadcast, 4 chain steps.
+// nfull: how many of the 4 blocks are full (scrambled); block nfull (if < 4) is the partial one.
+__device__ __forceinline__ void fold_round(uint64_t s0, uint64_t s1, uint64_t& a0, uint64_t& a1,
+                                           uint64_t sk0, uint64_t sk1, int nfull) {
+    row_fold(s0, s1);
     uint64_t t0[4], t1[4];
-    bcast_rows64<VARIANT>(s0, t0, lane);
-    bcast_rows64<VARIANT>(s1, t1, lane);
+    bcast_rows64(s0, t0);
+    bcast_rows64(s1, t1);
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
         if (g < nfull) {
@@ -230,8 +226,7 @@ __device__ __forceinline__ uint4 bload16(__amdgpu_buffer_rsrc_t rsrc, uint32_t v
 template <int VARIANT, bool TEXT, bool BS>
 __device__ __forceinline__ void wave_long(const uint8_t* __restrict__ p, uint64_t len,
                                           uint64_t* __restrict__ out, int lane, const uint64_t* lds_sec,
-                                          uint64_t* __restrict__ counts, uint32_t bs = 0, uint64_t* stash = nullptr,
-                                          uint64_t phase = 0) {
+                                          uint64_t* __restrict__ counts, uint32_t bs = 0) {
     constexpr bool BW = Cfg<VARIANT>::BLOCKWISE;
     constexpr uint32_t JSTRIDE = BW ? 1024u : 256u;  // bytes between a lane's loads j and j+1
     const int g = lane >> 4, q = (lane >> 2) & 3, k = lane & 3;
@@ -285,14 +280,13 @@ __device__ __forceinline__ void wave_long(const uint8_t* __restrict__ p, uint64_
             // first dword completes the last live piece; dwords past the item read as 0)
             const bool fp = fin_part(j);
             const bool extra = BS && (rr == nr) & fp & (stripe_of(j) == ns) & (k == 0);
-            dst[j] = bload16<Cfg<VARIANT>::NT>(rsrc, (live_j(rr, j) | extra) ? vo + j * JSTRIDE : kOOB);
+            dst[j] = bload16<true>(rsrc, (live_j(rr, j) | extra) ? vo + j * JSTRIDE : kOOB);
         }
         if constexpr (BS) {
             // the dword right after the last piece of load 3, for the lane that holds that piece
             // (row-wise: each row's last lane, 15 / 31 / 47 / 63; block-wise: lane 63)
             const bool tail = BW ? lane == 63 : (lane & 15) == 15;
-            ext = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (tail && live_j(rr, 3)) ? vo + 3 * JSTRIDE + 16 : kOOB, 0,
-                                                       Cfg<VARIANT>::NT ? 2 : 0);
+            ext = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (tail && live_j(rr, 3)) ? vo + 3 * JSTRIDE + 16 : kOOB, 0, 2);
         } else {
             ext = 0;
         }
@@ -343,57 +337,7 @@ __device__ __forceinline__ void wave_long(const uint8_t* __restrict__ p, uint64_
                 }
             }
         }
-        fold_round<Cfg<VARIANT>::BCAST>(s0, s1, a0, a1, sk0, sk1, partial ? (int)(nb - nr * 4) : 4, lane);
-    };
-    // ROT: visit v of the full rounds reads round seq(v). With phi > 0 the first wr - phi visits read
-    // rounds phi .. wr-1 and stash their block sums (slot v), the next phi read rounds 0 .. phi-1 into
-    // the chain, and the stash is then replayed in order; visits from wr on read round v.
-    constexpr bool ROT = Cfg<VARIANT>::ROT && !BW;
-    const uint64_t wr = ROT ? (nr < 16 ? nr : 16) : 0;
-    const uint64_t phi = (ROT && wr >= 2) ? phase % wr : 0;
-    auto seq = [&](uint64_t v) -> uint64_t {
-        if (!ROT || phi == 0 || v >= wr) return v;
-        return v < wr - phi ? phi + v : v - (wr - phi);
-    };
-    // a full round's block sums: row g's lanes q == 0 hold block g's, accumulators (2k, 2k + 1)
-    auto stash4 = [&](uint4 (&src)[4], uint32_t ext, uint64_t slot) {
-        realign(src, ext);
-        uint64_t s0 = 0, s1 = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            uint64_t k0, k1;
-            keys(j, k0, k1);
-            accum16(src[j], k0, k1, s0, s1);
-            if constexpr (TEXT) count16(src[j], n_nl, n_cont);
-        }
-        s0 += dpp64<DPP_ROW_ROR4>(s0);
-        s1 += dpp64<DPP_ROW_ROR4>(s1);
-        s0 += dpp64<DPP_ROW_ROR8>(s0);
-        s1 += dpp64<DPP_ROW_ROR8>(s1);
-        if (q == 0) {
-            const uint32_t at = (uint32_t)(((slot * 4 + (uint64_t)g) * 4 + (uint64_t)k) * 2);
-            stash[at] = s0;
-            stash[at + 1] = s1;
-        }
-    };
-    auto replay = [&]() {
-        for (uint64_t slot = 0; slot < wr - phi; ++slot) {
-#pragma unroll
-            for (int gg = 0; gg < 4; ++gg) {
-                const uint32_t at = (uint32_t)(((slot * 4 + (uint64_t)gg) * 4 + (uint64_t)k) * 2);
-                a0 = scramble1(a0 + stash[at], sk0);
-                a1 = scramble1(a1 + stash[at + 1], sk1);
-            }
-        }
-    };
-    // fold visit v (a full round), replaying the stash after the window's last visit
-    auto visit = [&](uint4 (&src)[4], uint32_t ext, uint64_t v) {
-        if (ROT && phi != 0 && v < wr - phi) {
-            stash4(src, ext, v);
-        } else {
-            fold4(src, ext, seq(v), false);
-            if (ROT && phi != 0 && v == wr - 1) replay();
-        }
+        fold_round(s0, s1, a0, a1, sk0, sk1, partial ? (int)(nb - nr * 4) : 4);
     };
     // the last stripe (at len - 64, secret offset 121) is fetched up front with the first rounds
     const __amdgpu_buffer_rsrc_t rsrc_last =
@@ -408,14 +352,13 @@ __device__ __forceinline__ void wave_long(const uint8_t* __restrict__ p, uint64_
         uint4 ring[D][4];
         uint32_t ext[D];
 #pragma unroll
-        for (int d = 0; d < D; ++d) load_round(seq((uint64_t)d), ring[d], ext[d]);
+        for (int d = 0; d < D; ++d) load_round((uint64_t)d, ring[d], ext[d]);
         uint64_t r = 0;
         for (; r + D <= nr; r += D) {  // every slot holds a full round
 #pragma unroll
             for (int d = 0; d < D; ++d) {
-                if constexpr (ROT) visit(ring[d], ext[d], r + d);
-                else fold4(ring[d], ext[d], r + d, false);
-                load_round(seq(r + d + D), ring[d], ext[d]);
+                fold4(ring[d], ext[d], r + d, false);
+                load_round(r + d + D, ring[d], ext[d]);
                 // keep slot d+1's arithmetic below this point: otherwise the scheduler hoists its
                 // data-only adds above the refill and hipcc has to drain every load (vmcnt(0))
                 __builtin_amdgcn_sched_barrier(0);
@@ -425,20 +368,13 @@ __device__ __forceinline__ void wave_long(const uint8_t* __restrict__ p, uint64_
 #pragma unroll
         for (int d = 0; d < D; ++d) {
             if (r + d < nr) {
-                if constexpr (ROT) visit(ring[d], ext[d], r + d);
-                else fold4(ring[d], ext[d], r + d, false);
+                fold4(ring[d], ext[d], r + d, false);
             } else if (r + d == nr) {
                 fold4(ring[d], ext[d], r + d, true);
             }
         }
     }
-    // last stripe, at len - 64, with the secret shifted to offset 121
-    {
-        const uint64_t w0 = ((uint64_t)last.y << 32) | last.x, w1 = ((uint64_t)last.w << 32) | last.z;
-        const uint64_t k0 = w0 ^ kLastW[2 * k], k1 = w1 ^ kLastW[2 * k + 1];
-        a0 += mul32x32(k0) + w1;
-        a1 += mul32x32(k1) + w0;
-    }
+    last_stripe(last, k, a0, a1);
     if constexpr (TEXT) {
         // bytes [E, len) not covered by the stripes above come from the last stripe, which always
         // spans them (len - E is 1..64); `last` depends only on k, so only lanes 0..3 count it
@@ -446,9 +382,6 @@ __device__ __forceinline__ void wave_long(const uint8_t* __restrict__ p, uint64_
         const uint64_t p0 = len - 64 + 16 * (uint64_t)k;
         const uint32_t skip = E > p0 ? (uint32_t)(E - p0 < 16 ? E - p0 : 16) : 0u;
         const uint32_t w[4] = {last.x, last.y, last.z, last.w};
-#ifdef OXH_DEBUG_LANES
-        const uint32_t dbg_ring = n_nl;
-#endif
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
             const int sd = (int)skip - 4 * d;
@@ -458,11 +391,6 @@ __device__ __forceinline__ void wave_long(const uint8_t* __restrict__ p, uint64_
                 n_cont += count_cont32(w[d] & m);
             }
         }
-#ifdef OXH_DEBUG_LANES
-        counts[2 + 3 * lane] = dbg_ring;
-        counts[3 + 3 * lane] = n_nl;
-        counts[4 + 3 * lane] = skip;
-#endif
 #pragma unroll
         for (int off = 1; off < 64; off <<= 1) {
             n_nl += (uint32_t)__shfl_xor((int)n_nl, off, 64);
@@ -493,8 +421,6 @@ __device__ __forceinline__ void wave_item(const uint8_t* __restrict__ arena, con
                                           const uint64_t* __restrict__ lens, uint64_t n, uint64_t chunk,
                                           uint64_t total, uint64_t* __restrict__ out, uint64_t* __restrict__ counts) {
     __shared__ uint64_t lds_sec[24];
-    // ROT: 16 rounds x 4 blocks x 8 accumulators per wave (4 waves per workgroup at most)
-    __shared__ uint64_t rot_stash[Cfg<VARIANT>::ROT ? 4 * 16 * 32 : 1];
     if constexpr (Cfg<VARIANT>::KEYS_LDS) {
         if (threadIdx.x < 24) lds_sec[threadIdx.x] = kSecW[threadIdx.x];
         __syncthreads();
@@ -503,12 +429,6 @@ __device__ __forceinline__ void wave_item(const uint8_t* __restrict__ arena, con
     // one item per wave; launched with 1, 2 or 4 waves per workgroup (blockDim.x = 64 * waves)
     const uint64_t item = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (uint64_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (item >= n) return;
-    if constexpr (Cfg<VARIANT>::STAGGER) {
-        if (blockIdx.x < 2048) {
-            const int steps = (int)(item & 15) * 40;  // s_sleep 1 ~ 64 clocks
-            for (int t = 0; t < steps; ++t) __builtin_amdgcn_s_sleep(1);
-        }
-    }
     uint64_t off, len;
     if constexpr (DESC) {
         off = offsets[item];
@@ -541,11 +461,10 @@ __device__ __forceinline__ void wave_item(const uint8_t* __restrict__ arena, con
     const uint32_t bs = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 3);
     const uint64_t nb_ = (len - 1) >> 10;
     const uint64_t E = (nb_ << 10) + ((((len - 1) - (nb_ << 10)) >> 6) << 6);
-    uint64_t* stash = Cfg<VARIANT>::ROT ? rot_stash + (threadIdx.x >> 6) * (16 * 32) : nullptr;
     if (bs && len - E >= 4)
-        wave_long<VARIANT, TEXT, true>(p, len, o, lane, lds_sec, TEXT ? counts + 2 * item : nullptr, bs, stash, item);
+        wave_long<VARIANT, TEXT, true>(p, len, o, lane, lds_sec, TEXT ? counts + 2 * item : nullptr, bs);
     else
-        wave_long<VARIANT, TEXT, false>(p, len, o, lane, lds_sec, TEXT ? counts + 2 * item : nullptr, 0, stash, item);
+        wave_long<VARIANT, TEXT, false>(p, len, o, lane, lds_sec, TEXT ? counts + 2 * item : nullptr);
 }
 
 __device__ __forceinline__ uint64_t readlane64(uint64_t x, int l) {
@@ -564,10 +483,6 @@ __device__ __forceinline__ uint64_t readlane64(uint64_t x, int l) {
 // and 4 chain steps per round on every lane -- and is VALU-issue bound there (SQ_ACTIVE_INST_VALU at
 // the SIMDs' issue capacity, profiles/r04e_cdc_pmc.txt); here a 4 KiB iteration (one block of each
 // of 4 items) takes ~138 (the loop's .s), and packed items become bound by their access pattern.
-// RPI = 2 (Cfg bit 9, "K1H"): two rows (32 lanes) per item, two items per wave. Load j (0..1) reads
-// 512 contiguous bytes of the item (5 lines when unaligned, against 2 x 3 for two row loads); the lane
-// sums stripes {t/4, 8 + t/4} (t = lane % 32); the block sum takes one permlane16 swap more, and each
-// item's chain runs once per block on its 32 lanes.
 // The items of a wave run in lockstep to the longest one; a row whose item is done idles (its loads
 // go to kOOB and are dropped). All rows address their items through ONE buffer descriptor (it is
 // wave-uniform) over [lowest start, highest end) of the wave's items; items further apart than that
@@ -579,18 +494,13 @@ __device__ __forceinline__ void rows_item(const uint8_t* __restrict__ arena, con
                                           const uint64_t* __restrict__ lens, uint64_t n, uint64_t chunk,
                                           uint64_t total, uint64_t* __restrict__ out) {
     constexpr int D = Cfg<VARIANT>::DEPTH;
-    constexpr bool NT = Cfg<VARIANT>::NT;
-    constexpr int RPI = Cfg<VARIANT>::ROWS2 ? 2 : 1;  // 16-lane rows per item
-    constexpr int LPI = 16 * RPI;                      // lanes per item
-    constexpr int IPW = 4 / RPI;                       // items per wave
-    constexpr int NL = 4 / RPI;                        // loads per 1 KiB block, 256 * RPI bytes each
     const int lane = threadIdx.x & 63;
-    const int t = lane & (LPI - 1), k = lane & 3, st0 = t >> 2;  // the lane's stripe in load j: 4*RPI*j + st0
+    const int t = lane & 15, k = lane & 3, q = t >> 2;  // the lane's stripe in load j: 4j + q
     const bool head = t == 0;
     const uint64_t first =
-        ((uint64_t)blockIdx.x * (blockDim.x >> 6) + (uint64_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) * IPW;
+        ((uint64_t)blockIdx.x * (blockDim.x >> 6) + (uint64_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) * 4;
     if (first >= n) return;
-    const uint64_t item = first + (uint64_t)(lane / LPI);
+    const uint64_t item = first + (uint64_t)(lane / 16);
     const bool valid = item < n;
     uint64_t off = 0, len = 0;
     if (valid) {
@@ -610,9 +520,9 @@ __device__ __forceinline__ void rows_item(const uint8_t* __restrict__ arena, con
     // the wave's long items under one descriptor: [lowest aligned start, highest end)
     uint64_t wlo = ~0ull, whi = 0;
 #pragma unroll
-    for (int r = 0; r < IPW; ++r) {
-        const uint64_t a = readlane64(lng ? astart : ~0ull, LPI * r);
-        const uint64_t e = readlane64(lng ? start + len : 0, LPI * r);
+    for (int r = 0; r < 4; ++r) {
+        const uint64_t a = readlane64(lng ? astart : ~0ull, 16 * r);
+        const uint64_t e = readlane64(lng ? start + len : 0, 16 * r);
         wlo = a < wlo ? a : wlo;
         whi = e > whi ? e : whi;
     }
@@ -626,11 +536,11 @@ __device__ __forceinline__ void rows_item(const uint8_t* __restrict__ arena, con
         }
         return;
     }
-    uint64_t key0[NL], key1[NL];
+    uint64_t key0[4], key1[4];
 #pragma unroll
-    for (int j = 0; j < NL; ++j) {
-        key0[j] = kSecW[4 * RPI * j + st0 + 2 * k];
-        key1[j] = kSecW[4 * RPI * j + st0 + 2 * k + 1];
+    for (int j = 0; j < 4; ++j) {
+        key0[j] = kSecW[4 * j + q + 2 * k];
+        key1[j] = kSecW[4 * j + q + 2 * k + 1];
     }
     const uint64_t sk0 = kSecW[16 + 2 * k], sk1 = kSecW[16 + 2 * k + 1];
     if (whi != 0) {
@@ -642,66 +552,51 @@ __device__ __forceinline__ void rows_item(const uint8_t* __restrict__ arena, con
         const uint32_t ns = act ? (uint32_t)(((len - 1) - ((uint64_t)nb << 10)) >> 6) : 0;
         uint32_t B = 0;  // the wave's last iteration: its longest item's partial block
 #pragma unroll
-        for (int r = 0; r < IPW; ++r) {
-            const uint32_t x = (uint32_t)__builtin_amdgcn_readlane((int)nb, LPI * r);
+        for (int r = 0; r < 4; ++r) {
+            const uint32_t x = (uint32_t)__builtin_amdgcn_readlane((int)nb, 16 * r);
             B = x > B ? x : B;
         }
         const bool shifted = act && bs != 0;
-        // pieces j < jpart of the partial block are live (stripe 4*RPI*j + st0 < ns)
-        const uint32_t jpart = act && ns > (uint32_t)st0 ? (ns - (uint32_t)st0 + 4 * RPI - 1) / (4 * RPI) : 0u;
+        // pieces j < jpart of the partial block are live (stripe 4j + q < ns)
+        const uint32_t jpart = act && ns > (uint32_t)q ? (ns - (uint32_t)q + 3) / 4 : 0u;
         uint64_t a0 = kInitW[2 * k], a1 = kInitW[2 * k + 1];
-        // pieces j < live_n(b) of iteration b are live: NL in a full block, jpart in the partial one
-        auto live_n = [&](uint32_t b) -> uint32_t { return (act & (b < nb)) ? (uint32_t)NL : (b == nb) ? jpart : 0u; };
+        // pieces j < live_n(b) of iteration b are live: 4 in a full block, jpart in the partial one
+        auto live_n = [&](uint32_t b) -> uint32_t { return (act & (b < nb)) ? 4u : (b == nb) ? jpart : 0u; };
         const __amdgpu_buffer_rsrc_t rsrc =
             __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(base), (short)0, (int)(uint32_t)span, kRsrcFlags);
         // Byte-shifted items load every piece 4 bytes late: the lane then holds dwords w1..w4 of the
         // five its piece spans (w0 = the dword holding the piece's first byte) and takes w0 from the
-        // previous lane's w4 (DPP row_ror:1; a row's first lane from the previous row of the item
-        // through a permlane16 swap (RPI 2), or from the previous load, for load 0 from the previous
-        // iteration (`carry`; before the first, one dword load). No load reads past a live piece, and
-        // no extra loads are needed per iteration. v_perm_b32 then picks bytes bs..bs+3 of each dword
-        // pair; an aligned item loads on time and picks bytes 4..7 (the loaded dword itself).
+        // previous lane's w4 (DPP row_ror:1; a row's first lane from the previous load, for load 0 from
+        // the previous iteration (`carry`; before the first, one dword load). No load reads past a live
+        // piece, and no extra loads are needed per iteration. v_perm_b32 then picks bytes bs..bs+3 of
+        // each dword pair; an aligned item loads on time and picks bytes 4..7 (the loaded dword itself).
         const uint32_t late = shifted ? 4u : 0u;
         const uint32_t psel = 0x03020100u + 0x01010101u * (shifted ? bs : 4u);
-        auto load_iter = [&](uint32_t b, uint4 (&dst)[NL]) {
+        auto load_iter = [&](uint32_t b, uint4 (&dst)[4]) {
             const uint32_t vo = vb + (b << 10) + 16u * (uint32_t)t + late;
             const uint32_t jn = live_n(b);
 #pragma unroll
-            for (int j = 0; j < NL; ++j) dst[j] = bload16<NT>(rsrc, (uint32_t)j < jn ? vo + (uint32_t)(256 * RPI * j) : kOOB);
+            for (int j = 0; j < 4; ++j) dst[j] = bload16<true>(rsrc, (uint32_t)j < jn ? vo + (uint32_t)(256 * j) : kOOB);
         };
         uint32_t carry = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (shifted & head) ? vb : kOOB, 0, 0);
-        auto fold = [&](uint4 (&src)[NL], uint32_t b) {
-            uint32_t w0s[NL];
+        auto fold = [&](uint4 (&src)[4], uint32_t b) {
+            uint32_t w0s[4];
 #pragma unroll
-            for (int j = 0; j < NL; ++j) {
+            for (int j = 0; j < 4; ++j) {
                 const uint32_t pw = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)src[j].w, 0x121, 0xf, 0xf, false);
-                if constexpr (RPI == 1) {
-                    w0s[j] = head ? carry : pw;
-                    carry = pw;  // lane 0 of the row now holds the row's last w4
-                } else {
-                    // rows (0, 1) of the item: swap[0] gives row 1 row 0's values, swap[1] row 0 row 1's
-                    const auto sw = __builtin_amdgcn_permlane16_swap(pw, pw, false, false);
-                    w0s[j] = head ? carry : (t == 16 ? sw[0] : pw);
-                    carry = sw[1];  // lane 0 of the item now holds the item's last w4 of this load
-                }
+                w0s[j] = head ? carry : pw;
+                carry = pw;  // lane 0 of the row now holds the row's last w4
             }
             const uint32_t jn = live_n(b);
             uint64_t s0 = 0, s1 = 0;
 #pragma unroll
-            for (int j = 0; j < NL; ++j) {
+            for (int j = 0; j < 4; ++j) {
                 const uint4 a = src[j];
                 const uint4 d = make_uint4(__builtin_amdgcn_perm(a.x, w0s[j], psel), __builtin_amdgcn_perm(a.y, a.x, psel),
                                            __builtin_amdgcn_perm(a.z, a.y, psel), __builtin_amdgcn_perm(a.w, a.z, psel));
                 if ((uint32_t)j < jn) accum16(d, key0[j], key1[j], s0, s1);
             }
-            s0 += dpp64<DPP_ROW_ROR4>(s0);
-            s1 += dpp64<DPP_ROW_ROR4>(s1);
-            s0 += dpp64<DPP_ROW_ROR8>(s0);
-            s1 += dpp64<DPP_ROW_ROR8>(s1);
-            if constexpr (RPI == 2) {
-                s0 = swap16_add(s0, s0);  // the item's two rows
-                s1 = swap16_add(s1, s1);
-            }
+            row_fold(s0, s1);
             const bool full = act & (b < nb), part = act & (b == nb);
             const uint64_t t0 = a0 + s0, t1 = a1 + s1;
             const uint64_t c0 = scramble1(t0, sk0), c1 = scramble1(t1, sk1);
@@ -711,7 +606,7 @@ __device__ __forceinline__ void rows_item(const uint8_t* __restrict__ arena, con
         // the last stripe (at len - 64, secret offset 121), fetched with the first iterations
         const uint4 last = bload16<false>(rsrc, act ? vb + bs + (uint32_t)len - 64 + 16 * (uint32_t)k : kOOB);
         {
-            uint4 ring[D][NL];
+            uint4 ring[D][4];
 #pragma unroll
             for (int d = 0; d < D; ++d) load_iter((uint32_t)d, ring[d]);
             // one loop to the end, the last group's folds guarded: with a separate tail after the loop
@@ -725,12 +620,7 @@ __device__ __forceinline__ void rows_item(const uint8_t* __restrict__ arena, con
                 }
             }
         }
-        {
-            const uint64_t w0 = ((uint64_t)last.y << 32) | last.x, w1 = ((uint64_t)last.w << 32) | last.z;
-            const uint64_t k0 = w0 ^ kLastW[2 * k], k1 = w1 ^ kLastW[2 * k + 1];
-            a0 += mul32x32(k0) + w1;
-            a1 += mul32x32(k1) + w0;
-        }
+        last_stripe(last, k, a0, a1);
         uint64_t mlo = mul_fold64(a0 ^ kMrgLo[2 * k], a1 ^ kMrgLo[2 * k + 1]);
         uint64_t mhi = mul_fold64(a0 ^ kMrgHi[2 * k], a1 ^ kMrgHi[2 * k + 1]);
         mlo += dpp64<DPP_QUAD_XOR1>(mlo);
@@ -1090,9 +980,8 @@ __global__ void fill_splitmix_tail_kernel(uint8_t* __restrict__ dst, uint64_t wo
     for (uint64_t j = 0; j < nbytes; ++j) dst[j] = (uint8_t)(v >> (8 * j));
 }
 
-// explicit instantiations used by the host runtime (variants: see Cfg). The shipped library carries
-// the shapes the dispatch picks (8, 72, 104, 264) and the fallback 0; the experiments that lost their
-// A/Bs only in the probe build (tools/build_probe_lib.sh, -DOXH_PROBE_VARIANTS).
+// explicit instantiations used by the host runtime: the shapes the dispatch picks (8, 72, 104, 264)
+// and the fallback 0 (see Cfg)
 template __global__ void xxh3_wave_kernel<true, 0>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
 template __global__ void xxh3_wave_kernel<false, 0>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
 template __global__ void xxh3_wave_kernel<true, 8>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
@@ -1103,36 +992,6 @@ template __global__ void xxh3_wave_kernel<true, 104>(const uint8_t*, const uint6
 template __global__ void xxh3_wave_kernel<false, 104>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
 template __global__ void xxh3_wave_kernel<true, 264>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
 template __global__ void xxh3_wave_kernel<false, 264>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
-#ifdef OXH_PROBE_VARIANTS
-template __global__ void xxh3_wave_kernel<true, 1>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
-template __global__ void xxh3_wave_kernel<false, 1>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
-template __global__ void xxh3_wave_kernel<true, 2>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
-template __global__ void xxh3_wave_kernel<false, 2>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
-template __global__ void xxh3_wave_kernel<true, 4>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
-template __global__ void xxh3_wave_kernel<false, 4>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
-template __global__ void xxh3_wave_kernel<true, 12>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
-template __global__ void xxh3_wave_kernel<false, 12>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
-template __global__ void xxh3_wave_kernel<true, 40>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
-template __global__ void xxh3_wave_kernel<false, 40>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
-template __global__ void xxh3_wave_kernel<true, 64>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
-template __global__ void xxh3_wave_kernel<false, 64>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
-template __global__ void xxh3_wave_kernel<true, 74>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
-template __global__ void xxh3_wave_kernel<false, 74>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
-template __global__ void xxh3_wave_kernel<true, 256>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
-template __global__ void xxh3_wave_kernel<false, 256>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
-template __global__ void xxh3_wave_kernel<true, 260>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
-template __global__ void xxh3_wave_kernel<false, 260>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
-template __global__ void xxh3_wave_kernel<true, 768>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
-template __global__ void xxh3_wave_kernel<false, 768>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
-template __global__ void xxh3_wave_kernel<true, 772>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
-template __global__ void xxh3_wave_kernel<false, 772>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
-template __global__ void xxh3_wave_kernel<true, 776>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
-template __global__ void xxh3_wave_kernel<false, 776>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
-template __global__ void xxh3_wave_kernel<true, 1032>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
-template __global__ void xxh3_wave_kernel<false, 1032>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
-template __global__ void xxh3_wave_kernel<true, 1024>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
-template __global__ void xxh3_wave_kernel<false, 1024>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t, uint64_t, uint64_t*);
-#endif
 template __global__ void xxh3_text_wave_kernel<72>(const uint8_t*, const uint64_t*, const uint64_t*, uint64_t, uint64_t*, uint64_t*);
 template __global__ void xxh3_blocksum_kernel<true>(const uint8_t*, uint64_t, uint64_t*);
 template __global__ void xxh3_blocksum_kernel<false>(const uint8_t*, uint64_t, uint64_t*);

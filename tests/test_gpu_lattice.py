@@ -17,9 +17,12 @@ pytestmark = pytest.mark.gpu
 
 # The K1 shapes the shipped library instantiates, as in test_gpu_parity.py. 0 means "no forced variant": the
 # dispatch then picks 8 for a WAVE batch, so the 4-round ring (Cfg<0>, the fallback of any forced variant
-# that has no kernel) runs only under such a number; 392 is the one test_chunk_digests uses.
+# that has no kernel) runs only under such a number; 392 is the one test_chunk_digests uses. 776 and 1032
+# have the K1R bit and the bits of two experiments that are gone (git history has them): they too must run
+# the 4-round ring at one item per wave, not K1R's launch geometry.
 VARIANTS = [0, 8, 72, 104, 264]
 RING4 = 392
+RING4_FORMER = [776, 1032]
 MODE_WAVE, MODE_LANE, MODE_SHORT, MODE_PACKED = (_capi.OXH_MODE_WAVE, _capi.OXH_MODE_LANE, _capi.OXH_MODE_WAVE_SHORT,
                                                   _capi.OXH_MODE_WAVE_PACKED)
 
@@ -76,11 +79,11 @@ def _assert_digests(got, want, offs, lens, what):
     assert total == 0, f"{what}: {total} of {len(lens)} digests differ, first (shift, len): {first}"
 
 
-@pytest.mark.parametrize("order", ["lattice", "permuted"])
-@pytest.mark.parametrize("variant", VARIANTS + [RING4])
+@pytest.mark.parametrize("variant,order", [(v, o) for o in ("lattice", "permuted") for v in VARIANTS + [RING4]] +
+                         [(v, "lattice") for v in RING4_FORMER])
 def test_k1_wave_lattice(cuda, lattice, arenas, variant, order):
-    """K1 (one wave per item; 264: K1R, a 16-lane row per item; 392: the 4-round ring) over the whole
-    lattice. In lattice order a K1R wave's four rows hold neighbouring lengths; permuted they hold very
+    """K1 (one wave per item; 264: K1R, a 16-lane row per item; 392, 776, 1032: the 4-round ring) over the
+    whole lattice. In lattice order a K1R wave's four rows hold neighbouring lengths; permuted they hold very
     different ones, short (<= 240) items among long ones, in lockstep to the longest."""
     offs, lens, want = lattice["offs"], lattice["lens"], lattice["want"]["splitmix"]
     if order == "permuted":

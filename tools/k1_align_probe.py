@@ -70,7 +70,7 @@ def main():
     from oxen_amd import _capi
     layouts = {"c2_aligned": (np.arange(n) * 65536, np.full(n, 65536)), "ragged_256": (offs256, lens),
                "ragged_packed": (offs_packed, lens2), "ragged_4p1": (offs4 + 1, lens2)}
-    for v in (64, 65, 66, 68, 72, 76, 8):
+    for v in (72, 8):
         _capi.lib().oxh_set_kernel_variant(v)
         for name, (o, ln) in layouts.items():
             res[f"{name}_v{v}"] = case(o, ln)

@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp
 OUT=gpurun_out/k1pmc
 mkdir -p $OUT
-V=${VARIANTS:-104 264 776}
+V=${VARIANTS:-104 264}
 export PROBE_CASES=${PROBE_CASES:-cdc_packed,cdc_256} PROBE_WG=2
 run() {  # name, counters...
   local name=$1

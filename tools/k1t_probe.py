@@ -3,9 +3,9 @@
     python tools/k1t_probe.py
 
 Layouts (~6.5 GB device-resident, HIP-event timed, 20 launches): c2 = 100 000 x 64 KiB packed;
-ragged = lengths uniform in [4 KiB, 128 KiB) packed back to back. Variant 8 / 72 / 4 (= the <0>
-instantiation) forced with oxh_set_kernel_variant. Every K1T launch's digests must equal K1's and
-its counts must match numpy on 256 sampled items.
+ragged = lengths uniform in [4 KiB, 128 KiB) packed back to back. Variant 8 / 72 forced with
+oxh_set_kernel_variant (K1 only: K1T ships one shape). Every K1T launch's digests must equal K1's
+and its counts must match numpy on 256 sampled items.
 """
 from __future__ import annotations
 
@@ -51,7 +51,7 @@ def main():
         sample = rng.choice(n, 256, replace=False)
         want = np.array([[1 + np.count_nonzero(host[offs[i]:offs[i] + lens[i]] == 10),
                           lens[i] - np.count_nonzero((host[offs[i]:offs[i] + lens[i]] & 0xC0) == 0x80)] for i in sample])
-        for v in (8, 72, 4):
+        for v in (8, 72):
             L.oxh_set_kernel_variant(v)
             out = torch.empty((n, 2), dtype=torch.int64, device=dev)
             cnt = torch.empty((n, 2), dtype=torch.int64, device=dev)

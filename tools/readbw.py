@@ -75,7 +75,7 @@ def main():
         return f
 
     ref = None
-    for v in (0, 8, 72):  # the shipped K1 shapes (the probe build has the others: tools/build_probe_lib.py)
+    for v in (0, 8, 72):  # the dispatch's own choice and two shipped K1 shapes
         variants[f"k1_xxh3_v{v}"] = k1(v)
         k1(v)()
         torch.cuda.synchronize()
