@@ -157,8 +157,8 @@ int oxh_hash_files_meta(oxh_ctx* ctx, const char* const* paths, const uint64_t* 
  * renamed into place once the digest is known (host memory stays bounded by the bounce buffers).
  * The reference reads a new file three times and hashes it twice (verify-before-publish); here the
  * published bytes are the hashed bytes, so the check holds by construction.
- * Identical content in several items is published once. stored[i] = 1 for the item that wrote the
- * blob, 0 otherwise. status[i] = OXH_ERR_IO (digest 0) for an unreadable file AND for every item
+ * Identical content in several items is published once. stored[i] = 1 for the first item of a content
+ * whose blob this call wrote, 0 otherwise. status[i] = OXH_ERR_IO (digest 0) for an unreadable file AND for every item
  * whose content could not be published, OXH_ERR_NOMEM as for oxh_hash_files. */
 int oxh_add_files(oxh_ctx* ctx, const char* const* paths, uint64_t n, const char* versions_root,
                   uint64_t* out, uint64_t* sizes, int32_t* status, int32_t* stored);
@@ -352,6 +352,35 @@ int oxh_chunk_digests_host_multi(oxh_ctx* const* ctxs, int nctx, const uint8_t* 
  * normalization level (fastcdc v2020 MASKS[bits +/- level], bits = round(log2(avg))). Host only. */
 int oxh_fastcdc_gear(uint64_t* out256);
 int oxh_fastcdc_masks(uint32_t avg_size, uint32_t level, uint64_t* mask_s, uint64_t* mask_l);
+
+/* ---------------------------------------------------------------- dedup index
+ * Which chunks are duplicates: the question the block-level dedup experiment answers through the file
+ * system, one stat or file creation per chunk (fixedsize.rs:78-89 `chunk_path.exists()`,
+ * fastcdchunker.rs:95-108 writes every chunk). The index is a hash table in device memory keyed by the
+ * 128-bit chunk digests, persistent across calls. Every inserted row has an ORDINAL: the number of rows
+ * inserted before its call plus its position in the call. For each row the index answers "which ordinal
+ * first carried this digest" -- a row is a first occurrence exactly when that is its own ordinal.
+ * The handle is opaque (like `stream`). The index uses `ctx`'s device and streams: destroy it before the
+ * context. Calls on one index serialise on its mutex and ordinals follow lock order, so every result is
+ * a pure function of the sequence of calls. The table grows as rows arrive (load kept at or below one
+ * half; memory is 16 B per row of keys plus 16-32 B per row of table); when a larger table or key store
+ * cannot be allocated the call returns OXH_ERR_NOMEM and the index is unchanged. n == 0 is OXH_OK and
+ * touches nothing. Without a gfx950 device, create fails with OXH_ERR_NODEVICE. */
+int oxh_dedup_index_create(oxh_ctx* ctx, uint64_t capacity_rows, void** out);   /* 0 = small default; grows */
+int oxh_dedup_index_destroy(void* index);
+/* Insert n digests (device: 2n u64, lo then hi; d_lens may be NULL). d_first (device, n u64, may be
+ * NULL) = smallest ordinal carrying the same digest, over everything inserted so far including this
+ * call. stats (host, 4 u64, may be NULL) = {new distinct rows, their bytes, duplicate rows, their bytes}.
+ * Blocks until complete. */
+int oxh_dedup_index_insert_device(void* index, const uint64_t* d_digests, const uint64_t* d_lens, uint64_t n,
+                                  uint64_t* d_first, uint64_t* stats, void* stream);
+int oxh_dedup_index_insert_host(void* index, const uint64_t* digests, const uint64_t* lens, uint64_t n,
+                                uint64_t* first, uint64_t* stats);
+/* Look up without inserting: first[i] = ordinal of the first row with that digest, or ~0 if absent. */
+int oxh_dedup_index_query_device(void* index, const uint64_t* d_digests, uint64_t n, uint64_t* d_first, void* stream);
+int oxh_dedup_index_query_host(void* index, const uint64_t* digests, uint64_t n, uint64_t* first);
+/* out4 = {rows, distinct digests, bytes, distinct bytes} over the index's lifetime. */
+int oxh_dedup_index_counts(void* index, uint64_t* out4);
 
 /* ---------------------------------------------------------------- K2: merkle parent nodes */
 /* get_combined_hash (hasher.rs:67-80) x n on the device:

@@ -7,7 +7,8 @@ Modules:
   hasher    -- mirror of liboxen `util::hasher` (same names / errors) plus batched forms
   merkle    -- MerkleHash and the commit-time parent-node streams (K2)
   version_store -- verify-before-publish writes (AtomicFile.with_hash, LocalVersionStore)
-  dedup     -- fixed-size and FastCDC chunking + chunk digests (block-level dedup)
+  dedup     -- fixed-size and FastCDC chunking + chunk digests (block-level dedup), and the
+               device-resident dedup index that says which chunks are duplicates (DedupIndex)
   procpool  -- file hashing sharded over reader processes (the open/close floor is per process)
   shard     -- multi-GPU sharding and the RCCL digest gather
   device    -- device-resident (HBM) batch entry points over torch buffers

@@ -16,7 +16,8 @@ LIB = os.path.join(HERE, "liboxen_hash.so")
 # the C ABI runtime (capi_internal.hpp lists its pieces), the kernels, FastCDC, the reader pool, RCCL
 SOURCES = [os.path.join(CSRC, f) for f in (
     "xxh3_kernels.hip", "capi_dispatch.hip", "capi_context.hip", "staging.hip", "large_items.hip", "xxh3_stream.hip",
-    "engine.hip", "modified.hip", "publish.hip", "fastcdc.hip", "reader_pool.cpp", "comm.cpp", "fastcdc_host.cpp")]
+    "engine.hip", "modified.hip", "publish.hip", "fastcdc.hip", "dedup_index.hip", "reader_pool.cpp", "comm.cpp",
+    "fastcdc_host.cpp")]
 DEPS = SOURCES + [os.path.join(CSRC, h) for h in ("capi_internal.hpp", "xxh3_device.hpp", "fastcdc_gear.h", "pool.hpp",
                                                  "scratch.hpp", "reader_pool.hpp", "env.hpp")] + [os.path.join(ROOT, "include", "oxen_hash.h")]
 HELPER_SRC = os.path.join(CSRC, "hash_helper.cpp")

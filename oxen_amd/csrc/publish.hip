@@ -175,7 +175,13 @@ class VersionPublisher final : public ItemSink {
     // Per-item outcome into the caller's arrays: a file whose content failed to publish (its own
     // publish or the one its duplicate claimed) fails with OXH_ERR_IO and digest 0, like the
     // reference's add of that file (add.rs:533-544).
+    // Which of several items of one content claimed it is a race between the readers that staged them
+    // and the threads that put them; the caller is told the same thing whichever won: stored = 1 on
+    // the first of those items (the one the serial direct path reports).
     void finish(uint64_t n, uint64_t* out, int32_t* status, int32_t* stored) const {
+        std::vector<uint64_t> first_of(n, kNone);  // by owner: the lowest item that shares its publish
+        for (uint64_t i = 0; i < n; ++i)
+            if (status[i] == OXH_OK && owner_[i] != kNone && first_of[owner_[i]] == kNone) first_of[owner_[i]] = i;
         for (uint64_t i = 0; i < n; ++i) {
             stored[i] = 0;
             if (status[i] != OXH_OK) continue;
@@ -185,7 +191,7 @@ class VersionPublisher final : public ItemSink {
                 out[2 * i] = out[2 * i + 1] = 0;
                 continue;
             }
-            stored[i] = (o == i && result_[o] == kWritten) ? 1 : 0;
+            stored[i] = (first_of[o] == i && result_[o] == kWritten) ? 1 : 0;
         }
     }
 

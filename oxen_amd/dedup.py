@@ -19,7 +19,7 @@ from __future__ import annotations
 import ctypes
 import os
 import struct
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -230,10 +230,12 @@ def fastcdc_host(buffers, min_size: int, avg_size: int, max_size: int, level: in
 class FixedChunkTable:
     """Fixed-size chunk digests in host memory (oxh_chunk_digests_files / _host): digests[k] = (lo, hi)
     of chunk k; file i's chunks are rows first[i] .. first[i+1]-1, chunk j of a file being its bytes
-    [j*chunk, min((j+1)*chunk, size)). sizes / status / os_error per file (files only)."""
+    [j*chunk, min((j+1)*chunk, size)). sizes per file; status / os_error per file (files only).
+    chunk_size is what the table was cut at (the chunk lengths follow from it and sizes)."""
 
-    def __init__(self, digests, first, sizes=None, status=None, os_error=None):
+    def __init__(self, digests, first, sizes=None, status=None, os_error=None, chunk_size=None):
         self.digests, self.first, self.sizes, self.status, self.os_error = digests, first, sizes, status, os_error
+        self.chunk_size = chunk_size
 
     def file(self, i: int):
         return self.digests[int(self.first[i]):int(self.first[i + 1])]
@@ -299,7 +301,7 @@ def chunk_digests_files(paths, chunk_size: int, ctx: Optional[_capi.Context] = N
                 raise
             cap = need
             continue
-        return FixedChunkTable(dig[:int(first[n])], first, sizes, status, oserr)
+        return FixedChunkTable(dig[:int(first[n])], first, sizes, status, oserr, chunk_size=int(chunk_size))
     raise _capi.OxenError("oxh_chunk_digests_files: the files keep growing", _capi.OXH_ERR_INVALID)
 
 
@@ -326,7 +328,187 @@ def chunk_digests_host(buffers, chunk_size: int, ctx: Optional[_capi.Context] = 
                     "oxh_chunk_digests_host_multi")
     else:
         _capi.check(_capi.lib().oxh_chunk_digests_host(ctx.handle, ptrs, *tail), "oxh_chunk_digests_host")
-    return FixedChunkTable(dig[:int(first[n])], first)
+    return FixedChunkTable(dig[:int(first[n])], first, sizes=lens_in, chunk_size=int(chunk_size))
+
+
+ABSENT = (1 << 64) - 1  # DedupIndex.query: no row carries this digest
+
+
+class DedupStats(NamedTuple):
+    """One insert: rows that brought a digest the index had not seen (and their bytes), rows that
+    repeated one (and theirs)."""
+    new_rows: int
+    new_bytes: int
+    dup_rows: int
+    dup_bytes: int
+
+
+class DedupCounts(NamedTuple):
+    """An index's lifetime: rows inserted, distinct digests among them, their bytes, distinct bytes."""
+    rows: int
+    distinct: int
+    bytes: int
+    distinct_bytes: int
+
+
+def _digest_rows(digests) -> np.ndarray:
+    a = np.ascontiguousarray(digests, dtype=np.uint64)
+    if a.ndim != 2 or a.shape[1] != 2:
+        if a.size == 0:
+            return a.reshape(0, 2)
+        raise _capi.OxenError("digests must be an (n, 2) uint64 array of (lo, hi) rows", _capi.OXH_ERR_INVALID)
+    return a
+
+
+class DedupIndex:
+    """oxh_dedup_index_*: a hash table in device memory keyed by 128-bit chunk digests, persistent
+    across calls. Every inserted row has an ordinal (rows inserted before its call + its position in
+    the call); `insert` returns, per row, the smallest ordinal that carries the same digest, so a row is
+    a first occurrence exactly when that is its own ordinal. Replaces the per-chunk
+    `chunk_path.exists()` of fixedsize.rs:78-89 and the write-everything of fastcdchunker.rs:95-108.
+    The index uses its context's device and streams: close it before the context."""
+
+    def __init__(self, ctx: Optional[_capi.Context] = None, capacity: int = 0):
+        from .hasher import default_context
+
+        self.handle = None
+        self.ctx = ctx or default_context()
+        h = ctypes.c_void_p()
+        _capi.check(_capi.lib().oxh_dedup_index_create(self.ctx.handle, int(capacity), ctypes.byref(h)),
+                    "oxh_dedup_index_create")
+        self.handle = h
+
+    def _live(self):
+        if not self.handle:
+            raise _capi.OxenError("the dedup index is closed", _capi.OXH_ERR_INVALID)
+        return self.handle
+
+    def insert(self, digests, lens=None):
+        """digests: (n, 2) uint64 rows of (lo, hi), as FastCdcTable.digests; lens: n chunk lengths or
+        None. Returns (first, stats): first[i] (numpy uint64) = the smallest ordinal with row i's
+        digest, over everything inserted so far including this call; stats a DedupStats."""
+        h = self._live()
+        dig = _digest_rows(digests)
+        n = dig.shape[0]
+        ln = None
+        if lens is not None:
+            ln = np.ascontiguousarray(lens, dtype=np.uint64)
+            if ln.shape != (n,):
+                raise _capi.OxenError("lens must hold one length per digest", _capi.OXH_ERR_INVALID)
+        first = np.zeros(n, dtype=np.uint64)
+        stats = np.zeros(4, dtype=np.uint64)
+        _capi.check(_capi.lib().oxh_dedup_index_insert_host(h, dig.ctypes.data_as(_capi._u64p),
+                                                            ln.ctypes.data_as(_capi._u64p) if ln is not None else None, n,
+                                                            first.ctypes.data_as(_capi._u64p),
+                                                            stats.ctypes.data_as(_capi._u64p)), "oxh_dedup_index_insert_host")
+        return first, DedupStats(*(int(v) for v in stats))
+
+    def insert_device(self, d_digests: torch.Tensor, d_lens: Optional[torch.Tensor] = None, stream=None):
+        """The same over device-resident tensors (digests (n, 2), 64-bit; lens n, 64-bit or None) on
+        `stream` (default: the current torch stream). Returns (first, stats), first an int64 device
+        tensor holding the raw u64 words. Blocks until complete."""
+        from .device import _require_cuda, _stream
+
+        h = self._live()
+        _require_cuda(d_digests, *([d_lens] if d_lens is not None else []))
+        if d_digests.element_size() != 8 or d_digests.numel() % 2 or not d_digests.is_contiguous():
+            raise _capi.OxenError("d_digests must be a contiguous 64-bit (n, 2) tensor", _capi.OXH_ERR_INVALID)
+        n = d_digests.numel() // 2
+        if d_lens is not None and (d_lens.element_size() != 8 or d_lens.numel() != n or not d_lens.is_contiguous()):
+            raise _capi.OxenError("d_lens must be a contiguous 64-bit tensor of one length per digest", _capi.OXH_ERR_INVALID)
+        first = torch.empty(n, dtype=torch.int64, device=d_digests.device)
+        stats = np.zeros(4, dtype=np.uint64)
+        _capi.check(_capi.lib().oxh_dedup_index_insert_device(h, d_digests.data_ptr(),
+                                                              d_lens.data_ptr() if d_lens is not None else None, n,
+                                                              first.data_ptr(), stats.ctypes.data_as(_capi._u64p),
+                                                              _stream(stream)), "oxh_dedup_index_insert_device")
+        return first, DedupStats(*(int(v) for v in stats))
+
+    def query(self, digests) -> np.ndarray:
+        """first[i] = the ordinal of the first row with that digest, or ABSENT; inserts nothing."""
+        h = self._live()
+        dig = _digest_rows(digests)
+        first = np.zeros(dig.shape[0], dtype=np.uint64)
+        _capi.check(_capi.lib().oxh_dedup_index_query_host(h, dig.ctypes.data_as(_capi._u64p), dig.shape[0],
+                                                           first.ctypes.data_as(_capi._u64p)), "oxh_dedup_index_query_host")
+        return first
+
+    def counts(self) -> DedupCounts:
+        out = np.zeros(4, dtype=np.uint64)
+        _capi.check(_capi.lib().oxh_dedup_index_counts(self._live(), out.ctypes.data_as(_capi._u64p)),
+                    "oxh_dedup_index_counts")
+        return DedupCounts(*(int(v) for v in out))
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            _capi.lib().oxh_dedup_index_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def _own_first(index, digests, lens) -> np.ndarray:
+    """Insert a table's rows; True for the rows that are their own first occurrence in the index."""
+    base = int(index.counts()[0])
+    first, _ = index.insert(digests, lens)
+    return np.asarray(first, dtype=np.uint64) == np.arange(base, base + len(first), dtype=np.uint64)
+
+
+def table_lens(table, chunk_size: Optional[int] = None) -> np.ndarray:
+    """Chunk lengths of a table's rows: a FastCdcTable carries them; a FixedChunkTable's follow from
+    its files' sizes and the chunk size (every chunk of a file is chunk_size long but the last)."""
+    if getattr(table, "lens", None) is not None:
+        return np.asarray(table.lens, dtype=np.uint64)
+    chunk = int(chunk_size or getattr(table, "chunk_size", None) or 0)
+    if chunk <= 0 or table.sizes is None:
+        raise _capi.OxenError("a fixed-size table needs its files' sizes and the chunk size", _capi.OXH_ERR_INVALID)
+    first = np.asarray(table.first, dtype=np.int64)
+    lens = np.full(int(first[-1]), chunk, dtype=np.uint64)
+    for i, size in enumerate(np.asarray(table.sizes, dtype=np.uint64).tolist()):
+        a, b = int(first[i]), int(first[i + 1])
+        if b > a:
+            if (size + chunk - 1) // chunk != b - a:
+                raise _capi.OxenError(f"file {i}: {b - a} chunks do not cover {size} bytes at {chunk}", _capi.OXH_ERR_INVALID)
+            lens[b - 1] = size - (b - a - 1) * chunk
+    return lens
+
+
+def dedup_report(table, index=None, chunk_size: Optional[int] = None) -> dict:
+    """The dedup ratio of a chunk table (FastCdcTable / FixedChunkTable): its rows go into `index` (a
+    fresh DedupIndex when None) in table order, and a chunk counts as distinct where it is its own
+    first occurrence -- so with an index that already holds rows, "distinct" means new to the index,
+    and a file's distinct chunks are those no earlier file (or row) carried. Returns
+    {"chunks", "distinct_chunks", "bytes", "distinct_bytes", "ratio", "files": [the same per file]};
+    ratio = distinct_bytes / bytes (1.0 for no bytes)."""
+    lens = table_lens(table, chunk_size)
+    own = index is None
+    index = DedupIndex() if own else index
+    try:
+        is_first = _own_first(index, table.digests, lens)
+    finally:
+        if own:
+            index.close()
+
+    def row(a: int, b: int) -> dict:
+        total = int(lens[a:b].sum(dtype=np.uint64))
+        distinct = int(lens[a:b][is_first[a:b]].sum(dtype=np.uint64))
+        return {"chunks": b - a, "distinct_chunks": int(is_first[a:b].sum()), "bytes": total, "distinct_bytes": distinct,
+                "ratio": distinct / total if total else 1.0}
+
+    first = np.asarray(table.first, dtype=np.int64)
+    out = row(0, len(lens))
+    out["files"] = [row(int(first[i]), int(first[i + 1])) for i in range(len(first) - 1)]
+    return out
 
 
 # fixedsize.rs:67-91 reads through `BufReader::new(File)` (8 KiB buffer) and stops at the first read
@@ -369,10 +551,13 @@ class FastCDChunker:
                                               self.max_chunk_size)
         return to_numpy_u64(c_off), to_numpy_u64(c_len), to_numpy_u64(dig).reshape(-1, 2)
 
-    def pack(self, input_file: str, output_dir: str, ctx: Optional[_capi.Context] = None) -> str:
+    def pack(self, input_file: str, output_dir: str, ctx: Optional[_capi.Context] = None, index=None) -> str:
         """fastcdchunker.rs:72-122. The library reads the file (oxh_fastcdc_files: its bytes stream to
         the device once; boundaries and chunk digests come back to host memory); the chunk files are
-        then written from a read-only map of the input, as the reference writes its slices."""
+        then written from a read-only map of the input, as the reference writes its slices.
+        index (a DedupIndex that belongs to this output_dir: every row ever inserted into it is a chunk
+        file there): the table is inserted and only the rows that are their own first occurrence are
+        written -- the directory ends up the same, without the rewrites of repeated chunks."""
         import errno as _errno
         import mmap
 
@@ -383,12 +568,15 @@ class FastCDChunker:
             raise OSError(e, os.strerror(e), input_file)
         size = os.stat(input_file).st_size  # input_file.metadata()?.len() (:77-78)
         names = []
+        wanted = _own_first(index, tab.digests, tab.lens).tolist() if index is not None else None
         with open(input_file, "rb") as fh:
             content = mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ) if size else b""
             try:
-                for o, l, (lo, hi) in zip(tab.offsets, tab.lens, tab.digests):
+                for k, (o, l, (lo, hi)) in enumerate(zip(tab.offsets, tab.lens, tab.digests)):
                     name = chunk_name(lo, hi)
                     names.append(name)
+                    if wanted is not None and not wanted[k]:
+                        continue
                     with open(os.path.join(output_dir, name), "wb") as out:
                         out.write(content[int(o):int(o) + int(l)])
             finally:
@@ -435,11 +623,14 @@ class _FixedSizeBase:
         """Bytes of the file the reference chunks (all of them; FixedSizeChunker overrides)."""
         return size
 
-    def chunk_file(self, path: str, output_dir: str) -> list[str]:
+    def chunk_file(self, path: str, output_dir: str, index=None) -> list[str]:
         """Decimal xxh3_128 names of the file's chunks; a chunk file is written unless one of that
         name exists (fixedsize.rs:78-89, fixedsize_multithreaded.rs:95-105). The library reads the file
         and returns the digests (oxh_chunk_digests_files); the chunk files are written from a read-only
-        map of it by `concurrency` threads."""
+        map of it by `concurrency` threads.
+        index (a DedupIndex that belongs to this output_dir: every row ever inserted into it is a chunk
+        file there): the digests are inserted and only the rows that are their own first occurrence
+        are looked at; the others cost no `exists` call."""
         import errno as _errno
         import mmap
         from concurrent.futures import ThreadPoolExecutor
@@ -460,6 +651,11 @@ class _FixedSizeBase:
         names = [chunk_name(lo, hi) for lo, hi in dig.tolist()]
         if not names:
             return names
+        rows = range(len(names))
+        if index is not None:
+            starts = np.arange(len(names), dtype=np.uint64) * np.uint64(self.chunk_size)
+            lens = np.minimum(starts + np.uint64(self.chunk_size), np.uint64(pre)) - starts
+            rows = np.nonzero(_own_first(index, dig, lens))[0].tolist()
         with open(path, "rb") as fh:
             content = mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ)
             try:
@@ -471,7 +667,7 @@ class _FixedSizeBase:
                             out.write(content[lo:min(pre, lo + self.chunk_size)])
 
                 with ThreadPoolExecutor(self.concurrency) as ex:
-                    list(ex.map(write, range(len(names))))
+                    list(ex.map(write, rows))
             finally:
                 content.close()
         return names
@@ -490,28 +686,29 @@ class FixedSizeChunker(_FixedSizeBase):
     def _prefix(self, size: int) -> int:
         return bufreader_prefix(size, self.chunk_size)
 
-    def _file_entry(self, path: str, base: str, output_dir: str) -> dict:
-        chunks = self.chunk_file(path, output_dir)
+    def _file_entry(self, path: str, base: str, output_dir: str, index=None) -> dict:
+        chunks = self.chunk_file(path, output_dir, index)
         return {"path": os.path.relpath(path, base), "is_dir": False, "chunks": chunks, "size": os.stat(path).st_size}
 
-    def _walk(self, cur: str, base: str, output_dir: str, entries: list) -> None:
+    def _walk(self, cur: str, base: str, output_dir: str, entries: list, index=None) -> None:
         with os.scandir(cur) as it:  # read_dir order (fixedsize.rs:116)
             for e in it:
                 if e.is_dir():  # metadata() follows symlinks, as here
                     entries.append({"path": os.path.relpath(e.path, base), "is_dir": True, "chunks": None, "size": None})
-                    self._walk(e.path, base, output_dir, entries)
+                    self._walk(e.path, base, output_dir, entries, index)
                 elif e.is_file():
-                    entries.append(self._file_entry(e.path, base, output_dir))
+                    entries.append(self._file_entry(e.path, base, output_dir, index))
 
-    def pack(self, input_path: str, output_dir: str) -> str:
+    def pack(self, input_path: str, output_dir: str, index=None) -> str:
+        """index: a DedupIndex that belongs to output_dir (chunk_file)."""
         os.makedirs(output_dir, exist_ok=True)
         entries: list = []
         if os.path.isfile(input_path):
             base = os.path.dirname(os.path.abspath(input_path))
-            entries.append(self._file_entry(os.path.abspath(input_path), base, output_dir))
+            entries.append(self._file_entry(os.path.abspath(input_path), base, output_dir, index))
         elif os.path.isdir(input_path):
             entries.append({"path": ".", "is_dir": True, "chunks": None, "size": None})
-            self._walk(input_path, input_path, output_dir, entries)
+            self._walk(input_path, input_path, output_dir, entries, index)
         else:
             raise _capi.OxenError("Input path must be a file or a directory", _capi.OXH_ERR_INVALID)
         with open(os.path.join(output_dir, METADATA_FILE_NAME), "wb") as f:
@@ -548,13 +745,14 @@ class FixedSizeMultiChunker(_FixedSizeBase):
     def name(self) -> str:
         return "fixed-size-64k-multithreaded"
 
-    def pack(self, input_file: str, output_dir: str) -> str:
+    def pack(self, input_file: str, output_dir: str, index=None) -> str:
+        """index: a DedupIndex that belongs to output_dir (chunk_file)."""
         os.makedirs(output_dir, exist_ok=True)
         try:
             size = os.stat(input_file).st_size
         except OSError as e:
             raise FileNotFoundError(f"Failed to read input file metadata '{input_file}': {e}") from e
-        names = self.chunk_file(input_file, output_dir) if size else []
+        names = self.chunk_file(input_file, output_dir, index) if size else []
         base = os.path.basename(os.path.normpath(input_file)) or "unknown_file"
         with open(os.path.join(output_dir, METADATA_FILE_NAME), "wb") as f:
             f.write(encode_fixed_metadata(base, size, self.chunk_size, names))
