@@ -139,27 +139,39 @@ def _pack(files, align_pad=3):
     return arena, np.array(offs, dtype=np.uint64), np.array([len(f) for f in files], dtype=np.uint64)
 
 
-def _check(cuda, oracle_lib, files, mn, av, mx, level=1):
+def _check_items(cuda, oracle_lib, arena, offs, lens, mn, av, mx, level=1, explain=None):
+    """fastcdc_device over the items arena[offs[i] : offs[i] + lens[i]] (they may overlap): every item's
+    chunk table against F.chunks of its bytes, every digest against the oracle's. explain(i, want,
+    got_off, got_len) -> str names a mismatch (the planted lattices: the class of the first wrong chunk)."""
     import torch
 
     from oxen_amd.device import fastcdc_device, to_numpy_u64
 
-    arena, offs, lens = _pack(files)
     d_arena = torch.from_numpy(arena).to(cuda)
     c_off, c_len, dig, first = fastcdc_device(d_arena, offs, lens, mn, av, mx, level)
     got_off, got_len = to_numpy_u64(c_off), to_numpy_u64(c_len)
     got_dig = to_numpy_u64(dig).reshape(-1, 2) if dig.numel() else np.zeros((0, 2), np.uint64)
-    assert first[0] == 0 and len(first) == len(files) + 1
-    for i, f in enumerate(files):
-        want = F.chunks(f, mn, av, mx, level)
+    assert first[0] == 0 and len(first) == len(offs) + 1
+    for i in range(len(offs)):
+        n = int(lens[i])
+        want = F.chunks(arena[int(offs[i]):int(offs[i]) + n], mn, av, mx, level)
         a, b = int(first[i]), int(first[i + 1])
-        assert b - a == len(want), (i, len(f), b - a, len(want))
-        assert np.array_equal(got_off[a:b] - offs[i], want[:, 0]), (i, len(f))
-        assert np.array_equal(got_len[a:b], want[:, 1]), (i, len(f))
+        go, gl = got_off[a:b] - offs[i], got_len[a:b]
+        if explain is not None and not (b - a == len(want) and np.array_equal(go, want[:, 0]) and
+                                        np.array_equal(gl, want[:, 1])):
+            pytest.fail(explain(i, want, go, gl))
+        assert b - a == len(want), (i, n, b - a, len(want))
+        assert np.array_equal(go, want[:, 0]), (i, n)
+        assert np.array_equal(gl, want[:, 1]), (i, n)
     if len(got_off):
         want_dig = oracle_lib.batch(arena, got_off, got_len, threads=8)
         assert np.array_equal(got_dig, want_dig)
     return int(first[-1])
+
+
+def _check(cuda, oracle_lib, files, mn, av, mx, level=1):
+    arena, offs, lens = _pack(files)
+    return _check_items(cuda, oracle_lib, arena, offs, lens, mn, av, mx, level)
 
 
 @pytest.mark.gpu
@@ -427,13 +439,14 @@ def _check_table(oracle_lib, tab, datas, mn, av, mx, level=1):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("piece_mib", [None, "32"], ids=["1GiB-pieces", "32MiB-pieces"])
+@pytest.mark.parametrize("piece_mib", [None, "32"], ids=["1GiB-pieces", "64MiB-pieces"])
 @pytest.mark.parametrize("cfg", [CONFIGS[0], CONFIGS[1], CONFIGS[3], CONFIGS[4]], ids=lambda c: "-".join(map(str, c)))
 def test_fastcdc_files_ragged(cuda, oracle_lib, tmp_path, monkeypatch, cfg, piece_mib):
     """oxh_fastcdc_files (the reference's fs::read -> chunk -> xxh3 per chunk, fastcdchunker.rs:75-98,
     starting and ending in host memory): empty, 1 B, < min, == min, odd tails, files that cross the
-    piece boundary and (with 32 MiB pieces) files cut into many segments whose carries must land on
-    the crate's boundaries. Every boundary and digest equals the oracle's."""
+    piece boundary and (with OXH_CDC_PIECE_MIB=32, which the planner rounds up to one 64 MiB bounce
+    window: 64 MiB pieces) files cut into two segments whose carries must land on the crate's
+    boundaries. Every boundary and digest equals the oracle's."""
     from oxen_amd import dedup
 
     if piece_mib:
