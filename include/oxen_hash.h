@@ -382,6 +382,30 @@ int oxh_dedup_index_query_host(void* index, const uint64_t* digests, uint64_t n,
 /* out4 = {rows, distinct digests, bytes, distinct bytes} over the index's lifetime. */
 int oxh_dedup_index_counts(void* index, uint64_t* out4);
 
+/* ---------------------------------------------------------------- chunk overlap between file versions
+ * How many chunks of one version of a file another version also holds: what the experiment's TestOxen
+ * command asks of the n latest commits (chunker/oxendedup.rs:72-209, `OxenChunker::pack`), pair by pair
+ * through `count_commit_overlap` (:56-70) -- for every hash of commit 1, with multiplicity, a
+ * `Vec<String>::contains` scan of commit 2. Here all sets are counted against all in one call.
+ * N = set_first[nsets] rows of (lo, hi) digests, set k = rows [set_first[k], set_first[k+1]); set_first
+ * (nsets + 1 entries, set_first[0] = 0, non-decreasing), rows_out and bytes_out are HOST arrays in both
+ * forms. rows_out[a * nsets + b] = the rows of set a, with multiplicity, whose digest occurs at least once
+ * in set b: the diagonal is set a's row count, `count_commit_overlap(c1, c2)` is entry [c1][c2], and the
+ * matrix is not symmetric when a set repeats a digest. bytes_out (may be NULL; needs the lengths) = the
+ * same sum over the rows' lengths. Blocks until complete. The call keeps nothing: it builds a table of
+ * its own on the device and frees it, and touches no oxh_dedup_index_* handle of the context.
+ * OXH_ERR_INVALID: NULL set_first / rows_out, nsets 0 or above OXH_CHUNK_OVERLAP_MAX_SETS, a set_first
+ * that does not start at 0 or decreases, N > 2^40, NULL digests with N > 0, bytes_out without lengths --
+ * all before OXH_ERR_NODEVICE (there is no CPU path), then a NULL ctx. N == 0: OXH_OK, zeroed outputs.
+ * A failed device allocation is OXH_ERR_NOMEM with the outputs untouched (memory: 40-56 B per row, 8 more
+ * in the host form with lengths, plus 8 * ceil(nsets / 64) B per row of set masks). */
+#define OXH_CHUNK_OVERLAP_MAX_SETS 256   /* TestOxen's n_commits is a u8 */
+int oxh_chunk_overlap_device(oxh_ctx* ctx, const uint64_t* d_digests, const uint64_t* d_lens,
+                             const uint64_t* set_first, uint64_t nsets, uint64_t* rows_out, uint64_t* bytes_out,
+                             void* stream);
+int oxh_chunk_overlap_host(oxh_ctx* ctx, const uint64_t* digests, const uint64_t* lens, const uint64_t* set_first,
+                           uint64_t nsets, uint64_t* rows_out, uint64_t* bytes_out);
+
 /* ---------------------------------------------------------------- K2: merkle parent nodes */
 /* get_combined_hash (hasher.rs:67-80) x n on the device:
  * XXH3-128(content.to_le_bytes() || metadata.to_le_bytes()), inputs as (lo, hi) pairs. */

@@ -8,7 +8,8 @@ Modules:
   merkle    -- MerkleHash and the commit-time parent-node streams (K2)
   version_store -- verify-before-publish writes (AtomicFile.with_hash, LocalVersionStore)
   dedup     -- fixed-size and FastCDC chunking + chunk digests (block-level dedup), and the
-               device-resident dedup index that says which chunks are duplicates (DedupIndex)
+               device-resident dedup index that says which chunks are duplicates (DedupIndex);
+               chunk overlap between the versions of a file (chunk_overlap, OxenChunker)
   procpool  -- file hashing sharded over reader processes (the open/close floor is per process)
   shard     -- multi-GPU sharding and the RCCL digest gather
   device    -- device-resident (HBM) batch entry points over torch buffers
@@ -18,3 +19,15 @@ Modules:
 from ._capi import OxenError  # noqa: F401
 
 __version__ = "0.1.0"
+
+# re-exported from oxen_amd.dedup on first use (that module imports torch; `import oxen_amd` does not)
+_FROM_DEDUP = ("ChunkOverlap", "chunk_overlap", "chunk_overlap_device", "names_to_digests", "count_commit_overlap",
+               "OxenChunker")
+
+
+def __getattr__(name):
+    if name in _FROM_DEDUP:
+        from . import dedup
+
+        return getattr(dedup, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

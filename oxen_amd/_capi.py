@@ -111,6 +111,8 @@ SIGNATURES = {
     "oxh_dedup_index_query_device": (_int, [_vp, _vp, _u64, _vp, _vp]),
     "oxh_dedup_index_query_host": (_int, [_vp, _u64p, _u64, _u64p]),
     "oxh_dedup_index_counts": (_int, [_vp, _u64p]),
+    "oxh_chunk_overlap_device": (_int, [_vp, _vp, _vp, _u64p, _u64, _u64p, _u64p, _vp]),
+    "oxh_chunk_overlap_host": (_int, [_vp, _u64p, _u64p, _u64p, _u64, _u64p, _u64p]),
     "oxh_comm_check": (_int, [_int]),
     "oxh_ctx_counters": (_int, [_vp, _u64p, _int]),
     "oxh_comm_unique_id": (_int, [ctypes.c_char_p]),

@@ -11,7 +11,8 @@
 //   engine.hip         the streaming file engine behind every file call (oxh_hash_files*)
 //   modified.hip       util::fs modified checks over one engine request (oxh_files_modified*)
 //   publish.hip        the fused add's version-store publisher and the fsck (oxh_add_files*, clean)
-//   dedup_index.hip    the device-resident dedup index: its kernels and entries (oxh_dedup_index_*)
+//   dedup_index.hip    the device-resident dedup index: its kernels and entries (oxh_dedup_index_*), and
+//                      the chunk overlap between sets of digests built on it (oxh_chunk_overlap_*)
 // There is no CPU hashing path: every digest this library returns was computed on the GPU.
 #pragma once
 

@@ -19,6 +19,10 @@
 // ordinal of an equal key), so there is nothing to publish and nothing to spin on. Probe loops are
 // bounded by the slot count and by the ordinals the table may hold; a lane that runs out sets the
 // error word, which the host turns into OXH_ERR_HIP. The host keeps the load at or below one half.
+//
+// oxh_chunk_overlap_* (how many chunks the versions of a file share, oxendedup.rs:56-70) are here too:
+// one insert into a private index gives every digest an id, and two more kernels mark which sets hold
+// each id and count the shared rows and bytes of every pair of sets (see at overlap_mark_kernel).
 #include "capi_internal.hpp"
 
 using namespace oxh::capi;
@@ -142,6 +146,105 @@ __global__ __launch_bounds__(256) void dedup_resolve_kernel(const uint64_t* __re
             if (sum) atomicAdd(&stats[threadIdx.x], sum);
         }
     }
+}
+
+// ---------------------------------------------------------------- chunk overlap between sets (oxh_chunk_overlap_*)
+// The rows are cut into contiguous sets (the chunk tables of a file's versions); first[] of one insert of
+// all of them gives every digest an id, the smallest ordinal that carries it. member[id * W + s / 64]
+// bit s % 64 = "set s holds this digest" (mark); a later launch (count), so every OR has landed, reads
+// the W words of each row's id and adds the row, and its length, to (its set, every set bit). Both
+// launch on a (workgroups, nsets) grid: a workgroup works on `chunk` contiguous rows of ONE set, the
+// set being blockIdx.y, and leaves at once when its set has no such rows. No lane waits for another.
+constexpr unsigned long long kErrFirst = 8, kErrSetBit = 16;
+constexpr uint32_t kOverlapMaxSets = OXH_CHUNK_OVERLAP_MAX_SETS;
+
+__global__ __launch_bounds__(256) void overlap_mark_kernel(const uint64_t* __restrict__ first,
+                                                           const uint64_t* __restrict__ set_first, uint32_t words, uint64_t n,
+                                                           uint64_t chunk, unsigned long long* __restrict__ member,
+                                                           unsigned long long* __restrict__ err) {
+    const uint32_t s = blockIdx.y;
+    const uint64_t lo = set_first[s], rows = set_first[s + 1] - lo, off = (uint64_t)blockIdx.x * chunk;
+    if (off >= rows) return;  // the whole workgroup
+    const uint64_t end = lo + (rows - off < chunk ? rows : off + chunk);
+    const unsigned long long bit = 1ull << (s & 63);
+    for (uint64_t at = lo + off; at < end; at += 256) {  // uniform over the workgroup: every lane reaches the shuffle
+        const uint64_t i = at + threadIdx.x;
+        const bool live = i < end;
+        const uint64_t f = live ? first[i] : kDedupEmpty;
+        // hints, as in the insert: a lane whose id is that of its wave neighbour (same set: the workgroup
+        // has one) has nothing to add, and a bit seen set stays set. The OR decides.
+        const uint64_t f_before = (uint64_t)__shfl_up((long long)f, 1, 64);
+        if (!live || ((threadIdx.x & 63) != 0 && f_before == f)) continue;
+        if (f >= n) {  // not an ordinal of this call: never index the membership array with it
+            __hip_atomic_fetch_or(err, kErrFirst, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            continue;
+        }
+        unsigned long long* p = &member[f * words + (s >> 6)];
+        if (!(slot_load(p) & bit)) __hip_atomic_fetch_or(p, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// matrix[a * nsets + b] += rows of set a whose digest set b holds; matrix[nsets^2 + ...] += their lengths.
+// Every row of a workgroup belongs to set a and neighbouring rows are mostly in the same sets (bit a at the
+// least), so the sums are taken per wave and distinct membership word -- a ballot for the rows, a shuffle
+// sum for the lengths -- and added to the workgroup's 2 x nsets counters in LDS; at the end each non-zero
+// counter costs one global atomic. Integer sums: exact, order-free.
+__global__ __launch_bounds__(256) void overlap_count_kernel(const uint64_t* __restrict__ first, const uint64_t* __restrict__ lens,
+                                                            const uint64_t* __restrict__ set_first, uint32_t nsets, uint32_t words,
+                                                            uint64_t n, uint64_t chunk,
+                                                            const unsigned long long* __restrict__ member,
+                                                            unsigned long long* __restrict__ matrix,
+                                                            unsigned long long* __restrict__ err) {
+    __shared__ unsigned long long cnt[2 * kOverlapMaxSets];
+    const uint32_t a = blockIdx.y;
+    const uint64_t lo = set_first[a], rows = set_first[a + 1] - lo, off = (uint64_t)blockIdx.x * chunk;
+    if (off >= rows) return;  // the whole workgroup, before any barrier
+    const uint64_t end = lo + (rows - off < chunk ? rows : off + chunk);
+    for (uint32_t k = threadIdx.x; k < 2 * nsets; k += 256) cnt[k] = 0;
+    __syncthreads();
+    const unsigned lane = threadIdx.x & 63;
+    for (uint64_t at = lo + off; at < end; at += 256) {  // uniform over the workgroup
+        const uint64_t i = at + threadIdx.x;
+        bool live = i < end;
+        const uint64_t f = live ? first[i] : 0;
+        const uint64_t len = live && lens ? lens[i] : 0;
+        if (live && f >= n) {
+            __hip_atomic_fetch_or(err, kErrFirst, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            live = false;
+        }
+        for (uint32_t w = 0; w < words; ++w) {
+            unsigned long long m = live ? member[f * words + w] : 0;
+            // each turn takes the word of the first lane that still holds one and serves every lane with that
+            // same word: at most 64 turns, and one where a wave's rows are in the same sets. Lane j then adds
+            // the turn's rows and bytes for bit j, so the adds of a turn go to different counters.
+            for (int turn = 0; turn < 64; ++turn) {
+                const unsigned long long pending = __ballot(m != 0);
+                if (!pending) break;  // uniform over the wave
+                const unsigned long long theirs = (unsigned long long)__shfl((long long)m, __builtin_ctzll(pending), 64);
+                const bool same = m == theirs;  // theirs is not 0
+                const unsigned long long who = __ballot(same);
+                unsigned long long bytes = same ? len : 0;
+                if (lens) {
+#pragma unroll
+                    for (int o = 1; o < 64; o <<= 1) bytes += (unsigned long long)__shfl_xor((long long)bytes, o, 64);
+                }
+                if (same) m = 0;
+                if ((theirs >> lane) & 1) {
+                    const uint32_t set_b = w * 64 + lane;
+                    if (set_b >= nsets) {  // no set of this call: never index the counters with it
+                        __hip_atomic_fetch_or(err, kErrSetBit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    } else {
+                        atomicAdd(&cnt[set_b], (unsigned long long)__popcll(who));
+                        if (bytes) atomicAdd(&cnt[nsets + set_b], bytes);
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    const uint64_t cells = (uint64_t)nsets * nsets;
+    for (uint32_t k = threadIdx.x; k < 2 * nsets; k += 256)
+        if (cnt[k]) atomicAdd(&matrix[(k < nsets ? 0 : cells - nsets) + (uint64_t)a * nsets + k], cnt[k]);
 }
 
 }  // namespace oxh
@@ -328,6 +431,111 @@ int piece_buffers(DedupIndex* ix) {
     return OXH_OK;
 }
 
+// ---------------------------------------------------------------- chunk overlap
+// What both forms check before they need a device (the order oxh_dedup_index_create keeps).
+int overlap_arguments(const uint64_t* digests, const uint64_t* lens, const uint64_t* set_first, uint64_t nsets,
+                      const uint64_t* rows_out, const uint64_t* bytes_out) {
+    if (!set_first || !rows_out) return fail(OXH_ERR_INVALID, "chunk overlap: set_first or rows_out is NULL");
+    if (nsets == 0 || nsets > OXH_CHUNK_OVERLAP_MAX_SETS)
+        return fail(OXH_ERR_INVALID, "chunk overlap: nsets must be 1.." + std::to_string(OXH_CHUNK_OVERLAP_MAX_SETS));
+    if (set_first[0] != 0) return fail(OXH_ERR_INVALID, "chunk overlap: set_first[0] is not 0");
+    for (uint64_t k = 0; k < nsets; ++k)
+        if (set_first[k + 1] < set_first[k]) return fail(OXH_ERR_INVALID, "chunk overlap: set_first decreases at set " + std::to_string(k));
+    if (set_first[nsets] > kMaxRows) return fail(OXH_ERR_INVALID, "chunk overlap: more than 2^40 rows");
+    if (!digests && set_first[nsets]) return fail(OXH_ERR_INVALID, "chunk overlap: digests is NULL");
+    if (bytes_out && !lens) return fail(OXH_ERR_INVALID, "chunk overlap: bytes_out needs the rows' lengths");
+    return OXH_OK;
+}
+
+// One call's temporaries, all made before any work starts: a private index sized for the rows (so its one
+// insert neither grows nor allocates), and one device block
+//   [first n | lens n (host form with lengths) | member n*words | matrix 2*nsets^2 | error word | set_first nsets+1]
+// with the pinned words the last three cross the link in. Freed once the stream has drained.
+struct Overlap {
+    DedupIndex* ix = nullptr;
+    uint64_t n = 0, nsets = 0, words = 0, cells = 0;
+    uint64_t* d_block = nullptr;
+    uint64_t *d_first = nullptr, *d_lens = nullptr, *d_sets = nullptr;
+    unsigned long long *d_member = nullptr, *d_matrix = nullptr;  // the error word follows the matrix
+    uint64_t* h_block = nullptr;  // [matrix 2*nsets^2 | error word | set_first nsets+1]
+
+    int make(oxh_ctx* ctx, const uint64_t* set_first, uint64_t nsets_, bool own_lens) {
+        nsets = nsets_;
+        n = set_first[nsets];
+        words = (nsets + 63) / 64;
+        cells = nsets * nsets;
+        void* handle = nullptr;
+        int rc = oxh_dedup_index_create(ctx, n, &handle);
+        if (rc) return rc;
+        ix = as_index(handle);
+        const uint64_t tail = 2 * cells + 1 + nsets + 1;
+        if (hipMalloc(&d_block, (n * (1 + (own_lens ? 1 : 0) + words) + tail) * 8) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(OXH_ERR_NOMEM, "chunk overlap: " + std::to_string(n) + " rows of first ordinals and set masks");
+        }
+        if (hipHostMalloc(&h_block, tail * 8, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(OXH_ERR_NOMEM, "chunk overlap: pinned result");
+        }
+        d_first = d_block;
+        d_lens = own_lens ? d_first + n : nullptr;
+        d_member = (unsigned long long*)(d_first + n * (own_lens ? 2 : 1));
+        d_matrix = d_member + n * words;
+        d_sets = (uint64_t*)(d_matrix + 2 * cells + 1);
+        memcpy(h_block + 2 * cells + 1, set_first, (nsets + 1) * 8);
+        return OXH_OK;
+    }
+
+    // mark and count over first[] on `st`, then the matrices to the caller; complete on return
+    int run(const uint64_t* lens_on_device, uint64_t* rows_out, uint64_t* bytes_out, hipStream_t st) {
+        HIP_TRY(hipMemsetAsync(d_member, 0, (n * words + 2 * cells + 1) * 8, st));
+        HIP_TRY(hipMemcpyAsync(d_sets, h_block + 2 * cells + 1, (nsets + 1) * 8, hipMemcpyHostToDevice, st));
+        // at most 2 048 workgroups have rows (as the resolve's grid), each `chunk` contiguous rows of one set
+        const uint64_t chunk = std::max<uint64_t>(256, ((n + 2047) / 2048 + 255) / 256 * 256);
+        uint64_t longest = 1;
+        for (uint64_t k = 0; k < nsets; ++k) longest = std::max(longest, h_block[2 * cells + 2 + k] - h_block[2 * cells + 1 + k]);
+        const dim3 grid((unsigned)((longest + chunk - 1) / chunk), (unsigned)nsets);
+        oxh::overlap_mark_kernel<<<grid, 256, 0, st>>>(d_first, d_sets, (uint32_t)words, n, chunk, d_member, d_matrix + 2 * cells);
+        HIP_TRY(hipGetLastError());
+        oxh::overlap_count_kernel<<<grid, 256, 0, st>>>(d_first, bytes_out ? lens_on_device : nullptr, d_sets, (uint32_t)nsets,
+                                                       (uint32_t)words, n, chunk, d_member, d_matrix, d_matrix + 2 * cells);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(h_block, d_matrix, (2 * cells + 1) * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (const uint64_t e = h_block[2 * cells]) {
+            std::string m = "oxh_chunk_overlap: ";
+            if (e & oxh::kErrFirst) m += "a first ordinal is not below the row count; ";
+            if (e & oxh::kErrSetBit) m += "a membership word holds a bit of no set; ";
+            return fail(OXH_ERR_HIP, m + "no result");
+        }
+        memcpy(rows_out, h_block, cells * 8);
+        if (bytes_out) memcpy(bytes_out, h_block + cells, cells * 8);
+        return OXH_OK;
+    }
+
+    void release(hipStream_t st, bool failed) {
+        if (failed && ix) (void)hipStreamSynchronize(st);  // work of a failed call may still be queued
+        if (d_block) (void)hipFree(d_block);
+        if (h_block) (void)hipHostFree(h_block);
+        if (ix) (void)oxh_dedup_index_destroy(ix);
+    }
+};
+
+int overlap_enter(oxh_ctx* ctx, const uint64_t* set_first, uint64_t nsets, uint64_t* rows_out, uint64_t* bytes_out, bool& done) {
+    done = false;
+    int rc = check_device(ctx ? ctx->device : 0);  // there is no CPU path
+    if (rc) return rc;
+    if (!ctx) return fail(OXH_ERR_INVALID, "ctx is NULL");
+    if (set_first[nsets] == 0) {
+        memset(rows_out, 0, nsets * nsets * 8);
+        if (bytes_out) memset(bytes_out, 0, nsets * nsets * 8);
+        done = true;
+        return OXH_OK;
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    return OXH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -465,6 +673,53 @@ int oxh_dedup_index_counts(void* index, uint64_t* out4) {
     std::lock_guard<std::mutex> g(ix->mu);
     for (int k = 0; k < 4; ++k) out4[k] = ix->life[k];
     return OXH_OK;
+}
+
+int oxh_chunk_overlap_device(oxh_ctx* ctx, const uint64_t* d_digests, const uint64_t* d_lens, const uint64_t* set_first,
+                             uint64_t nsets, uint64_t* rows_out, uint64_t* bytes_out, void* stream) {
+    int rc = overlap_arguments(d_digests, d_lens, set_first, nsets, rows_out, bytes_out);
+    if (rc) return rc;
+    bool done = false;
+    if ((rc = overlap_enter(ctx, set_first, nsets, rows_out, bytes_out, done)) || done) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    Overlap ov;
+    rc = ov.make(ctx, set_first, nsets, false);
+    if (rc == OXH_OK) rc = insert_rows(ov.ix, d_digests, hipMemcpyDeviceToDevice, nullptr, ov.n, ov.n, ov.d_first, nullptr, st);
+    if (rc == OXH_OK) rc = ov.run(d_lens, rows_out, bytes_out, st);
+    ov.release(st, rc != OXH_OK);
+    return rc;
+}
+
+int oxh_chunk_overlap_host(oxh_ctx* ctx, const uint64_t* digests, const uint64_t* lens, const uint64_t* set_first,
+                           uint64_t nsets, uint64_t* rows_out, uint64_t* bytes_out) {
+    int rc = overlap_arguments(digests, lens, set_first, nsets, rows_out, bytes_out);
+    if (rc) return rc;
+    bool done = false;
+    if ((rc = overlap_enter(ctx, set_first, nsets, rows_out, bytes_out, done)) || done) return rc;
+    hipStream_t st = ctx->stream;
+    const bool with_lens = lens && bytes_out;
+    Overlap ov;
+    rc = ov.make(ctx, set_first, nsets, with_lens);
+    if (rc == OXH_OK) rc = piece_buffers(ov.ix);
+    if (rc == OXH_OK)
+        rc = [&]() -> int {
+            uint64_t *h_dig = ov.ix->h_piece, *h_len = h_dig + 2 * kPieceRows;
+            // pieces in order give the first[] of one insert of all the rows (oxh_dedup_index_insert_host);
+            // the first piece makes room for the whole call, which the index already has
+            for (uint64_t at = 0; at < ov.n; at += kPieceRows) {
+                const uint64_t m = std::min(kPieceRows, ov.n - at);
+                memcpy(h_dig, digests + 2 * at, m * 16);
+                if (with_lens) {
+                    memcpy(h_len, lens + at, m * 8);
+                    HIP_TRY(hipMemcpyAsync(ov.d_lens + at, h_len, m * 8, hipMemcpyHostToDevice, st));
+                }
+                int r = insert_rows(ov.ix, h_dig, hipMemcpyHostToDevice, nullptr, m, ov.n - at, ov.d_first + at, nullptr, st);
+                if (r) return r;  // complete on return: the pinned piece is free again
+            }
+            return ov.run(ov.d_lens, rows_out, bytes_out, st);
+        }();
+    ov.release(st, rc != OXH_OK);
+    return rc;
 }
 
 }  // extern "C"

@@ -511,6 +511,113 @@ def dedup_report(table, index=None, chunk_size: Optional[int] = None) -> dict:
     return out
 
 
+OXH_CHUNK_OVERLAP_MAX_SETS = 256  # include/oxen_hash.h
+
+
+class ChunkOverlap(NamedTuple):
+    """rows[a][b] = the rows of set a, with multiplicity, whose digest occurs in set b (the diagonal is
+    set a's row count; not symmetric when a set repeats a digest); bytes the same sum over the rows'
+    lengths, None when no lengths were given. Both (nsets, nsets) uint64."""
+    rows: np.ndarray
+    bytes: Optional[np.ndarray]
+
+
+def _set_first(counts) -> np.ndarray:
+    first = np.zeros(len(counts) + 1, dtype=np.uint64)
+    np.cumsum(np.asarray(counts, dtype=np.uint64), out=first[1:])
+    return first
+
+
+def chunk_overlap(sets, lens=None, ctx: Optional[_capi.Context] = None) -> ChunkOverlap:
+    """oxh_chunk_overlap_host: how many chunks each set shares with each other set, all pairs in one
+    call on the device -- oxendedup.rs:56-70 `count_commit_overlap(c1, c2)` is rows[c1][c2].
+    sets: a list of (n_k, 2) uint64 arrays of (lo, hi) rows, or of FastCdcTable / FixedChunkTable
+    objects (their lengths come through table_lens); lens: one array of n_k lengths per set, or None."""
+    from .hasher import default_context
+
+    digs, lns = [], []
+    for k, s in enumerate(sets):
+        if hasattr(s, "digests") and hasattr(s, "first"):
+            digs.append(_digest_rows(s.digests))
+            lns.append(table_lens(s) if lens is None else None)
+        else:
+            digs.append(_digest_rows(s))
+            lns.append(None)
+        if lens is not None:
+            lns[k] = np.ascontiguousarray(lens[k], dtype=np.uint64)
+        if lns[k] is not None and lns[k].shape != (digs[k].shape[0],):
+            raise _capi.OxenError(f"set {k}: lens must hold one length per digest", _capi.OXH_ERR_INVALID)
+    nsets = len(digs)
+    with_lens = nsets > 0 and all(l is not None for l in lns)
+    dig = np.concatenate(digs) if nsets else np.zeros((0, 2), dtype=np.uint64)
+    ln = np.concatenate(lns) if with_lens else None
+    first = _set_first([d.shape[0] for d in digs])
+    rows = np.zeros((nsets, nsets), dtype=np.uint64)
+    nbytes = np.zeros((nsets, nsets), dtype=np.uint64) if with_lens else None
+    # without a device there is no context to make: the library answers OXH_ERR_NODEVICE (after its
+    # argument checks, which need neither)
+    handle = (ctx or default_context()).handle if ctx is not None or torch.cuda.is_available() else None
+    _capi.check(_capi.lib().oxh_chunk_overlap_host(handle, dig.ctypes.data_as(_capi._u64p),
+                                         ln.ctypes.data_as(_capi._u64p) if ln is not None else None,
+                                         first.ctypes.data_as(_capi._u64p), nsets, rows.ctypes.data_as(_capi._u64p),
+                                         nbytes.ctypes.data_as(_capi._u64p) if nbytes is not None else None),
+                "oxh_chunk_overlap_host")
+    return ChunkOverlap(rows, nbytes)
+
+
+def chunk_overlap_device(d_digests: torch.Tensor, set_first, d_lens: Optional[torch.Tensor] = None, stream=None,
+                         ctx: Optional[_capi.Context] = None) -> ChunkOverlap:
+    """oxh_chunk_overlap_device: the same over device-resident tensors (digests (N, 2), 64-bit; lens N,
+    64-bit or None) on `stream` (default: the current torch stream); set_first: nsets + 1 host integers,
+    set k = rows [set_first[k], set_first[k+1]). The matrices come back in host memory. Blocks."""
+    from .device import _require_cuda, _stream
+    from .hasher import default_context
+
+    _require_cuda(d_digests, *([d_lens] if d_lens is not None else []))
+    if d_digests.element_size() != 8 or d_digests.numel() % 2 or not d_digests.is_contiguous():
+        raise _capi.OxenError("d_digests must be a contiguous 64-bit (n, 2) tensor", _capi.OXH_ERR_INVALID)
+    n = d_digests.numel() // 2
+    if d_lens is not None and (d_lens.element_size() != 8 or d_lens.numel() != n or not d_lens.is_contiguous()):
+        raise _capi.OxenError("d_lens must be a contiguous 64-bit tensor of one length per digest", _capi.OXH_ERR_INVALID)
+    first = np.ascontiguousarray(set_first, dtype=np.uint64)
+    if first.ndim != 1 or first.size < 2 or int(first[-1]) != n:
+        raise _capi.OxenError("set_first must hold nsets + 1 entries and end at the row count", _capi.OXH_ERR_INVALID)
+    nsets = first.size - 1
+    rows = np.zeros((nsets, nsets), dtype=np.uint64)
+    nbytes = np.zeros((nsets, nsets), dtype=np.uint64) if d_lens is not None else None
+    _capi.check(_capi.lib().oxh_chunk_overlap_device((ctx or default_context()).handle, d_digests.data_ptr() if n else None,
+                                                     d_lens.data_ptr() if d_lens is not None and n else None,
+                                                     first.ctypes.data_as(_capi._u64p), nsets,
+                                                     rows.ctypes.data_as(_capi._u64p),
+                                                     nbytes.ctypes.data_as(_capi._u64p) if nbytes is not None else None,
+                                                     _stream(stream)), "oxh_chunk_overlap_device")
+    return ChunkOverlap(rows, nbytes)
+
+
+def names_to_digests(names) -> np.ndarray:
+    """Decimal u128 chunk names (chunk_name, the strings of get_chunk_hashes) -> (n, 2) uint64 rows of
+    (lo, hi): the inverse of chunk_name."""
+    out = np.zeros((len(names), 2), dtype=np.uint64)
+    for i, name in enumerate(names):
+        v = int(name)
+        if not 0 <= v < 1 << 128 or str(v) != str(name):
+            raise _capi.OxenError(f"{name!r} is not the decimal name of a 128-bit digest", _capi.OXH_ERR_INVALID)
+        out[i, 0], out[i, 1] = v & ((1 << 64) - 1), v >> 64
+    return out
+
+
+def count_commit_overlap(commit1, commit2, ctx: Optional[_capi.Context] = None) -> int:
+    """oxendedup.rs:56-70: the hashes of commit1, with multiplicity, that commit2 contains -- entry
+    [0][1] of one chunk_overlap call instead of a Vec::contains scan per hash."""
+    return int(chunk_overlap([names_to_digests(commit1), names_to_digests(commit2)], ctx=ctx).rows[0, 1])
+
+
+def rust_debug_strings(items) -> str:
+    """Rust's `{:?}` of a Vec<String> (the *_hashes.txt files, oxendedup.rs:170-173): `["1", "2"]`."""
+    esc = {"\\": "\\\\", '"': '\\"', "\n": "\\n", "\r": "\\r", "\t": "\\t"}
+    return "[" + ", ".join('"' + "".join(esc.get(c, c) for c in s) + '"' for s in items) + "]"
+
+
 # fixedsize.rs:67-91 reads through `BufReader::new(File)` (8 KiB buffer) and stops at the first read
 # shorter than chunk_size. BufReader::read serves a request from what is buffered (refilling with one
 # 8 KiB read when empty) unless the buffer is empty and the request is >= 8 KiB, which goes to the
@@ -783,6 +890,88 @@ def get_chunker(algorithm: str, chunk_size: int):
     if algorithm == "fastcdc":
         return FastCDChunker(chunk_size, 16)
     raise _capi.OxenError(f"Chunker '{algorithm}' not found", _capi.OXH_ERR_INVALID)
+
+
+VERSION_FILE_NAME = "data"  # oxendedup.rs:14
+
+
+class OxenChunker:
+    """oxendedup.rs:27-218, behind main.rs's `TestOxen`: pack one file's version blob in each of the n
+    latest commits and say how many chunks each version shares with the one before it."""
+
+    def __init__(self, chunk_size: int, chunk_algorithm: str, root_path):
+        self.chunk_size = int(chunk_size)
+        self.chunk_algorithm = str(chunk_algorithm)
+        self.root_path = os.fspath(root_path)
+
+    def version_dir(self, file_hash: str) -> str:
+        """oxendedup.rs:46-50: root/{hash[..2]}/{hash[2..]}."""
+        return os.path.join(self.root_path, file_hash[:2], file_hash[2:])
+
+    def version_path(self, file_hash: str) -> str:
+        """oxendedup.rs:52-54."""
+        return os.path.join(self.version_dir(file_hash), VERSION_FILE_NAME)
+
+    def pack(self, algo: str, chunk_size: int, versions, output_dir, n: Optional[int] = None,
+             ctx: Optional[_capi.Context] = None) -> dict:
+        """oxendedup.rs:72-209. versions: (commit_id, file_hash_hex or None) per commit, newest first --
+        what `commits::list` and `tree::get_file_by_path` give the reference (Oxen's commit and merkle
+        stores are not read here); the first n are used. Every present version is packed with
+        get_chunker(algo, chunk_size) into output_dir/<commit_id>; for every k >= 1 commit k's directory
+        gets <commit_{k-1}>_hashes.txt and <commit_k>_hashes.txt (`{:?}` of the chunk names). All overlaps
+        come from ONE chunk_overlap call over every version's get_chunk_hashes, where the reference runs
+        count_commit_overlap pair by pair. Returns {"commits", "matrix": ChunkOverlap, "pairs": [{"commit1",
+        "commit2", "overlap", "commit1_chunks", "commit2_chunks"}]}. No versions: ValueError (the
+        reference indexes [0]); a pair with a missing version: FileNotFoundError, as the reference's `?`."""
+        output_dir = os.fspath(output_dir)
+        latest = list(versions)[:n] if n is not None else list(versions)
+        if not latest:
+            raise ValueError("no commits to pack")
+        os.makedirs(output_dir, exist_ok=True)
+        chunker = get_chunker(algo, chunk_size)
+        commits = [str(c) for c, _ in latest]
+        hashes: list[list[str]] = []
+
+        def chunk_hashes(commit: str) -> list[str]:
+            try:
+                return chunker.get_chunk_hashes(os.path.join(output_dir, commit))
+            except FileNotFoundError as e:
+                raise FileNotFoundError(f"error getting chunk hashes for hash {commit} : {e}") from e
+
+        for k, (commit, file_hash) in enumerate(zip(commits, (h for _, h in latest))):
+            commit_dir = os.path.join(output_dir, commit)
+            os.makedirs(commit_dir, exist_ok=True)
+            if file_hash is not None:
+                chunker.pack(self.version_path(str(file_hash)), commit_dir)
+            else:
+                print(f"No file found for commit: {commit!r}")
+            if k >= 1:
+                if len(hashes) < k:
+                    hashes.append(chunk_hashes(commits[k - 1]))  # commit 0's, read with its first pair
+                hashes.append(chunk_hashes(commit))
+                for name, names in ((commits[k - 1], hashes[k - 1]), (commit, hashes[k])):
+                    with open(os.path.join(commit_dir, f"{name}_hashes.txt"), "w") as fh:
+                        fh.write(rust_debug_strings(names))
+        if not hashes:  # n == 1: no pair, and a missing version is no error
+            try:
+                hashes.append(chunk_hashes(commits[0]))
+            except FileNotFoundError:
+                hashes.append([])
+        matrix = chunk_overlap([names_to_digests(h) for h in hashes], ctx=ctx)
+        pairs = [{"commit1": commits[k - 1], "commit2": commits[k], "overlap": int(matrix.rows[k - 1, k]),
+                  "commit1_chunks": len(hashes[k - 1]), "commit2_chunks": len(hashes[k])} for k in range(1, len(commits))]
+        for p in pairs:  # oxendedup.rs:184-197
+            if p["overlap"] > 0:
+                print(f"Commit {p['commit1']} and {p['commit2']} have {p['overlap']} overlapping chunks out of "
+                      f"{p['commit1_chunks']}")
+            else:
+                print(f"Commit {p['commit1']} and {p['commit2']} have no overlapping chunks")
+        return {"commits": commits, "matrix": matrix, "pairs": pairs}
+
+    def unpack(self, input_dir, output_file):
+        """oxendedup.rs:211-217: the reference's stub -- it prints and returns output_file."""
+        print(f"Unpacking repository data with content-defined chunking... {os.fspath(input_dir)}")
+        return output_file
 
 
 def fastcdc_gear() -> list[int]:
