@@ -16,10 +16,11 @@ LIB = os.path.join(HERE, "liboxen_hash.so")
 # the C ABI runtime (capi_internal.hpp lists its pieces), the kernels, FastCDC, the reader pool, RCCL
 SOURCES = [os.path.join(CSRC, f) for f in (
     "xxh3_kernels.hip", "capi_dispatch.hip", "capi_context.hip", "staging.hip", "large_items.hip", "xxh3_stream.hip",
-    "engine.hip", "modified.hip", "publish.hip", "fastcdc.hip", "dedup_index.hip", "reader_pool.cpp", "comm.cpp",
-    "fastcdc_host.cpp")]
-DEPS = SOURCES + [os.path.join(CSRC, h) for h in ("capi_internal.hpp", "xxh3_device.hpp", "fastcdc_gear.h", "pool.hpp",
-                                                 "scratch.hpp", "reader_pool.hpp", "env.hpp")] + [os.path.join(ROOT, "include", "oxen_hash.h")]
+    "engine.hip", "modified.hip", "publish.hip", "fastcdc.hip", "fastcdc_scan.hip", "fastcdc_walk.hip", "dedup_index.hip",
+    "reader_pool.cpp", "comm.cpp", "fastcdc_host.cpp")]
+DEPS = SOURCES + [os.path.join(CSRC, h) for h in ("capi_internal.hpp", "xxh3_device.hpp", "fastcdc_gear.h", "fastcdc_plan.hpp",
+                                                 "fastcdc_device.hpp", "pool.hpp", "scratch.hpp", "reader_pool.hpp",
+                                                 "env.hpp")] + [os.path.join(ROOT, "include", "oxen_hash.h")]
 HELPER_SRC = os.path.join(CSRC, "hash_helper.cpp")
 HELPER = os.path.join(HERE, "oxh_hash_helper")  # the reader-pool helper process (oxh_pool_*)
 ARCH = "gfx950"
@@ -52,6 +53,8 @@ FAKE_HELPER_SRC = os.path.join(ROOT, "tests", "native", "fake_pool_helper.cpp")
 FAKE_HELPER = os.path.join(ROOT, "tests", "native", "fake_pool_helper")  # tests only: the pool without a GPU
 C_CONSUMER_SRC = os.path.join(ROOT, "tests", "native", "abi_c_consumer.c")
 C_CONSUMER = os.path.join(ROOT, "tests", "native", "abi_c_consumer")  # tests only: a plain C99 caller of the ABI
+PLAN_TEST_SRC = os.path.join(ROOT, "tests", "native", "cdc_plan_test.cpp")
+PLAN_TEST = os.path.join(ROOT, "tests", "native", "cdc_plan_test")  # tests only: the FastCDC planner on the CPU
 FAKE_RCCL_SRC = os.path.join(ROOT, "tests", "native", "fake_rccl.cpp")
 # tests only: an "RCCL" for N processes on one GPU (OXH_RCCL_LIB), with and without ncclGather
 FAKE_RCCL = os.path.join(ROOT, "tests", "native", "libfake_rccl.so")
@@ -66,7 +69,8 @@ def _stale(target: str, deps: list[str]) -> bool:
 def build_host(force: bool = False, verbose: bool = False) -> str:
     """The C++ host mirror over the C ABI (oxen_amd/host, g++): liboxen `util::hasher` + MerkleHash
     and the commit writer's K2 driver, in liboxen_hasher.so; its native test programs
-    (tests/native/test_hasher.cpp, commit_tree_cli.cpp). All link against liboxen_hash.so."""
+    (tests/native/test_hasher.cpp, commit_tree_cli.cpp), which link against liboxen_hash.so; and the
+    stand-alone CPU test of the FastCDC planner (tests/native/cdc_plan_test.cpp)."""
     hdr = os.path.join(ROOT, "include", "oxen_hash.h")
     steps = [
         (HELPER, [HELPER_SRC, os.path.join(CSRC, "reader_pool.hpp"), hdr, LIB],
@@ -86,13 +90,19 @@ def build_host(force: bool = False, verbose: bool = False) -> str:
         (COMMIT_CLI, [COMMIT_CLI_SRC, COMMIT_HDR, HOST_HDR, HOST_LIB],
          ["g++", "-std=c++17", "-O2", "-Wall", "-o", COMMIT_CLI + ".tmp", COMMIT_CLI_SRC,
           f"-L{HERE}", "-l:liboxen_hasher.so", "-l:liboxen_hash.so", "-Wl,-rpath,$ORIGIN/../../oxen_amd"]),
+        (PLAN_TEST, [PLAN_TEST_SRC, os.path.join(CSRC, "fastcdc_plan.hpp"), hdr],
+         ["g++", "-std=c++17", "-O2", "-Wall", "-o", PLAN_TEST + ".tmp", PLAN_TEST_SRC]),
     ]
     for target, extra in ((FAKE_RCCL, []), (FAKE_RCCL_NOGATHER, ["-DFAKE_NO_GATHER"])):
         steps.append((target, [FAKE_RCCL_SRC],
                       ["g++", "-std=c++17", "-O2", "-Wall", "-shared", "-fPIC", "-fvisibility=hidden",
                        "-D__HIP_PLATFORM_AMD__", f"-I{ROCM}/include", "-o", target + ".tmp", FAKE_RCCL_SRC] + extra +
                       [f"-L{ROCM}/lib", "-lamdhip64", "-lrt", f"-Wl,-rpath,{ROCM}/lib"]))
+    tests_native = os.path.join(ROOT, "tests", "native") + os.sep
     for target, deps, cmd in steps:
+        # a test program is built where its source is: the package builds beside any tests/ tree, or none
+        if deps[0].startswith(tests_native) and not os.path.exists(deps[0]):
+            continue
         if force or _stale(target, deps):
             if verbose:
                 print(" ".join(cmd), file=sys.stderr)

@@ -42,6 +42,7 @@
 
 #include "../../include/oxen_hash.h"
 #include "env.hpp"
+#include "fastcdc_plan.hpp"
 #include "pool.hpp"
 
 namespace oxh {
@@ -611,10 +612,9 @@ constexpr uint64_t kMaxFixedChunk = (3ull << 30) - (64ull << 20);
 // the crate's asserts (v2020::FastCDC::with_level) or the fixed chunk size's range, before any I/O
 int check_params(uint32_t mn, uint32_t av, uint32_t mx, uint32_t lv, uint64_t fixed) {
     if (fixed) return fixed > kMaxFixedChunk ? oxh::set_error(OXH_ERR_INVALID, "chunk_size above 3 GiB - 64 MiB") : OXH_OK;
-    uint64_t ms = 0, ml = 0;
-    if (mn < 64 || mn > 1048576) return oxh::set_error(OXH_ERR_INVALID, "min_size must be in [64, 1048576]");
-    if (mx < 1024 || mx > 16777216) return oxh::set_error(OXH_ERR_INVALID, "max_size must be in [1024, 16777216]");
-    return oxh_fastcdc_masks(av, lv, &ms, &ml);
+    const char* bad = nullptr;
+    const int rc = oxh::cdc_check_params(mn, av, mx, lv, &bad);
+    return rc ? oxh::set_error(rc, bad) : OXH_OK;
 }
 
 int run(oxh_ctx* ctx, CdcSource& src, uint64_t n, uint32_t mn, uint32_t av, uint32_t mx, uint32_t lv, uint64_t fixed,

@@ -14,7 +14,7 @@ the chunk q bytes long (byte q is the next chunk's first byte). The cut depends 
             eL and plant no trigger; the chunk is `max` long. An untestable length is reported in
             `absent`, and so is L = a0 + j, j <= 2, when no value of its j+1 hashed bytes matches.
 
-What each class of planted case is for in oxen_amd/csrc/fastcdc.hip:
+What each class of planted case is for in oxen_amd/csrc/fastcdc_scan.hip and fastcdc_walk.hip:
 
   trunc     L = a0 + j, j = 0..49: cdc_cut's and X's truncated window (the 47 positions from a0 whose
             hash has not seen 48 bytes: the walks recompute them from the bytes), its last position
@@ -54,7 +54,7 @@ from oracle import fastcdc as F
 
 GEAR = np.array(F.gear_table(), dtype=np.uint64)
 ANY = np.uint64(F.M64)  # an intermediate position with no condition (solve)
-HASH_SPAN = 47  # positions from a0 whose window is truncated (kHashSpan in fastcdc.hip)
+HASH_SPAN = 47  # positions from a0 whose window is truncated (kHashSpan in fastcdc_device.hpp)
 
 CONFIGS = [
     (4096, 8192, 16384),
