@@ -406,6 +406,63 @@ int oxh_chunk_overlap_device(oxh_ctx* ctx, const uint64_t* d_digests, const uint
 int oxh_chunk_overlap_host(oxh_ctx* ctx, const uint64_t* digests, const uint64_t* lens, const uint64_t* set_first,
                            uint64_t nsets, uint64_t* rows_out, uint64_t* bytes_out);
 
+/* ---------------------------------------------------------------- row hashes of a data frame, and the row set-diff
+ * `oxen diff` / `oxen df` on tabular files: core/df/tabular.rs:816-945 (`df_hash_rows`,
+ * `df_hash_rows_on_cols`) hashes every row of a frame -- `any_val_to_bytes` (:651-675) of each cell appended
+ * to one buffer, `hasher::hash_buffer` of it -- and repositories/diffs.rs:1023-1074
+ * (`compute_new_row_indices`) builds two HashMap<String, u32> over the hex strings to say which rows were
+ * added and which removed. Here the frame stays columnar (Arrow: values, offsets, validity bitmaps).
+ *
+ * A row's bytes are the concatenation, over the ncols columns IN THE ORDER GIVEN (the caller passes the
+ * frame's schema order), of each cell's bytes: none for a null; the raw little-endian bytes of a
+ * fixed-width cell (Int8: 1; Int32 / Float32: 4; Int64 / Float64 / Datetime(ms): 8); one byte 0 or 1 for a
+ * boolean; the UTF-8 bytes of a string. Every other dtype goes through to_string() in the reference: the
+ * caller renders such a column to strings and passes it as a byte column. Cells are not delimited, so
+ * ("ab","c") and ("a","bc") collide, as in the reference; a row of all nulls hashes the empty input.
+ * out[2r], out[2r+1] = XXH3-128 (lo, hi), seed 0, of row r's bytes.
+ *
+ * Columns are parallel arrays of ncols entries: kinds[c] (OXH_COL_*), values[c], offsets[c] (byte columns:
+ * nrows + 1 int32 / int64, row r = values[c][offsets[c][r] .. offsets[c][r+1]); offsets[c][0] need not be
+ * 0; ignored for the other kinds), validity[c] (NULL: no nulls; else an Arrow validity bitmap, row r's bit
+ * being bit bit_offsets[2c+1] + r, LSB first) and bit_offsets[2c] (OXH_COL_BOOL: row r's value is bit
+ * bit_offsets[2c] + r of values[c]). Bit offsets need not be multiples of 8 (a sliced Arrow array).
+ * kinds, bit_offsets and the three pointer arrays are HOST arrays in both forms and none may be NULL; what
+ * the pointers point to is on the device in _device (d_out too) and on the host in _host. Offsets must not
+ * decrease or be negative: the host form checks them (OXH_ERR_INVALID) and copies only the span
+ * [offsets[0], offsets[nrows]) of a byte column; the device form never reads outside the range a pair of
+ * offsets names -- a bad pair is a cell of length 0, and the call returns OXH_ERR_INVALID. Both forms block
+ * until complete.
+ * OXH_ERR_INVALID, before OXH_ERR_NODEVICE (there is no CPU path): a NULL array, ncols == 0, an unknown
+ * kind, more than 2^40 rows, then -- with rows -- NULL offsets of a byte column, NULL values (but for a byte
+ * column whose span is empty; the device form learns that on the device), a NULL out; then a NULL ctx.
+ * nrows == 0 (after the first four checks) is OXH_OK and touches nothing. A failed allocation is
+ * OXH_ERR_NOMEM with the outputs untouched. */
+#define OXH_COL_FIXED1 1      /* Int8 */
+#define OXH_COL_FIXED4 4      /* Int32, Float32 */
+#define OXH_COL_FIXED8 8      /* Int64, Float64, Datetime(ms) */
+#define OXH_COL_BOOL 16       /* Arrow bit-packed booleans, LSB first */
+#define OXH_COL_BYTES32 32    /* bytes + nrows+1 int32 offsets (Arrow Utf8/Binary) */
+#define OXH_COL_BYTES64 64    /* bytes + nrows+1 int64 offsets (LargeUtf8/LargeBinary) */
+int oxh_row_hashes_device(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const uint32_t* kinds, const void* const* d_values,
+                          const void* const* d_offsets, const uint8_t* const* d_validity, const uint64_t* bit_offsets,
+                          uint64_t* d_out, void* stream);
+int oxh_row_hashes_host(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const uint32_t* kinds, const void* const* values,
+                        const void* const* offsets, const uint8_t* const* validity, const uint64_t* bit_offsets, uint64_t* out);
+/* compute_new_row_indices over two digest tables (2 * n u64 each, (lo, hi) rows, as the row hashes above):
+ * HashMap::from_iter keeps the LAST row index of each distinct hash; `added` is that index for every distinct
+ * head digest absent from base, `removed` the mirror image. The device form writes one byte per row
+ * (d_removed: nbase, d_added: nhead; 1 = reported) and counts2 (host) = {removed, added}; the host form
+ * writes the ascending index lists (capacity nbase / nhead; u32, as the reference's Vec<u32>) and counts2.
+ * Either side may have 0 rows (its table and output may then be NULL). Both block until complete and keep
+ * nothing: a table of their own is built on the device and freed (memory: 56-72 B per row).
+ * OXH_ERR_INVALID, before OXH_ERR_NODEVICE: NULL counts2, more than 2^32 - 1 rows on a side, a NULL table
+ * or output of a side with rows; then a NULL ctx. No rows at all: OXH_OK, counts2 = {0, 0}. A failed
+ * allocation is OXH_ERR_NOMEM with the outputs untouched. */
+int oxh_row_diff_device(oxh_ctx* ctx, const uint64_t* d_base, uint64_t nbase, const uint64_t* d_head, uint64_t nhead,
+                        uint8_t* d_removed, uint8_t* d_added, uint64_t* counts2, void* stream);
+int oxh_row_diff_host(oxh_ctx* ctx, const uint64_t* base, uint64_t nbase, const uint64_t* head, uint64_t nhead,
+                      uint32_t* removed_idx, uint32_t* added_idx, uint64_t* counts2);
+
 /* ---------------------------------------------------------------- K2: merkle parent nodes */
 /* get_combined_hash (hasher.rs:67-80) x n on the device:
  * XXH3-128(content.to_le_bytes() || metadata.to_le_bytes()), inputs as (lo, hi) pairs. */

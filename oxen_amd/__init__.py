@@ -10,6 +10,8 @@ Modules:
   dedup     -- fixed-size and FastCDC chunking + chunk digests (block-level dedup), and the
                device-resident dedup index that says which chunks are duplicates (DedupIndex);
                chunk overlap between the versions of a file (chunk_overlap, OxenChunker)
+  tabular   -- row hashes of a data frame from its columns and the row set-diff (`oxen diff` on
+               tabular files: df_hash_rows, df_hash_rows_on_cols, compute_new_row_indices)
   procpool  -- file hashing sharded over reader processes (the open/close floor is per process)
   shard     -- multi-GPU sharding and the RCCL digest gather
   device    -- device-resident (HBM) batch entry points over torch buffers

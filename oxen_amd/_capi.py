@@ -32,6 +32,12 @@ OXH_MODE_WAVE_SHORT = 3
 OXH_MODE_WAVE_PACKED = 4
 OXH_MAX_STAGING_BYTES = 2147483392  # 2 GiB - 256 (include/oxen_hash.h)
 OXH_COMM_ID_BYTES = 128
+OXH_COL_FIXED1 = 1    # Int8
+OXH_COL_FIXED4 = 4    # Int32, Float32
+OXH_COL_FIXED8 = 8    # Int64, Float64, Datetime(ms)
+OXH_COL_BOOL = 16     # Arrow bit-packed booleans
+OXH_COL_BYTES32 = 32  # bytes + int32 offsets
+OXH_COL_BYTES64 = 64  # bytes + int64 offsets
 
 _u64 = ctypes.c_uint64
 _u32 = ctypes.c_uint32
@@ -113,6 +119,12 @@ SIGNATURES = {
     "oxh_dedup_index_counts": (_int, [_vp, _u64p]),
     "oxh_chunk_overlap_device": (_int, [_vp, _vp, _vp, _u64p, _u64, _u64p, _u64p, _vp]),
     "oxh_chunk_overlap_host": (_int, [_vp, _u64p, _u64p, _u64p, _u64, _u64p, _u64p]),
+    "oxh_row_hashes_device": (_int, [_vp, _u64, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                     ctypes.POINTER(_vp), _u64p, _vp, _vp]),
+    "oxh_row_hashes_host": (_int, [_vp, _u64, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                   ctypes.POINTER(_vp), _u64p, _u64p]),
+    "oxh_row_diff_device": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64p, _vp]),
+    "oxh_row_diff_host": (_int, [_vp, _u64p, _u64, _u64p, _u64, ctypes.POINTER(_u32), ctypes.POINTER(_u32), _u64p]),
     "oxh_comm_check": (_int, [_int]),
     "oxh_ctx_counters": (_int, [_vp, _u64p, _int]),
     "oxh_comm_unique_id": (_int, [ctypes.c_char_p]),

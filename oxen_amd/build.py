@@ -17,7 +17,7 @@ LIB = os.path.join(HERE, "liboxen_hash.so")
 SOURCES = [os.path.join(CSRC, f) for f in (
     "xxh3_kernels.hip", "capi_dispatch.hip", "capi_context.hip", "staging.hip", "large_items.hip", "xxh3_stream.hip",
     "engine.hip", "modified.hip", "publish.hip", "fastcdc.hip", "fastcdc_scan.hip", "fastcdc_walk.hip", "dedup_index.hip",
-    "reader_pool.cpp", "comm.cpp", "fastcdc_host.cpp")]
+    "row_hash.hip", "reader_pool.cpp", "comm.cpp", "fastcdc_host.cpp")]
 DEPS = SOURCES + [os.path.join(CSRC, h) for h in ("capi_internal.hpp", "xxh3_device.hpp", "fastcdc_gear.h", "fastcdc_plan.hpp",
                                                  "fastcdc_device.hpp", "pool.hpp", "scratch.hpp", "reader_pool.hpp",
                                                  "env.hpp")] + [os.path.join(ROOT, "include", "oxen_hash.h")]

@@ -13,6 +13,8 @@
 //   publish.hip        the fused add's version-store publisher and the fsck (oxh_add_files*, clean)
 //   dedup_index.hip    the device-resident dedup index: its kernels and entries (oxh_dedup_index_*), and
 //                      the chunk overlap between sets of digests built on it (oxh_chunk_overlap_*)
+//   row_hash.hip       row hashes of a data frame from its columns (oxh_row_hashes_*) and the row
+//                      set-diff over the index's public entries (oxh_row_diff_*)
 // There is no CPU hashing path: every digest this library returns was computed on the GPU.
 #pragma once
 

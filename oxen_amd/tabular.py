@@ -1,0 +1,271 @@
+"""Row hashes of a data frame from its columns, and the row set-diff (`oxen diff` / `oxen df`).
+
+The reference (core/df/tabular.rs:816-945 `df_hash_rows`, `df_hash_rows_on_cols`) walks a frame row by
+row: `any_val_to_bytes` (:651-675) of every cell appended to one buffer, `hasher::hash_buffer` of it, the
+hex string stored; repositories/diffs.rs:1023-1074 `compute_new_row_indices` then builds two
+HashMap<String, u32> over those strings. Here a frame stays columnar and `oxh_row_hashes_*` hashes every
+row on the device straight from the columns; `oxh_row_diff_*` answers the set question on the device too.
+
+A frame is an ordered mapping from column name to `Column`. A row's bytes are, over the columns in the
+frame's order: nothing for a null, the raw little-endian bytes of Int8 / Int32 / Float32 / Int64 /
+Float64 / Datetime(ms), one byte 0 or 1 for a boolean, the UTF-8 bytes of a string. Every other dtype
+goes through `to_string()` in the reference: render such a column to strings yourself and pass it as a
+byte column (polars' Display is not restated here). Cells are not delimited, as in the reference.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Any, Mapping, NamedTuple, Optional, Sequence
+
+import numpy as np
+
+from . import _capi
+from ._capi import (OXH_COL_BOOL, OXH_COL_BYTES32, OXH_COL_BYTES64, OXH_COL_FIXED1, OXH_COL_FIXED4,  # noqa: F401
+                    OXH_COL_FIXED8)
+
+_BYTES = (OXH_COL_BYTES32, OXH_COL_BYTES64)
+_WIDTH = {OXH_COL_FIXED1: 1, OXH_COL_FIXED4: 4, OXH_COL_FIXED8: 8}
+
+
+class Column(NamedTuple):
+    """One column as `oxh_row_hashes_*` takes it (numpy arrays for the host form, torch tensors on the
+    device for the device form). values: the nrows cells of a fixed-width column (any dtype of that
+    width), the bit-packed booleans (uint8, LSB first), or the bytes of a byte column (uint8);
+    offsets: nrows + 1 int32 / int64 for a byte column; validity: an Arrow validity bitmap (uint8) or
+    None for no nulls; value_bit / validity_bit: the bit of row 0 in a boolean's values / in validity."""
+    kind: int
+    nrows: int
+    values: Any
+    offsets: Any = None
+    validity: Any = None
+    value_bit: int = 0
+    validity_bit: int = 0
+
+
+def _pack(mask) -> np.ndarray:
+    return np.packbits(np.asarray(mask, dtype=bool), bitorder="little")
+
+
+def column(values, validity=None) -> Column:
+    """A Column from host data: a numpy array of int8 / int32 / float32 / int64 / float64 /
+    datetime64[ms] / bool, or a sequence of str / bytes / None (a string column; None is a null).
+    validity: a boolean mask (True = present) or None."""
+    mask = None if validity is None else _pack(validity)
+    if not isinstance(values, np.ndarray):
+        items = list(values)
+        present = [v is not None for v in items]
+        raw = [b"" if v is None else (v.encode("utf-8") if isinstance(v, str) else bytes(v)) for v in items]
+        offsets = np.zeros(len(raw) + 1, dtype=np.int64)
+        np.cumsum([len(b) for b in raw], out=offsets[1:])
+        wide = int(offsets[-1]) > np.iinfo(np.int32).max
+        data = np.frombuffer(b"".join(raw), dtype=np.uint8)
+        if mask is None and not all(present):
+            mask = _pack(present)
+        return Column(OXH_COL_BYTES64 if wide else OXH_COL_BYTES32, len(raw), data,
+                      offsets if wide else offsets.astype(np.int32), mask)
+    a = np.ascontiguousarray(values)
+    if a.ndim != 1:
+        raise _capi.OxenError("a column is one-dimensional", _capi.OXH_ERR_INVALID)
+    if a.dtype == np.bool_:
+        return Column(OXH_COL_BOOL, a.size, _pack(a), None, mask)
+    if a.dtype in (np.dtype(np.int8), np.dtype(np.int32), np.dtype(np.float32), np.dtype(np.int64), np.dtype(np.float64),
+                   np.dtype("datetime64[ms]")):
+        return Column(a.dtype.itemsize, a.size, a, None, mask)
+    raise _capi.OxenError(f"dtype {a.dtype} has no raw row bytes in the reference (it goes through to_string()): "
+                          "cast the column to strings", _capi.OXH_ERR_INVALID)
+
+
+def _as_columns(columns) -> list:
+    cols = [c if isinstance(c, Column) else column(c) for c in columns]
+    if cols and any(c.nrows != cols[0].nrows for c in cols):
+        raise _capi.OxenError("the columns of a frame have one row count", _capi.OXH_ERR_INVALID)
+    return cols
+
+
+def _tables(cols, ptr):
+    """The five parallel arrays of the ABI; ptr(x) = the address of an array / tensor, None for None."""
+    n = len(cols)
+    kinds = (ctypes.c_uint32 * max(n, 1))(*[int(c.kind) for c in cols])
+    values = (ctypes.c_void_p * max(n, 1))(*[ptr(c.values) for c in cols])
+    offsets = (ctypes.c_void_p * max(n, 1))(*[ptr(c.offsets) if c.kind in _BYTES else None for c in cols])
+    validity = (ctypes.c_void_p * max(n, 1))(*[ptr(c.validity) for c in cols])
+    bits = (ctypes.c_uint64 * max(2 * n, 1))()
+    for k, c in enumerate(cols):
+        bits[2 * k], bits[2 * k + 1] = int(c.value_bit), int(c.validity_bit)
+    return kinds, values, offsets, validity, bits
+
+
+def _handle(ctx):
+    # without a device there is no context to make: the library answers OXH_ERR_NODEVICE (after its
+    # argument checks, which need neither)
+    import torch
+
+    from .hasher import default_context
+
+    if ctx is not None:
+        return ctx.handle
+    return default_context().handle if torch.cuda.is_available() else None
+
+
+def row_hashes(columns: Sequence, ctx: Optional[_capi.Context] = None) -> np.ndarray:
+    """oxh_row_hashes_host: (n, 2) uint64 rows of (lo, hi), the XXH3-128 of every row's bytes.
+    columns: `Column`s (or what `column` takes) in the frame's order, in host memory."""
+    cols = _as_columns(columns)
+    nrows = cols[0].nrows if cols else 0
+    keep = []
+
+    def ptr(a):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a)
+        keep.append(a)
+        return a.ctypes.data if a.size else None
+
+    out = np.zeros((nrows, 2), dtype=np.uint64)
+    _capi.check(_capi.lib().oxh_row_hashes_host(_handle(ctx), nrows, len(cols), *_tables(cols, ptr),
+                                                out.ctypes.data_as(_capi._u64p)), "oxh_row_hashes_host")
+    return out
+
+
+def row_hashes_device(columns: Sequence[Column], stream=None, ctx: Optional[_capi.Context] = None):
+    """oxh_row_hashes_device: the same over `Column`s whose values / offsets / validity are torch tensors
+    on the device; returns an (n, 2) int64 device tensor holding the raw u64 words. Blocks."""
+    import torch
+
+    from .device import _require_cuda, _stream
+
+    cols = list(columns)
+    nrows = cols[0].nrows if cols else 0
+    tensors = [t for c in cols for t in (c.values, c.offsets, c.validity) if t is not None]
+    _require_cuda(*tensors)
+    if any(not t.is_contiguous() for t in tensors):
+        raise _capi.OxenError("column tensors must be contiguous", _capi.OXH_ERR_INVALID)
+    device = tensors[0].device if tensors else "cuda"
+    out = torch.empty((nrows, 2), dtype=torch.int64, device=device)
+    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()  # noqa: E731
+    _capi.check(_capi.lib().oxh_row_hashes_device(_handle(ctx), nrows, len(cols), *_tables(cols, ptr),
+                                                  out.data_ptr() if nrows else None, _stream(stream)),
+                "oxh_row_hashes_device")
+    return out
+
+
+def row_hash_strings(digests) -> list:
+    """The reference's row-hash strings: `format!("{:x}")` of the u128, lowercase and unpadded
+    (oxh_format_hex)."""
+    a = np.ascontiguousarray(digests, dtype=np.uint64).reshape(-1, 2)
+    buf = ctypes.create_string_buffer(33)
+    L = _capi.lib()
+    out = []
+    for lo, hi in a.tolist():
+        n = L.oxh_format_hex(lo, hi, buf)
+        out.append(buf.raw[:n].decode())
+    return out
+
+
+def df_hash_rows(frame: Mapping, ctx: Optional[_capi.Context] = None) -> np.ndarray:
+    """tabular.rs:816-878: the hash of every row over all the frame's columns, in its schema order."""
+    return row_hashes(list(frame.values()), ctx=ctx)
+
+
+def df_hash_rows_on_cols(frame: Mapping, hash_fields, ctx: Optional[_capi.Context] = None) -> Optional[np.ndarray]:
+    """tabular.rs:880-945: the hash of every row over the columns named in hash_fields. The frame's
+    column order is kept, not that of hash_fields; names that are not in the frame are ignored; None
+    (the reference's null column) when no named column is present."""
+    wanted = set(hash_fields)
+    cols = [c for name, c in frame.items() if name in wanted]
+    if not cols:
+        return None
+    return row_hashes(cols, ctx=ctx)
+
+
+def _digests(a) -> np.ndarray:
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    if a.ndim != 2 or a.shape[1] != 2:
+        if a.size == 0:
+            return a.reshape(0, 2)
+        raise _capi.OxenError("digests must be an (n, 2) uint64 array of (lo, hi) rows", _capi.OXH_ERR_INVALID)
+    return a
+
+
+def row_diff(base_digests, head_digests, ctx: Optional[_capi.Context] = None):
+    """oxh_row_diff_host over two (n, 2) digest tables: (added, removed), ascending uint32 row indices --
+    the last row of every distinct head digest that base lacks, and the mirror image."""
+    base, head = _digests(base_digests), _digests(head_digests)
+    removed = np.zeros(base.shape[0], dtype=np.uint32)
+    added = np.zeros(head.shape[0], dtype=np.uint32)
+    counts = np.zeros(2, dtype=np.uint64)
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    _capi.check(_capi.lib().oxh_row_diff_host(_handle(ctx), base.ctypes.data_as(_capi._u64p) if base.size else None,
+                                              base.shape[0], head.ctypes.data_as(_capi._u64p) if head.size else None,
+                                              head.shape[0], removed.ctypes.data_as(u32p) if base.size else None,
+                                              added.ctypes.data_as(u32p) if head.size else None,
+                                              counts.ctypes.data_as(_capi._u64p)), "oxh_row_diff_host")
+    return added[:int(counts[1])], removed[:int(counts[0])]
+
+
+def row_diff_device(d_base, d_head, stream=None, ctx: Optional[_capi.Context] = None):
+    """oxh_row_diff_device over two (n, 2) 64-bit device tensors: (added, removed, counts) -- one uint8
+    flag per head / base row on the device (1 = reported) and counts = (added rows, removed rows)."""
+    import torch
+
+    from .device import _require_cuda, _stream
+
+    _require_cuda(d_base, d_head)
+    for t in (d_base, d_head):
+        if t.element_size() != 8 or t.numel() % 2 or not t.is_contiguous():
+            raise _capi.OxenError("digest tables must be contiguous 64-bit (n, 2) tensors", _capi.OXH_ERR_INVALID)
+    nbase, nhead = d_base.numel() // 2, d_head.numel() // 2
+    removed = torch.zeros(nbase, dtype=torch.uint8, device=d_base.device)
+    added = torch.zeros(nhead, dtype=torch.uint8, device=d_head.device)
+    counts = np.zeros(2, dtype=np.uint64)
+    ptr = lambda t: t.data_ptr() if t.numel() else None  # noqa: E731
+    _capi.check(_capi.lib().oxh_row_diff_device(_handle(ctx), ptr(d_base), nbase, ptr(d_head), nhead, ptr(removed), ptr(added),
+                                                counts.ctypes.data_as(_capi._u64p), _stream(stream)), "oxh_row_diff_device")
+    return added, removed, (int(counts[1]), int(counts[0]))
+
+
+def compute_new_row_indices(base: Mapping, head: Mapping, ctx: Optional[_capi.Context] = None):
+    """diffs.rs:1023-1074 over two frames: (added, removed), each ascending -- two row-hash calls and one
+    diff call."""
+    return row_diff(df_hash_rows(base, ctx=ctx), df_hash_rows(head, ctx=ctx), ctx=ctx)
+
+
+def _buffer(buf, dtype) -> Optional[np.ndarray]:
+    return None if buf is None or buf.size == 0 else np.frombuffer(buf, dtype=dtype)
+
+
+def _arrow_column(name, arr) -> Column:
+    import pyarrow as pa
+
+    if isinstance(arr, pa.ChunkedArray):
+        arr = arr.combine_chunks() if arr.num_chunks != 1 else arr.chunk(0)
+    t, n, off = arr.type, len(arr), arr.offset
+    bufs = arr.buffers()
+    validity = _buffer(bufs[0], np.uint8) if arr.null_count else None
+    vbit = off if validity is not None else 0
+    width = {pa.int8(): 1, pa.int32(): 4, pa.float32(): 4, pa.int64(): 8, pa.float64(): 8}.get(t)
+    if width is None and pa.types.is_timestamp(t) and t.unit == "ms":
+        width = 8
+    if width is not None:
+        data = _buffer(bufs[1], np.uint8)
+        values = data[off * width:(off + n) * width] if data is not None else np.zeros(0, dtype=np.uint8)
+        return Column(width, n, values, None, validity, 0, vbit)
+    if pa.types.is_boolean(t):
+        return Column(OXH_COL_BOOL, n, _buffer(bufs[1], np.uint8), None, validity, off, vbit)
+    for kind, odt, match in ((OXH_COL_BYTES32, np.int32, (pa.types.is_string, pa.types.is_binary)),
+                             (OXH_COL_BYTES64, np.int64, (pa.types.is_large_string, pa.types.is_large_binary))):
+        if any(m(t) for m in match):
+            offsets = _buffer(bufs[1], odt)
+            offsets = offsets[off:off + n + 1] if offsets is not None else np.zeros(n + 1, dtype=odt)
+            return Column(kind, n, _buffer(bufs[2], np.uint8), offsets, validity, 0, vbit)
+    raise _capi.OxenError(f"column {name!r}: Arrow type {t} has no raw row bytes in the reference (it goes through "
+                          "to_string()): cast it to string first", _capi.OXH_ERR_INVALID)
+
+
+def columns_from_arrow(table_or_batch) -> dict:
+    """A pyarrow Table / RecordBatch as a frame: {name: Column} in schema order, the columns pointing
+    into the Arrow buffers (slices keep their offsets: nothing is copied but a chunked column's chunks).
+    Int8 / Int32 / Int64 / Float32 / Float64 / Timestamp(ms) / Boolean / (Large)Utf8 / (Large)Binary;
+    any other type raises: cast it to string, which is what the reference's `to_string()` arm amounts to."""
+    names = table_or_batch.schema.names
+    return {name: _arrow_column(name, table_or_batch.column(i)) for i, name in enumerate(names)}
