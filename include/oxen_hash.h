@@ -463,6 +463,66 @@ int oxh_row_diff_device(oxh_ctx* ctx, const uint64_t* d_base, uint64_t nbase, co
 int oxh_row_diff_host(oxh_ctx* ctx, const uint64_t* base, uint64_t nbase, const uint64_t* head, uint64_t nhead,
                       uint32_t* removed_idx, uint32_t* added_idx, uint64_t* counts2);
 
+/* ---------------------------------------------------------------- keyed tabular diff
+ * `oxen diff --keys ... --targets ...` after the four df_hash_rows_on_cols passes (repositories/diffs.rs:
+ * 881-901 `diff_dfs`, :1009-1021 `hash_dfs`): repositories/diffs/join_diff.rs full-joins the two frames on
+ * the key hash (:290), labels every joined row through `test_function` (:458-484), filters the unchanged
+ * ones out (:88-92), counts the rest (:434-456) and counts the rows of duplicated keys on each side
+ * (core/df/tabular.rs:263-271 `n_duped_rows`). Here the join, the labels and the counts are one call over
+ * the digest tables; nothing row-shaped crosses the link but the result.
+ *
+ * Per side (left = df_1, right = df_2): the key digests (2 * n u64 of (lo, hi) rows, as oxh_row_hashes_*
+ * writes them), the target digests (the same shape; NULL = the reference's null column, no named target
+ * is in that frame) and the validity bitmap of the cell of keys[0] -- the first key AS THE CALLER LISTED
+ * IT -- (Arrow, LSB first, row r of the left side = bit bit_offsets2[0] + r, of the right side bit
+ * bit_offsets2[1] + r; NULL = no nulls; offsets need not be multiples of 8). bit_offsets2 and counts8 are
+ * HOST arrays in both forms; every other pointer is device memory in _device and host memory in _host.
+ *
+ * Joined rows: every (l, r) whose key digests are equal (the whole cross product when a key repeats),
+ * (l, none) for a left row without a partner, (none, r) for a right row without one. Status, in the order
+ * test_function tests: 1. left absent or the left row's keys[0] cell null -> ADDED (a matched pair too);
+ * 2. else right absent or the right row's keys[0] cell null -> REMOVED; 3. else both target tables NULL ->
+ * UNCHANGED; 4. else the target digests differ -> MODIFIED (NULL equals NULL and differs from every
+ * digest, so with one table NULL every pair that gets here is MODIFIED); 5. else UNCHANGED.
+ *
+ * counts8 = {emitted pairs, added, removed, modified, unchanged, rows of duplicated keys left, right,
+ * pairs written}; [1..4] count all joined rows whatever the flag. Emitted are all joined rows with
+ * OXH_KEYED_DIFF_KEEP_UNCHANGED, the not-UNCHANGED ones without. The pairs go to three parallel arrays of
+ * `capacity` entries, left_idx / right_idx (OXH_KEYED_DIFF_NONE = absent) and status (OXH_DIFF_*), ONLY
+ * when emitted <= capacity (then counts8[7] == counts8[0]); otherwise counts8[7] = 0, the arrays are
+ * untouched and the call is still OXH_OK: call again with counts8[0]. capacity == 0 with NULL arrays is
+ * the counts-only call. nleft + nright entries are enough whenever no key repeats on the right.
+ * Order of the pairs: the left rows ascending, each followed by its pairs or its one (l, none); then the
+ * right-only rows ascending. Within one left row's pairs the host form writes the right rows ascending;
+ * the DEVICE FORM MAY WRITE THEM IN ANY ORDER (only the rows of a key that repeats on the right are
+ * affected), and that order may differ from call to call.
+ *
+ * Both forms block until complete and keep nothing: a private index and one device block are freed once
+ * the stream has drained, and no oxh_dedup_index_* handle of the context is touched (memory: 68-84 B per
+ * row of both sides together, 4 B more per right row; the host form adds the tables it copies, 16-32 B per
+ * row, and 9 B per emitted pair).
+ * OXH_ERR_INVALID, before OXH_ERR_NODEVICE (there is no CPU path): NULL counts8 or bit_offsets2; more than
+ * 2^32 - 2 rows on a side; a NULL key table of a side with rows; a target table of a side with rows that
+ * overlaps that side's key table without being the same pointer (two tables of n rows cannot share part
+ * of their bytes; the same pointer -- keys and targets naming the same columns -- is fine); capacity > 0
+ * with a NULL array; a flag bit other than OXH_KEYED_DIFF_KEEP_UNCHANGED; then a NULL ctx. No rows at
+ * all: OXH_OK, counts8 zeroed. A failed allocation is OXH_ERR_NOMEM with the outputs untouched. */
+#define OXH_KEYED_DIFF_KEEP_UNCHANGED 1
+#define OXH_KEYED_DIFF_NONE 0xFFFFFFFF
+#define OXH_DIFF_UNCHANGED 0
+#define OXH_DIFF_ADDED 1
+#define OXH_DIFF_REMOVED 2
+#define OXH_DIFF_MODIFIED 3
+int oxh_keyed_diff_device(oxh_ctx* ctx, const uint64_t* d_left_keys, uint64_t nleft, const uint64_t* d_right_keys,
+                          uint64_t nright, const uint64_t* d_left_targets, const uint64_t* d_right_targets,
+                          const uint8_t* d_left_key0_valid, const uint8_t* d_right_key0_valid, const uint64_t* bit_offsets2,
+                          uint32_t flags, uint64_t capacity, uint32_t* d_left_idx, uint32_t* d_right_idx, uint8_t* d_status,
+                          uint64_t* counts8, void* stream);
+int oxh_keyed_diff_host(oxh_ctx* ctx, const uint64_t* left_keys, uint64_t nleft, const uint64_t* right_keys, uint64_t nright,
+                        const uint64_t* left_targets, const uint64_t* right_targets, const uint8_t* left_key0_valid,
+                        const uint8_t* right_key0_valid, const uint64_t* bit_offsets2, uint32_t flags, uint64_t capacity,
+                        uint32_t* left_idx, uint32_t* right_idx, uint8_t* status, uint64_t* counts8);
+
 /* ---------------------------------------------------------------- K2: merkle parent nodes */
 /* get_combined_hash (hasher.rs:67-80) x n on the device:
  * XXH3-128(content.to_le_bytes() || metadata.to_le_bytes()), inputs as (lo, hi) pairs. */

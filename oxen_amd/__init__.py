@@ -11,7 +11,8 @@ Modules:
                device-resident dedup index that says which chunks are duplicates (DedupIndex);
                chunk overlap between the versions of a file (chunk_overlap, OxenChunker)
   tabular   -- row hashes of a data frame from its columns and the row set-diff (`oxen diff` on
-               tabular files: df_hash_rows, df_hash_rows_on_cols, compute_new_row_indices)
+               tabular files: df_hash_rows, df_hash_rows_on_cols, compute_new_row_indices), and the
+               keyed diff of two frames (keyed_diff_digests, diff_dfs)
   procpool  -- file hashing sharded over reader processes (the open/close floor is per process)
   shard     -- multi-GPU sharding and the RCCL digest gather
   device    -- device-resident (HBM) batch entry points over torch buffers
@@ -25,6 +26,8 @@ __version__ = "0.1.0"
 # re-exported from oxen_amd.dedup on first use (that module imports torch; `import oxen_amd` does not)
 _FROM_DEDUP = ("ChunkOverlap", "chunk_overlap", "chunk_overlap_device", "names_to_digests", "count_commit_overlap",
                "OxenChunker")
+# and from oxen_amd.tabular
+_FROM_TABULAR = ("KeyedDiff", "STATUS_NAMES", "keyed_diff_digests", "keyed_diff_digests_device", "diff_dfs")
 
 
 def __getattr__(name):
@@ -32,4 +35,8 @@ def __getattr__(name):
         from . import dedup
 
         return getattr(dedup, name)
+    if name in _FROM_TABULAR:
+        from . import tabular
+
+        return getattr(tabular, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -38,6 +38,12 @@ OXH_COL_FIXED8 = 8    # Int64, Float64, Datetime(ms)
 OXH_COL_BOOL = 16     # Arrow bit-packed booleans
 OXH_COL_BYTES32 = 32  # bytes + int32 offsets
 OXH_COL_BYTES64 = 64  # bytes + int64 offsets
+OXH_KEYED_DIFF_KEEP_UNCHANGED = 1
+OXH_KEYED_DIFF_NONE = 0xFFFFFFFF
+OXH_DIFF_UNCHANGED = 0
+OXH_DIFF_ADDED = 1
+OXH_DIFF_REMOVED = 2
+OXH_DIFF_MODIFIED = 3
 
 _u64 = ctypes.c_uint64
 _u32 = ctypes.c_uint32
@@ -125,6 +131,9 @@ SIGNATURES = {
                                    ctypes.POINTER(_vp), _u64p, _u64p]),
     "oxh_row_diff_device": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64p, _vp]),
     "oxh_row_diff_host": (_int, [_vp, _u64p, _u64, _u64p, _u64, ctypes.POINTER(_u32), ctypes.POINTER(_u32), _u64p]),
+    "oxh_keyed_diff_device": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _u64p, _u32, _u64, _vp, _vp, _vp, _u64p,
+                                     _vp]),
+    "oxh_keyed_diff_host": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _u64p, _u32, _u64, _vp, _vp, _vp, _u64p]),
     "oxh_comm_check": (_int, [_int]),
     "oxh_ctx_counters": (_int, [_vp, _u64p, _int]),
     "oxh_comm_unique_id": (_int, [ctypes.c_char_p]),

@@ -15,6 +15,9 @@
 //                      the chunk overlap between sets of digests built on it (oxh_chunk_overlap_*)
 //   row_hash.hip       row hashes of a data frame from its columns (oxh_row_hashes_*) and the row
 //                      set-diff over the index's public entries (oxh_row_diff_*)
+//   keyed_diff.hip     the keyed tabular diff over four digest tables (oxh_keyed_diff_*): join on the key
+//                      digests through the index's public entries, status of every joined row; and the
+//                      device-wide exclusive scan it orders its output with (exclusive_scan_u32)
 // There is no CPU hashing path: every digest this library returns was computed on the GPU.
 #pragma once
 
@@ -118,6 +121,18 @@ int launch_text(const uint8_t* arena, const uint64_t* offs, const uint64_t* lens
 int launch_chunks(const uint8_t* buf, uint64_t n, uint64_t chunk, uint64_t total, uint64_t* out, hipStream_t st);
 int launch_lane(const uint8_t* arena, const uint64_t* offs, const uint64_t* lens, uint64_t n, uint64_t* out,
                 hipStream_t st);
+
+}  // namespace oxh::capi
+
+// ---------------------------------------------------------------- device-wide scan (keyed_diff.hip)
+namespace oxh {
+// d_out[i] = d_in[0] + ... + d_in[i-1] over n u32, as u64, enqueued on `st` (three launches; no workgroup
+// waits for another). d_sums: scan_tiles(n) + 1 words of device scratch; the last receives the total.
+uint64_t scan_tiles(uint64_t n);
+int exclusive_scan_u32(const uint32_t* d_in, uint64_t n, uint64_t* d_out, unsigned long long* d_sums, hipStream_t st);
+}  // namespace oxh
+
+namespace oxh::capi {
 
 // ---------------------------------------------------------------- host resources (capi_context.hip)
 int usable_cpus();

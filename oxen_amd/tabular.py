@@ -1,10 +1,14 @@
-"""Row hashes of a data frame from its columns, and the row set-diff (`oxen diff` / `oxen df`).
+"""Row hashes of a data frame from its columns, the row set-diff and the keyed diff (`oxen diff` / `oxen df`).
 
 The reference (core/df/tabular.rs:816-945 `df_hash_rows`, `df_hash_rows_on_cols`) walks a frame row by
 row: `any_val_to_bytes` (:651-675) of every cell appended to one buffer, `hasher::hash_buffer` of it, the
 hex string stored; repositories/diffs.rs:1023-1074 `compute_new_row_indices` then builds two
 HashMap<String, u32> over those strings. Here a frame stays columnar and `oxh_row_hashes_*` hashes every
 row on the device straight from the columns; `oxh_row_diff_*` answers the set question on the device too.
+
+`oxh_keyed_diff_*` is `oxen diff --keys ... --targets ...` after the hashing (diffs.rs:881-901 `diff_dfs`,
+repositories/diffs/join_diff.rs): the full join of the two frames on their key hashes, every joined row
+labelled added / removed / modified / unchanged, and the summary counts -- `keyed_diff_digests`, `diff_dfs`.
 
 A frame is an ordered mapping from column name to `Column`. A row's bytes are, over the columns in the
 frame's order: nothing for a null, the raw little-endian bytes of Int8 / Int32 / Float32 / Int64 /
@@ -228,6 +232,170 @@ def compute_new_row_indices(base: Mapping, head: Mapping, ctx: Optional[_capi.Co
     """diffs.rs:1023-1074 over two frames: (added, removed), each ascending -- two row-hash calls and one
     diff call."""
     return row_diff(df_hash_rows(base, ctx=ctx), df_hash_rows(head, ctx=ctx), ctx=ctx)
+
+
+# ---------------------------------------------------------------- keyed diff
+STATUS_NAMES = ("unchanged", "added", "removed", "modified")   # by OXH_DIFF_* code
+
+
+class KeyedDiff(NamedTuple):
+    """The classified joined rows of a keyed diff, in the canonical order (the left rows ascending, each
+    followed by its pairs or its one (l, none); then the right-only rows ascending), and its summary.
+    left_rows / right_rows: -1 = absent; status: an index into STATUS_NAMES. added / removed / modified /
+    unchanged count all joined rows, emitted or not; dupes_left / dupes_right are the rows whose key
+    occurs more than once on their own side."""
+    left_rows: Any
+    right_rows: Any
+    status: Any
+    added: int
+    removed: int
+    modified: int
+    unchanged: int
+    dupes_left: int
+    dupes_right: int
+
+
+def _key0_valid(v, nrows):
+    """(bitmap, bit of row 0) from None, a boolean mask (True = present) or (Arrow bitmap, bit offset)."""
+    if v is None:
+        return None, 0
+    if isinstance(v, tuple):
+        bitmap, bit = v
+        if bitmap is None:
+            return None, 0
+        bitmap = np.ascontiguousarray(bitmap, dtype=np.uint8)
+        if bitmap.size * 8 < int(bit) + nrows:
+            raise _capi.OxenError("a validity bitmap is shorter than its rows", _capi.OXH_ERR_INVALID)
+        return bitmap, int(bit)
+    mask = np.asarray(v, dtype=bool)
+    if mask.shape != (nrows,):
+        raise _capi.OxenError("a validity mask has one entry per row", _capi.OXH_ERR_INVALID)
+    return _pack(mask), 0
+
+
+def keyed_diff_digests(left_keys, right_keys, left_targets=None, right_targets=None, left_key0_valid=None,
+                       right_key0_valid=None, keep_unchanged: bool = False, ctx: Optional[_capi.Context] = None) -> KeyedDiff:
+    """oxh_keyed_diff_host over (n, 2) uint64 digest tables: the full join of the two sides on their key
+    digests, every joined row labelled as join_diff.rs:458-484 (`test_function`) labels it, the unchanged
+    ones left out unless keep_unchanged. Targets: None = the null column (no named target in that frame).
+    *_key0_valid: the validity of the cell of keys[0] -- None (no nulls), a boolean mask, or (Arrow
+    bitmap, bit of row 0). A row whose keys[0] is null on the left is `added`, else one whose keys[0] is
+    null on the right `removed`, whatever it is paired with (the reference's behaviour).
+    The first call has room for nleft + nright pairs, enough unless a key repeats on the right of a
+    matched group; then the call is made again with the exact count."""
+    lk, rk = _digests(left_keys), _digests(right_keys)
+    nl, nr = lk.shape[0], rk.shape[0]
+    lt = None if left_targets is None else _digests(left_targets)
+    rt = None if right_targets is None else _digests(right_targets)
+    if (lt is not None and lt.shape[0] != nl) or (rt is not None and rt.shape[0] != nr):
+        raise _capi.OxenError("a target table has one row per key row", _capi.OXH_ERR_INVALID)
+    lv, lbit = _key0_valid(left_key0_valid, nl)
+    rv, rbit = _key0_valid(right_key0_valid, nr)
+    bits = np.array([lbit, rbit], dtype=np.uint64)
+    counts = np.zeros(8, dtype=np.uint64)
+    ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+    flags = _capi.OXH_KEYED_DIFF_KEEP_UNCHANGED if keep_unchanged else 0
+    capacity = nl + nr
+    while True:
+        left = np.empty(capacity, dtype=np.uint32)
+        right = np.empty(capacity, dtype=np.uint32)
+        status = np.empty(capacity, dtype=np.uint8)
+        _capi.check(_capi.lib().oxh_keyed_diff_host(_handle(ctx), ptr(lk), nl, ptr(rk), nr, ptr(lt), ptr(rt), ptr(lv), ptr(rv),
+                                                    bits.ctypes.data_as(_capi._u64p), flags, capacity, ptr(left), ptr(right),
+                                                    ptr(status), counts.ctypes.data_as(_capi._u64p)), "oxh_keyed_diff_host")
+        if int(counts[7]) == int(counts[0]):
+            break
+        capacity = int(counts[0])   # a key repeats on the right: now the exact count
+    n = int(counts[7])
+    none = _capi.OXH_KEYED_DIFF_NONE
+    rows = lambda a: np.where(a[:n] == none, -1, a[:n].astype(np.int64))  # noqa: E731
+    return KeyedDiff(rows(left), rows(right), status[:n].copy(), *(int(c) for c in counts[1:7]))
+
+
+def keyed_diff_digests_device(d_left_keys, d_right_keys, d_left_targets=None, d_right_targets=None, d_left_key0_valid=None,
+                              d_right_key0_valid=None, keep_unchanged: bool = False, stream=None,
+                              ctx: Optional[_capi.Context] = None) -> KeyedDiff:
+    """oxh_keyed_diff_device over (n, 2) 64-bit device tensors (targets: None = the null column;
+    *_key0_valid: None or (uint8 device tensor holding an Arrow bitmap, bit of row 0)). The three arrays
+    of the result are device tensors: left_rows / right_rows int32 holding the call's u32 words, so an
+    absent side reads -1 (and a row index of 2^31 or more negative: view them as unsigned then), status
+    uint8. Within one left row's pairs the right rows come in any order. Blocks."""
+    import torch
+
+    from .device import _require_cuda, _stream
+
+    valid = [v if v is not None else (None, 0) for v in (d_left_key0_valid, d_right_key0_valid)]
+    tables = [d_left_keys, d_right_keys, d_left_targets, d_right_targets]
+    tensors = [t for t in tables + [valid[0][0], valid[1][0]] if t is not None]
+    _require_cuda(*tensors)
+    for t in tables:
+        if t is not None and (t.element_size() != 8 or t.numel() % 2 or not t.is_contiguous()):
+            raise _capi.OxenError("digest tables must be contiguous 64-bit (n, 2) tensors", _capi.OXH_ERR_INVALID)
+    nl, nr = d_left_keys.numel() // 2, d_right_keys.numel() // 2
+    for t, n in ((d_left_targets, nl), (d_right_targets, nr)):
+        if t is not None and t.numel() != 2 * n:
+            raise _capi.OxenError("a target table has one row per key row", _capi.OXH_ERR_INVALID)
+    for (bitmap, bit), n in zip(valid, (nl, nr)):
+        if bitmap is not None and (bitmap.element_size() != 1 or not bitmap.is_contiguous() or bitmap.numel() * 8 < int(bit) + n):
+            raise _capi.OxenError("a validity bitmap is a contiguous uint8 tensor that holds its rows' bits",
+                                  _capi.OXH_ERR_INVALID)
+    bits = np.array([int(valid[0][1]), int(valid[1][1])], dtype=np.uint64)
+    counts = np.zeros(8, dtype=np.uint64)
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+    flags = _capi.OXH_KEYED_DIFF_KEEP_UNCHANGED if keep_unchanged else 0
+    device = d_left_keys.device
+    capacity = nl + nr
+    while True:
+        left = torch.empty(capacity, dtype=torch.int32, device=device)
+        right = torch.empty(capacity, dtype=torch.int32, device=device)
+        status = torch.empty(capacity, dtype=torch.uint8, device=device)
+        _capi.check(_capi.lib().oxh_keyed_diff_device(_handle(ctx), ptr(d_left_keys), nl, ptr(d_right_keys), nr, ptr(d_left_targets),
+                                                      ptr(d_right_targets), ptr(valid[0][0]), ptr(valid[1][0]),
+                                                      bits.ctypes.data_as(_capi._u64p), flags, capacity, ptr(left), ptr(right),
+                                                      ptr(status), counts.ctypes.data_as(_capi._u64p), _stream(stream)),
+                    "oxh_keyed_diff_device")
+        if int(counts[7]) == int(counts[0]):
+            break
+        capacity = int(counts[0])
+    n = int(counts[7])
+    return KeyedDiff(left[:n], right[:n], status[:n], *(int(c) for c in counts[1:7]))
+
+
+def diff_dfs(left: Mapping, right: Mapping, keys: Sequence[str] = (), targets: Sequence[str] = (),
+             ctx: Optional[_capi.Context] = None) -> KeyedDiff:
+    """diffs.rs:881-901 `diff_dfs` up to the classified joined rows: the schema diff by column name, the
+    smart defaults of :938-973 (keys only: targets = the unchanged columns that are not keys; neither:
+    keys = all unchanged columns, targets = the added and removed columns; targets without keys raises),
+    the four `df_hash_rows_on_cols` tables, the validity of keys[0] -- the first key as listed -- from
+    each frame that has that column, and one `keyed_diff_digests` call. Building the output frame
+    (the .left / .right columns, display, the sort on the keys) is the caller's: gather by the returned
+    row indices.
+    The reference keeps the schema diff in HashSets, so the keys[0] of its defaulted keys is whichever
+    column iteration yields first; here it is the first unchanged column in the left frame's order.
+    When the keys select no column of a frame the reference joins null hashes; that case is out of
+    scope here and raises OxenError."""
+    as_col = lambda c: c if isinstance(c, Column) else column(c)  # noqa: E731
+    left = {name: as_col(c) for name, c in left.items()}
+    right = {name: as_col(c) for name, c in right.items()}
+    keys, targets = list(keys), list(targets)
+    added_cols = [c for c in right if c not in left]
+    removed_cols = [c for c in left if c not in right]
+    unchanged_cols = [c for c in left if c in right]
+    if keys and not targets:
+        targets = [c for c in unchanged_cols if c not in keys]
+    elif targets and not keys:
+        raise _capi.OxenError("Must specify at least one key column if specifying target columns.", _capi.OXH_ERR_INVALID)
+    elif not keys:
+        keys, targets = list(unchanged_cols), added_cols + removed_cols
+    left_keys = df_hash_rows_on_cols(left, keys, ctx=ctx) if keys else None
+    right_keys = df_hash_rows_on_cols(right, keys, ctx=ctx) if keys else None
+    if left_keys is None or right_keys is None:
+        raise _capi.OxenError(f"the keys {keys!r} select no column of the {'left' if left_keys is None else 'right'} frame "
+                              "(the reference joins null hashes there; not supported)", _capi.OXH_ERR_INVALID)
+    left_targets = df_hash_rows_on_cols(left, targets, ctx=ctx)
+    right_targets = df_hash_rows_on_cols(right, targets, ctx=ctx)
+    valid = [(f[keys[0]].validity, f[keys[0]].validity_bit) if keys[0] in f else None for f in (left, right)]
+    return keyed_diff_digests(left_keys, right_keys, left_targets, right_targets, valid[0], valid[1], ctx=ctx)
 
 
 def _buffer(buf, dtype) -> Optional[np.ndarray]:
