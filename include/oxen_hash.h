@@ -523,6 +523,67 @@ int oxh_keyed_diff_host(oxh_ctx* ctx, const uint64_t* left_keys, uint64_t nleft,
                         const uint8_t* right_key0_valid, const uint64_t* bit_offsets2, uint32_t flags, uint64_t capacity,
                         uint32_t* left_idx, uint32_t* right_idx, uint8_t* status, uint64_t* counts8);
 
+/* ---------------------------------------------------------------- take: the columns of the joined rows
+ * What join_diff.rs returns is the frame TabularDiff.contents: the key columns coalesced right-then-left
+ * (:95-102), the targets' and display columns' `.left` / `.right` sides, the status. With the pairs of
+ * oxh_keyed_diff_* on the device, those columns are one take (gather by row index) of the two frames'
+ * Arrow columns, null indices included, with an optional fallback source (polars' `coalesce`).
+ *
+ * Sources: nsrc columns, described as oxh_row_hashes_* takes them (kinds, values, offsets, validity,
+ * bit_offsets[2c] / [2c+1]), and src_rows[c], the rows of column c (the two frames differ in height).
+ * Indices: idx0 and idx1, nout_rows u32 each -- the keyed diff's left_idx / right_idx as it writes them;
+ * OXH_TAKE_NULL (the value of OXH_KEYED_DIFF_NONE) = absent; either may be NULL = all absent.
+ * Outputs: nout columns, each four u32 at plan[4 * o]: the source column a, the index array a is read
+ * through (0 or 1), a fallback source column b or OXH_TAKE_NO_COLUMN, the index array b is read through.
+ * Cell (o, i) is the cell of column a at row idx[ia][i] if that index is present and the cell valid; else
+ * the cell of column b at idx[ib][i] if b exists, that index is present and the cell valid; else null. The
+ * output's kind is kinds[a]; kinds[b] must equal it. kinds, bit_offsets, src_rows, plan, value_capacity,
+ * value_bytes, written and the six pointer arrays are HOST arrays in both forms; what the pointers (and
+ * idx0 / idx1) point to is on the device in _device and on the host in _host.
+ *
+ * Output layout, fully defined (Arrow buffers that start at bit / offset 0): out_validity[o] is
+ * ceil(nout_rows / 8) bytes, always written, pad bits 0. Fixed-width values: nout_rows * width bytes, a null
+ * cell's value 0. Booleans: bit-packed, ceil(nout_rows / 8) bytes, null cells and pad bits 0. Byte columns:
+ * nout_rows + 1 offsets of the column's own width (int32 / int64) from 0 in out_offsets[o] and the values
+ * tightly packed; a null cell is an empty span. A BYTES32 output of more than 2^31 - 1 bytes is
+ * OXH_ERR_INVALID (pass the column as BYTES64); nothing is written.
+ *
+ * Capacity (the keyed diff's contract): value_capacity[o] = the room of out_values[o] of a byte column (the
+ * other kinds have the sizes above). value_bytes[o] = what column o's values need, filled on every successful
+ * call. The outputs are written ONLY when every byte column fits, then *written = 1; otherwise *written = 0,
+ * no output array is touched and the call is still OXH_OK: call again with value_bytes. out_values,
+ * out_offsets and out_validity all NULL (value_capacity is then not read) is the sizes-only call.
+ * The device form writes the bit-packed outputs (validity, boolean values) a 64-row word at a time: they
+ * must be 8-byte aligned.
+ *
+ * Both forms block until complete and keep nothing. The host form copies to the device only what the rows
+ * name (as oxh_row_hashes_host) and the two index arrays, runs the device path into a second block once the
+ * sizes are known, and copies the outputs back.
+ * OXH_ERR_INVALID, before OXH_ERR_NODEVICE (there is no CPU path): a NULL kinds, values, offsets, validity,
+ * bit_offsets, src_rows or plan; nsrc == 0 or nout == 0; an unknown kind; a plan entry naming a column that
+ * is not there or an index array above 1; kinds[a] != kinds[b]; nout_rows or a src_rows[c] above 2^32 - 2;
+ * NULL value_bytes or written; a byte source column with rows and no offsets; in the host form, offsets that
+ * are negative or decrease, bytes without values; a column with rows and no values; some but not all of the
+ * three output arrays NULL, outputs without value_capacity, a NULL or (device form) misaligned output of a
+ * column that needs it; then a NULL ctx. nout_rows == 0 is OXH_OK: sizes 0, and out_offsets[o] of a byte
+ * column gets its single 0 when outputs are given. On the device an index that is neither absent nor below
+ * src_rows (the cell is null; nothing is read through it) and a decreasing or negative pair of offsets (a
+ * cell of length 0) make the call return OXH_ERR_INVALID. A failed allocation is OXH_ERR_NOMEM with the
+ * outputs untouched. */
+#define OXH_TAKE_NULL 0xFFFFFFFF
+#define OXH_TAKE_NO_COLUMN 0xFFFFFFFF
+int oxh_take_columns_device(oxh_ctx* ctx, uint32_t nsrc, const uint32_t* kinds, const void* const* d_values,
+                            const void* const* d_offsets, const uint8_t* const* d_validity, const uint64_t* bit_offsets,
+                            const uint64_t* src_rows, uint64_t nout_rows, const uint32_t* d_idx0, const uint32_t* d_idx1,
+                            uint32_t nout, const uint32_t* plan, const uint64_t* value_capacity, void* const* d_out_values,
+                            void* const* d_out_offsets, uint8_t* const* d_out_validity, uint64_t* value_bytes, uint32_t* written,
+                            void* stream);
+int oxh_take_columns_host(oxh_ctx* ctx, uint32_t nsrc, const uint32_t* kinds, const void* const* values,
+                          const void* const* offsets, const uint8_t* const* validity, const uint64_t* bit_offsets,
+                          const uint64_t* src_rows, uint64_t nout_rows, const uint32_t* idx0, const uint32_t* idx1, uint32_t nout,
+                          const uint32_t* plan, const uint64_t* value_capacity, void* const* out_values, void* const* out_offsets,
+                          uint8_t* const* out_validity, uint64_t* value_bytes, uint32_t* written);
+
 /* ---------------------------------------------------------------- K2: merkle parent nodes */
 /* get_combined_hash (hasher.rs:67-80) x n on the device:
  * XXH3-128(content.to_le_bytes() || metadata.to_le_bytes()), inputs as (lo, hi) pairs. */

@@ -12,7 +12,8 @@ Modules:
                chunk overlap between the versions of a file (chunk_overlap, OxenChunker)
   tabular   -- row hashes of a data frame from its columns and the row set-diff (`oxen diff` on
                tabular files: df_hash_rows, df_hash_rows_on_cols, compute_new_row_indices), and the
-               keyed diff of two frames (keyed_diff_digests, diff_dfs)
+               keyed diff of two frames (keyed_diff_digests, diff_dfs) with its contents: the take of
+               the joined rows' columns on the device (take, diff_contents, diff_dfs_contents)
   procpool  -- file hashing sharded over reader processes (the open/close floor is per process)
   shard     -- multi-GPU sharding and the RCCL digest gather
   device    -- device-resident (HBM) batch entry points over torch buffers
@@ -27,7 +28,8 @@ __version__ = "0.1.0"
 _FROM_DEDUP = ("ChunkOverlap", "chunk_overlap", "chunk_overlap_device", "names_to_digests", "count_commit_overlap",
                "OxenChunker")
 # and from oxen_amd.tabular
-_FROM_TABULAR = ("KeyedDiff", "STATUS_NAMES", "keyed_diff_digests", "keyed_diff_digests_device", "diff_dfs")
+_FROM_TABULAR = ("KeyedDiff", "STATUS_NAMES", "keyed_diff_digests", "keyed_diff_digests_device", "diff_dfs",
+                 "take", "take_device", "diff_contents", "diff_dfs_contents", "output_columns", "columns_to_arrow")
 
 
 def __getattr__(name):

@@ -44,6 +44,8 @@ OXH_DIFF_UNCHANGED = 0
 OXH_DIFF_ADDED = 1
 OXH_DIFF_REMOVED = 2
 OXH_DIFF_MODIFIED = 3
+OXH_TAKE_NULL = 0xFFFFFFFF        # an absent index (the value of OXH_KEYED_DIFF_NONE)
+OXH_TAKE_NO_COLUMN = 0xFFFFFFFF   # no fallback source column
 
 _u64 = ctypes.c_uint64
 _u32 = ctypes.c_uint32
@@ -134,6 +136,14 @@ SIGNATURES = {
     "oxh_keyed_diff_device": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _u64p, _u32, _u64, _vp, _vp, _vp, _u64p,
                                      _vp]),
     "oxh_keyed_diff_host": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _u64p, _u32, _u64, _vp, _vp, _vp, _u64p]),
+    "oxh_take_columns_device": (_int, [_vp, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                       ctypes.POINTER(_vp), _u64p, _u64p, _u64, _vp, _vp, _u32, ctypes.POINTER(_u32), _u64p,
+                                       ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u64p,
+                                       ctypes.POINTER(_u32), _vp]),
+    "oxh_take_columns_host": (_int, [_vp, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                     ctypes.POINTER(_vp), _u64p, _u64p, _u64, _vp, _vp, _u32, ctypes.POINTER(_u32), _u64p,
+                                     ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u64p,
+                                     ctypes.POINTER(_u32)]),
     "oxh_comm_check": (_int, [_int]),
     "oxh_ctx_counters": (_int, [_vp, _u64p, _int]),
     "oxh_comm_unique_id": (_int, [ctypes.c_char_p]),

@@ -18,6 +18,9 @@
 //   keyed_diff.hip     the keyed tabular diff over four digest tables (oxh_keyed_diff_*): join on the key
 //                      digests through the index's public entries, status of every joined row; and the
 //                      device-wide exclusive scan it orders its output with (exclusive_scan_u32)
+//   take_columns.hip   the columns of the joined rows (oxh_take_columns_*): a take of Arrow columns by the keyed
+//                      diff's row indices, with a fallback source (coalesce); columns.hpp holds what it shares
+//                      with row_hash.hip (the column descriptor, the cell of a row, the host forms' staging)
 // There is no CPU hashing path: every digest this library returns was computed on the GPU.
 #pragma once
 
@@ -128,6 +131,7 @@ int launch_lane(const uint8_t* arena, const uint64_t* offs, const uint64_t* lens
 namespace oxh {
 // d_out[i] = d_in[0] + ... + d_in[i-1] over n u32, as u64, enqueued on `st` (three launches; no workgroup
 // waits for another). d_sums: scan_tiles(n) + 1 words of device scratch; the last receives the total.
+// Callers: the keyed diff's pair offsets, the take's byte-column offsets (take_columns.hip).
 uint64_t scan_tiles(uint64_t n);
 int exclusive_scan_u32(const uint32_t* d_in, uint64_t n, uint64_t* d_out, unsigned long long* d_sums, hipStream_t st);
 }  // namespace oxh

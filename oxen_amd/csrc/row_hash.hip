@@ -31,56 +31,16 @@
 // every digest an id, its first ordinal; mark takes, per id and side, the largest row index (atomic max),
 // flag sets a row's byte when it is that index and the other side has none for the id.
 #include "capi_internal.hpp"
+#include "columns.hpp"
 
 using namespace oxh::capi;
 
 namespace oxh {
 
-struct RowCol {
-    const uint8_t* values;
-    const uint8_t* offsets;   // byte columns: nrows + 1 int32 / int64
-    const uint8_t* validity;  // NULL: no nulls
-    uint64_t vbit;            // OXH_COL_BOOL: the bit of row 0 in values
-    uint64_t nbit;            // the bit of row 0 in validity
-    uint32_t kind, pad;
-};
-
 constexpr uint32_t kRowShortMax = 240;  // the XXH3 short paths (xxh3_lane_short)
-constexpr unsigned long long kRowErrOffsets = 1, kRowErrValues = 2, kRowErrPlan = 4;
+constexpr unsigned long long kRowErrPlan = 4;  // beside kRowErrOffsets, kRowErrValues (columns.hpp)
 // ctrl words of one call
 constexpr int kCtrlMax = 0, kCtrlLong = 1, kCtrlLongBytes = 2, kCtrlErr = 3, kCtrlCursor = 4 /* and 5 */, kCtrlWords = 8;
-
-__device__ __forceinline__ bool row_bit(const uint8_t* p, uint64_t bit) { return (p[bit >> 3] >> (bit & 7)) & 1; }
-
-// Length of row r's cell in column c; byte columns: `start` = where its bytes begin in c.values.
-__device__ __forceinline__ uint64_t row_cell(const RowCol& c, uint64_t r, uint64_t& start, unsigned long long& bad) {
-    if (c.validity && !row_bit(c.validity, c.nbit + r)) return 0;
-    switch (c.kind) {
-        case OXH_COL_FIXED1:
-        case OXH_COL_BOOL: return 1;
-        case OXH_COL_FIXED4: return 4;
-        case OXH_COL_FIXED8: return 8;
-        default: break;
-    }
-    int64_t s, e;
-    if (c.kind == OXH_COL_BYTES32) {
-        s = (int32_t)ld32u(c.offsets + 4 * r);
-        e = (int32_t)ld32u(c.offsets + 4 * r + 4);
-    } else {
-        s = (int64_t)ld64u(c.offsets + 8 * r);
-        e = (int64_t)ld64u(c.offsets + 8 * r + 8);
-    }
-    if (s < 0 || e < s) {  // never a read through such a pair
-        bad |= kRowErrOffsets;
-        return 0;
-    }
-    if (e > s && !c.values) {
-        bad |= kRowErrValues;
-        return 0;
-    }
-    start = (uint64_t)s;
-    return (uint64_t)(e - s);
-}
 
 __device__ __forceinline__ uint64_t row_length(const RowCol* __restrict__ cols, uint32_t ncols, uint64_t r, unsigned long long& bad) {
     uint64_t len = 0, start = 0;
@@ -347,16 +307,10 @@ constexpr uint64_t kMaxDiffRows = 0xFFFFFFFFull;   // the reference's Vec<u32>
 constexpr uint64_t kLaunchRows = 1ull << 38;       // rows of one row-per-lane launch: the grid fits 31 bits
 constexpr int kVariantGatherAll = 9001;            // oxh_set_kernel_variant: every row through the arena (tools/row_hash_probe.py)
 
-bool is_bytes(uint32_t kind) { return kind == OXH_COL_BYTES32 || kind == OXH_COL_BYTES64; }
-bool known_kind(uint32_t kind) {
-    return kind == OXH_COL_FIXED1 || kind == OXH_COL_FIXED4 || kind == OXH_COL_FIXED8 || kind == OXH_COL_BOOL || is_bytes(kind);
-}
+using oxh::cols::is_bytes;
+using oxh::cols::known_kind;
 unsigned grid_for(uint64_t n) { return (unsigned)((n + 255) / 256); }
 unsigned stride_grid(uint64_t n) { return (unsigned)std::min<uint64_t>((n + 255) / 256, 2048); }  // as the index's resolve
-
-int64_t offset_at(const void* offsets, uint32_t kind, uint64_t r) {
-    return kind == OXH_COL_BYTES32 ? (int64_t)((const int32_t*)offsets)[r] : ((const int64_t*)offsets)[r];
-}
 
 // What both row-hash forms check before they need a device. `done`: nrows == 0, nothing to do.
 int row_arguments(uint64_t nrows, uint32_t ncols, const uint32_t* kinds, const void* const* values, const void* const* offsets,
@@ -374,22 +328,9 @@ int row_arguments(uint64_t nrows, uint32_t ncols, const uint32_t* kinds, const v
         return OXH_OK;
     }
     for (uint32_t c = 0; c < ncols; ++c) {
-        const std::string col = "row hashes: column " + std::to_string(c);
-        if (is_bytes(kinds[c])) {
-            if (!offsets[c]) return fail(OXH_ERR_INVALID, col + " is a byte column without offsets");
-            if (!host) continue;  // the spans are on the device: the kernels check them
-            int64_t before = offset_at(offsets[c], kinds[c], 0);
-            if (before < 0) return fail(OXH_ERR_INVALID, col + ": offsets[0] is negative");
-            const int64_t lo = before;
-            for (uint64_t r = 1; r <= nrows; ++r) {
-                const int64_t at = offset_at(offsets[c], kinds[c], r);
-                if (at < before) return fail(OXH_ERR_INVALID, col + ": offsets decrease at row " + std::to_string(r - 1));
-                before = at;
-            }
-            if (!values[c] && before > lo) return fail(OXH_ERR_INVALID, col + " has bytes but no values");
-        } else if (!values[c]) {
-            return fail(OXH_ERR_INVALID, col + " has no values");
-        }
+        const std::string what = oxh::cols::column_error("row hashes: column " + std::to_string(c), kinds[c], values[c], offsets[c],
+                                                         nrows, host);
+        if (!what.empty()) return fail(OXH_ERR_INVALID, what);
     }
     if (!out) return fail(OXH_ERR_INVALID, "row hashes: out is NULL");
     return OXH_OK;
@@ -402,23 +343,6 @@ int device_enter(oxh_ctx* ctx) {
     HIP_TRY(hipSetDevice(ctx->device));
     return OXH_OK;
 }
-
-// A call's small block: the column descriptors and the control words, on the device and pinned.
-struct RowCall {
-    uint8_t *d = nullptr, *h = nullptr;
-    ~RowCall() {
-        if (d) (void)hipFree(d);
-        if (h) (void)hipHostFree(h);
-    }
-    int make(size_t bytes, const char* what) {
-        if (hipMalloc(&d, bytes) != hipSuccess || hipHostMalloc(&h, bytes, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(OXH_ERR_NOMEM, std::string(what) + ": control block");
-        }
-        memset(h, 0, bytes);
-        return OXH_OK;
-    }
-};
 
 int row_error(unsigned long long e) {
     if (!e) return OXH_OK;
@@ -435,7 +359,7 @@ int row_hashes_run(uint64_t nrows, uint32_t ncols, const uint32_t* kinds, const 
     const bool gather_all = g_variant.load() == kVariantGatherAll;
     const uint32_t short_max = gather_all ? 0 : oxh::kRowShortMax;
     const size_t ctrl_at = (ncols * sizeof(RowCol) + 63) & ~(size_t)63, bytes = ctrl_at + oxh::kCtrlWords * 8;
-    RowCall call;
+    CallBlock call;
     int rc = call.make(bytes, "row hashes");
     if (rc) return rc;
     RowCol* h_cols = (RowCol*)call.h;
@@ -566,11 +490,6 @@ int row_diff_run(oxh_ctx* ctx, const uint64_t* d_base, uint64_t nbase, const uin
     return release(rc);
 }
 
-struct Piece {
-    const void* src;
-    uint64_t bytes, at;
-};
-
 }  // namespace
 
 extern "C" {
@@ -595,49 +514,27 @@ int oxh_row_hashes_host(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const uint
     // One device block: the digests, then for every column only what its rows name -- nrows values (the
     // bytes that hold its bits for a boolean), the nrows + 1 offsets and the span [offsets[0],
     // offsets[nrows]) of a byte column, the bytes that hold its validity bits -- each 16-B aligned.
-    std::vector<Piece> pieces;
+    oxh::cols::Staging plan;
+    plan.total = nrows * 16;
+    std::vector<oxh::cols::Staged> staged(ncols);
     std::vector<const void*> d_values(ncols, nullptr), d_offsets(ncols, nullptr);
     std::vector<const uint8_t*> d_validity(ncols, nullptr);
-    std::vector<uint64_t> bits(2 * (size_t)ncols, 0), span_lo(ncols, 0);
-    std::vector<int64_t> where(3 * (size_t)ncols, -1);  // piece of values / offsets / validity
-    uint64_t total = nrows * 16;
-    auto add = [&](const void* src, uint64_t bytes) {
-        pieces.push_back({src, bytes, total});
-        total += (bytes + 15) & ~15ull;
-        return (int64_t)pieces.size() - 1;
-    };
-    auto add_bits = [&](const uint8_t* src, uint64_t bit0, uint64_t& bit_out) {
-        bit_out = bit0 & 7;
-        return add(src + (bit0 >> 3), (bit_out + nrows + 7) >> 3);
-    };
-    for (uint32_t c = 0; c < ncols; ++c) {
-        switch (kinds[c]) {
-            case OXH_COL_FIXED1:
-            case OXH_COL_FIXED4:
-            case OXH_COL_FIXED8: where[3 * c] = add(values[c], nrows * (kinds[c] == OXH_COL_FIXED1 ? 1 : kinds[c])); break;
-            case OXH_COL_BOOL: where[3 * c] = add_bits((const uint8_t*)values[c], bit_offsets[2 * c], bits[2 * c]); break;
-            default: {
-                const uint64_t lo = (uint64_t)offset_at(offsets[c], kinds[c], 0), hi = (uint64_t)offset_at(offsets[c], kinds[c], nrows);
-                span_lo[c] = lo;
-                where[3 * c + 1] = add(offsets[c], (nrows + 1) * (kinds[c] == OXH_COL_BYTES32 ? 4 : 8));
-                if (hi > lo) where[3 * c] = add((const uint8_t*)values[c] + lo, hi - lo);
-            }
-        }
-        if (validity[c]) where[3 * c + 2] = add_bits(validity[c], bit_offsets[2 * c + 1], bits[2 * c + 1]);
-    }
+    std::vector<uint64_t> bits(2 * (size_t)ncols, 0);
+    for (uint32_t c = 0; c < ncols; ++c)
+        staged[c] = plan.add_column(kinds[c], values[c], offsets[c], validity[c], bit_offsets[2 * c], bit_offsets[2 * c + 1], nrows);
+    const uint64_t total = plan.total;
     uint8_t* d_block = nullptr;
     if (hipMalloc(&d_block, total) != hipSuccess) {
         (void)hipGetLastError();
         return fail(OXH_ERR_NOMEM, "row hashes: " + std::to_string(total) + " B for the columns on the device");
     }
     rc = [&]() -> int {
-        for (const Piece& p : pieces) HIP_TRY(hipMemcpyAsync(d_block + p.at, p.src, p.bytes, hipMemcpyHostToDevice, st));
+        for (const oxh::cols::Piece& p : plan.pieces) HIP_TRY(hipMemcpyAsync(d_block + p.at, p.src, p.bytes, hipMemcpyHostToDevice, st));
         for (uint32_t c = 0; c < ncols; ++c) {
-            // a byte column's values pointer is where byte 0 of the caller's buffer would be: the kernels
-            // add the offsets as they are, and only [offsets[0], offsets[nrows]) is ever read
-            if (where[3 * c] >= 0) d_values[c] = (const void*)((uintptr_t)(d_block + pieces[where[3 * c]].at) - (uintptr_t)span_lo[c]);
-            if (where[3 * c + 1] >= 0) d_offsets[c] = d_block + pieces[where[3 * c + 1]].at;
-            if (where[3 * c + 2] >= 0) d_validity[c] = d_block + pieces[where[3 * c + 2]].at;
+            d_values[c] = plan.values_at(d_block, staged[c]);
+            d_offsets[c] = plan.offsets_at(d_block, staged[c]);
+            d_validity[c] = plan.validity_at(d_block, staged[c]);
+            bits[2 * c] = staged[c].vbit, bits[2 * c + 1] = staged[c].nbit;
         }
         int r = row_hashes_run(nrows, ncols, kinds, d_values.data(), d_offsets.data(), d_validity.data(), bits.data(),
                                (uint64_t*)d_block, st);

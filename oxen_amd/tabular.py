@@ -10,6 +10,10 @@ row on the device straight from the columns; `oxh_row_diff_*` answers the set qu
 repositories/diffs/join_diff.rs): the full join of the two frames on their key hashes, every joined row
 labelled added / removed / modified / unchanged, and the summary counts -- `keyed_diff_digests`, `diff_dfs`.
 
+`oxh_take_columns_*` builds what that diff returns, `TabularDiff.contents`: a take of both frames' columns by
+the joined rows' indices, null indices and a fallback source (the keys' coalesce) included -- `take`,
+`take_device`, `diff_contents`, `diff_dfs_contents`, and `columns_to_arrow` back to pyarrow.
+
 A frame is an ordered mapping from column name to `Column`. A row's bytes are, over the columns in the
 frame's order: nothing for a null, the raw little-endian bytes of Int8 / Int32 / Float32 / Int64 /
 Float64 / Datetime(ms), one byte 0 or 1 for a boolean, the UTF-8 bytes of a string. Every other dtype
@@ -361,32 +365,44 @@ def keyed_diff_digests_device(d_left_keys, d_right_keys, d_left_targets=None, d_
     return KeyedDiff(left[:n], right[:n], status[:n], *(int(c) for c in counts[1:7]))
 
 
-def diff_dfs(left: Mapping, right: Mapping, keys: Sequence[str] = (), targets: Sequence[str] = (),
-             ctx: Optional[_capi.Context] = None) -> KeyedDiff:
-    """diffs.rs:881-901 `diff_dfs` up to the classified joined rows: the schema diff by column name, the
-    smart defaults of :938-973 (keys only: targets = the unchanged columns that are not keys; neither:
-    keys = all unchanged columns, targets = the added and removed columns; targets without keys raises),
-    the four `df_hash_rows_on_cols` tables, the validity of keys[0] -- the first key as listed -- from
-    each frame that has that column, and one `keyed_diff_digests` call. Building the output frame
-    (the .left / .right columns, display, the sort on the keys) is the caller's: gather by the returned
-    row indices.
-    The reference keeps the schema diff in HashSets, so the keys[0] of its defaulted keys is whichever
-    column iteration yields first; here it is the first unchanged column in the left frame's order.
-    When the keys select no column of a frame the reference joins null hashes; that case is out of
-    scope here and raises OxenError."""
-    as_col = lambda c: c if isinstance(c, Column) else column(c)  # noqa: E731
-    left = {name: as_col(c) for name, c in left.items()}
-    right = {name: as_col(c) for name, c in right.items()}
+def _as_frame(frame: Mapping) -> dict:
+    return {name: c if isinstance(c, Column) else column(c) for name, c in frame.items()}
+
+
+def _schema_diff(left: Mapping, right: Mapping):
+    """diffs.rs:903-936 by column name: (added, removed, unchanged), each in its frame's order (the
+    reference keeps them in HashSets)."""
+    return [c for c in right if c not in left], [c for c in left if c not in right], [c for c in left if c in right]
+
+
+def _keys_targets_smart_defaults(left: Mapping, right: Mapping, keys, targets):
+    """diffs.rs:938-973."""
     keys, targets = list(keys), list(targets)
-    added_cols = [c for c in right if c not in left]
-    removed_cols = [c for c in left if c not in right]
-    unchanged_cols = [c for c in left if c in right]
+    added_cols, removed_cols, unchanged_cols = _schema_diff(left, right)
     if keys and not targets:
         targets = [c for c in unchanged_cols if c not in keys]
     elif targets and not keys:
         raise _capi.OxenError("Must specify at least one key column if specifying target columns.", _capi.OXH_ERR_INVALID)
     elif not keys:
         keys, targets = list(unchanged_cols), added_cols + removed_cols
+    return keys, targets
+
+
+def diff_dfs(left: Mapping, right: Mapping, keys: Sequence[str] = (), targets: Sequence[str] = (),
+             ctx: Optional[_capi.Context] = None) -> KeyedDiff:
+    """diffs.rs:881-901 `diff_dfs` up to the classified joined rows: the schema diff by column name, the
+    smart defaults of :938-973 (keys only: targets = the unchanged columns that are not keys; neither:
+    keys = all unchanged columns, targets = the added and removed columns; targets without keys raises),
+    the four `df_hash_rows_on_cols` tables, the validity of keys[0] -- the first key as listed -- from
+    each frame that has that column, and one `keyed_diff_digests` call. The output frame (the coalesced
+    keys, the .left / .right columns, display, the status) is `diff_contents` over the returned row
+    indices; `diff_dfs_contents` does both.
+    The reference keeps the schema diff in HashSets, so the keys[0] of its defaulted keys is whichever
+    column iteration yields first; here it is the first unchanged column in the left frame's order.
+    When the keys select no column of a frame the reference joins null hashes; that case is out of
+    scope here and raises OxenError."""
+    left, right = _as_frame(left), _as_frame(right)
+    keys, targets = _keys_targets_smart_defaults(left, right, keys, targets)
     left_keys = df_hash_rows_on_cols(left, keys, ctx=ctx) if keys else None
     right_keys = df_hash_rows_on_cols(right, keys, ctx=ctx) if keys else None
     if left_keys is None or right_keys is None:
@@ -396,6 +412,252 @@ def diff_dfs(left: Mapping, right: Mapping, keys: Sequence[str] = (), targets: S
     right_targets = df_hash_rows_on_cols(right, targets, ctx=ctx)
     valid = [(f[keys[0]].validity, f[keys[0]].validity_bit) if keys[0] in f else None for f in (left, right)]
     return keyed_diff_digests(left_keys, right_keys, left_targets, right_targets, valid[0], valid[1], ctx=ctx)
+
+
+# ---------------------------------------------------------------- take: the columns of the joined rows
+STATUS_COLUMN = "_oxen_diff_status"   # constants.rs DIFF_STATUS_COL
+
+
+def _take_tables(cols, plan):
+    """(rows, plan words, the plan as a list, kind of each output column) of a take over `cols`. plan: one
+    (a, ia, b, ib) per output column, b None for no fallback; None = a plain take of every column
+    through idx0."""
+    if plan is None:
+        plan = [(c, 0, None, 0) for c in range(len(cols))]
+    plan = [tuple(p) for p in plan]
+    words = []
+    for a, ia, b, ib in plan:
+        if not 0 <= int(a) < len(cols) or (b is not None and not 0 <= int(b) < len(cols)):
+            raise _capi.OxenError(f"a plan entry names column {a if b is None else (a, b)} of {len(cols)}", _capi.OXH_ERR_INVALID)
+        words += [int(a), int(ia), _capi.OXH_TAKE_NO_COLUMN if b is None else int(b), int(ib)]
+    rows = (ctypes.c_uint64 * max(len(cols), 1))(*[int(c.nrows) for c in cols])
+    return rows, (ctypes.c_uint32 * max(len(words), 1))(*words), plan, [int(cols[p[0]].kind) for p in plan]
+
+
+def _pointers(addresses):
+    return (ctypes.c_void_p * max(len(addresses), 1))(*addresses)
+
+
+def _take_sizes(kinds, nout_rows, value_bytes):
+    """Per output column the bytes of (values, offsets, validity)."""
+    bitmap = (nout_rows + 7) // 8
+    return [(int(value_bytes[o]), (nout_rows + 1) * (4 if k == OXH_COL_BYTES32 else 8) if k in _BYTES else 0, bitmap)
+            for o, k in enumerate(kinds)]
+
+
+def _host_index(a) -> Optional[np.ndarray]:
+    """An index array as the ABI takes it: u32, OXH_TAKE_NULL = absent. Signed arrays (KeyedDiff's
+    left_rows / right_rows) say absent with a negative value."""
+    if a is None:
+        return None
+    a = np.asarray(a)
+    if a.dtype.kind == "i":
+        a = np.where(a < 0, _capi.OXH_TAKE_NULL, a)
+    return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+def take(columns: Sequence, idx0, idx1=None, plan=None, ctx: Optional[_capi.Context] = None) -> list:
+    """oxh_take_columns_host: the take (gather by row index) of `Column`s in host memory. idx0 / idx1: row
+    indices, u32 with OXH_TAKE_NULL or signed with a negative value for an absent row (a null cell);
+    either may be None (all absent). plan: one (a, ia, b, ib) per output column -- the cell of column a at
+    idx[ia][i] when that row is present and the cell valid, else the cell of column b (None: no fallback,
+    else a column of the same kind) at idx[ib][i], else null: polars' `coalesce`. None: every column through
+    idx0. The columns may differ in height. Returns the output `Column`s over fresh numpy buffers that
+    start at bit / offset 0, validity always present, null cells and pad bits 0: the sizes-only call, the
+    allocation, then the call that writes."""
+    cols = [c if isinstance(c, Column) else column(c) for c in columns]
+    i0, i1 = _host_index(idx0), _host_index(idx1)
+    if i0 is None and i1 is None:
+        raise _capi.OxenError("take needs at least one index array", _capi.OXH_ERR_INVALID)
+    if i0 is not None and i1 is not None and i0.shape != i1.shape:
+        raise _capi.OxenError("the two index arrays have one length", _capi.OXH_ERR_INVALID)
+    nout_rows = int((i0 if i0 is not None else i1).size)
+    keep = []
+
+    def ptr(a):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a)
+        keep.append(a)
+        return a.ctypes.data if a.size else None
+
+    rows, words, plan, kinds = _take_tables(cols, plan)
+    nout = len(plan)
+    tables = _tables(cols, ptr)
+    value_bytes = (ctypes.c_uint64 * max(nout, 1))()
+    written = ctypes.c_uint32(0)
+    handle, L = _handle(ctx), _capi.lib()
+    head = (handle, len(cols), *tables, rows, nout_rows, ptr(i0), ptr(i1), nout, words)
+    _capi.check(L.oxh_take_columns_host(*head, None, None, None, None, value_bytes, ctypes.byref(written)), "oxh_take_columns_host")
+    outs = [[np.zeros(size, dtype=np.uint8) for size in sizes] for sizes in _take_sizes(kinds, nout_rows, value_bytes)]
+    capacity = (ctypes.c_uint64 * max(nout, 1))(*[o[0].size for o in outs])
+    arrays = [_pointers([o[k].ctypes.data if o[k].size else None for o in outs]) for k in range(3)]
+    _capi.check(L.oxh_take_columns_host(*head, capacity, *arrays, value_bytes, ctypes.byref(written)), "oxh_take_columns_host")
+    if nout and not written.value:
+        raise _capi.OxenError("oxh_take_columns_host: the columns changed between the two calls", _capi.OXH_ERR_INVALID)
+    result = []
+    for (a, *_), kind, (values, offsets, validity) in zip(plan, kinds, outs):
+        src = cols[a].values
+        if kind in _WIDTH and getattr(src, "dtype", None) is not None and src.dtype.itemsize == _WIDTH[kind]:
+            values = values.view(src.dtype)   # a Column carries a width; the source's dtype is the likeliest reading
+        offs = offsets.view(np.int32 if kind == OXH_COL_BYTES32 else np.int64) if kind in _BYTES else None
+        result.append(Column(kind, nout_rows, values, offs, validity, 0, 0))
+    return result
+
+
+def take_device(columns: Sequence[Column], idx0, idx1=None, plan=None, stream=None, ctx: Optional[_capi.Context] = None) -> list:
+    """oxh_take_columns_device: `take` over `Column`s whose values / offsets / validity are torch tensors
+    on the device, with idx0 / idx1 as 32-bit device tensors holding the u32 words (the left_rows /
+    right_rows of `keyed_diff_digests_device` as they are: -1 is OXH_TAKE_NULL). Nothing crosses the link
+    but the sizes. Returns `Column`s over fresh device tensors. Blocks."""
+    import torch
+
+    from .device import _require_cuda, _stream
+
+    cols = list(columns)
+    tensors = [t for c in cols for t in (c.values, c.offsets, c.validity) if t is not None] + [t for t in (idx0, idx1) if t is not None]
+    _require_cuda(*tensors)
+    if any(not t.is_contiguous() for t in tensors):
+        raise _capi.OxenError("column and index tensors must be contiguous", _capi.OXH_ERR_INVALID)
+    if idx0 is None and idx1 is None:
+        raise _capi.OxenError("take needs at least one index array", _capi.OXH_ERR_INVALID)
+    for t in (idx0, idx1):
+        if t is not None and (t.element_size() != 4 or t.dim() != 1):
+            raise _capi.OxenError("index arrays are one-dimensional 32-bit tensors", _capi.OXH_ERR_INVALID)
+    if idx0 is not None and idx1 is not None and idx0.numel() != idx1.numel():
+        raise _capi.OxenError("the two index arrays have one length", _capi.OXH_ERR_INVALID)
+    first = idx0 if idx0 is not None else idx1
+    nout_rows, device = int(first.numel()), first.device
+    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()  # noqa: E731
+    rows, words, plan, kinds = _take_tables(cols, plan)
+    nout = len(plan)
+    tables = _tables(cols, ptr)
+    value_bytes = (ctypes.c_uint64 * max(nout, 1))()
+    written = ctypes.c_uint32(0)
+    handle, L, st = _handle(ctx), _capi.lib(), _stream(stream)
+    head = (handle, len(cols), *tables, rows, nout_rows, ptr(idx0), ptr(idx1), nout, words)
+    _capi.check(L.oxh_take_columns_device(*head, None, None, None, None, value_bytes, ctypes.byref(written), st),
+                "oxh_take_columns_device")
+    # fresh allocations are aligned far beyond the 8 bytes the bit-packed outputs need; not zero-filled: the
+    # call writes every byte, and a fill queued on torch's stream is not ordered with the call's stream
+    outs = [[torch.empty(size, dtype=torch.uint8, device=device) for size in sizes]
+            for sizes in _take_sizes(kinds, nout_rows, value_bytes)]
+    capacity = (ctypes.c_uint64 * max(nout, 1))(*[o[0].numel() for o in outs])
+    arrays = [_pointers([ptr(o[k]) for o in outs]) for k in range(3)]
+    _capi.check(L.oxh_take_columns_device(*head, capacity, *arrays, value_bytes, ctypes.byref(written), st),
+                "oxh_take_columns_device")
+    if nout and not written.value:
+        raise _capi.OxenError("oxh_take_columns_device: the columns changed between the two calls", _capi.OXH_ERR_INVALID)
+    result = []
+    for (a, *_), kind, (values, offsets, validity) in zip(plan, kinds, outs):
+        src = cols[a].values
+        if kind in _WIDTH and src is not None and src.element_size() == _WIDTH[kind]:
+            values = values.view(src.dtype)
+        offs = offsets.view(torch.int32 if kind == OXH_COL_BYTES32 else torch.int64) if kind in _BYTES else None
+        result.append(Column(kind, nout_rows, values, offs, validity, 0, 0))
+    return result
+
+
+def _trim_suffix(name: str, suffix: str) -> str:
+    while name.endswith(suffix):   # str::trim_end_matches strips every repetition
+        name = name[:-len(suffix)]
+    return name
+
+
+def output_columns(left: Mapping, right: Mapping, keys: Sequence[str], targets: Sequence[str], display: Sequence[str] = ()) -> list:
+    """The columns of TabularDiff.contents and where each comes from: (name, (side, column), fallback)
+    with side "left" / "right" and fallback None or another (side, column); the status column is not in
+    the list. join_diff.rs:204-278 `get_output_columns` restated as written, with diffs.rs:975-1007
+    `get_display_smart_defaults` for an empty display. keys and targets are the resolved ones (after
+    `get_keys_targets_smart_defaults`).
+
+    `order_columns_by_schema` keeps only the names that are literally columns of the RIGHT frame and
+    sorts them by its schema. So a key or target the right frame lacks is dropped, and a display name
+    such as "note.left" -- every name the smart defaults make has such a suffix -- survives only when the
+    right frame has a column of that literal name. That is the reference's behaviour and is kept.
+    A key is `coalesce(key.right, key.left)` (:95-102); where the left frame lacks the key it is the
+    right column alone."""
+    added, removed, unchanged = _schema_diff(left, right)
+    keys, targets, display = list(keys), list(targets), list(display)
+    if not display:
+        for c in unchanged:
+            if c not in keys and c not in targets:
+                display += [c + ".left", c + ".right"]
+        display += [c + ".left" for c in removed if c not in keys and c not in targets]
+        display += [c + ".right" for c in added if c not in keys and c not in targets]
+    position = {name: i for i, name in enumerate(right)}
+    ordered = lambda names: sorted((n for n in names if n in position), key=position.get)  # noqa: E731  (a stable sort, as sort_by_key)
+    out = []
+    for key in ordered(keys):
+        out.append((key, ("right", key), ("left", key) if key in left else None))
+    for target in ordered(targets):
+        if target in added:
+            out.append((target + ".right", ("right", target), None))
+        elif target in removed:
+            out.append((target + ".left", ("left", target), None))
+        else:
+            out.append((target + ".left", ("left", target), None))
+            out.append((target + ".right", ("right", target), None))
+    for col in ordered(display):
+        if col.endswith(".left"):
+            stripped = _trim_suffix(col, ".left")
+            if stripped in removed or stripped in unchanged:
+                out.append((col, ("left", stripped), None))
+        if col.endswith(".right"):
+            stripped = _trim_suffix(col, ".right")
+            if stripped in added or stripped in unchanged:
+                out.append((col, ("right", stripped), None))
+    return out
+
+
+def diff_contents(left: Mapping, right: Mapping, diff: KeyedDiff, keys: Sequence[str], targets: Sequence[str],
+                  display: Sequence[str] = (), ctx: Optional[_capi.Context] = None) -> dict:
+    """TabularDiff.contents of join_diff.rs `diff` after `diff_dfs`, as an ordered {name: Column}: the
+    columns `output_columns` lists -- one `take` over both frames' columns through diff.left_rows /
+    diff.right_rows, the keys coalesced right-then-left -- and `_oxen_diff_status`, a string column built
+    from STATUS_NAMES on the host. keys / targets: the resolved ones (`diff_dfs_contents` passes them).
+    The rows come in the keyed diff's canonical order. `sort_df_on_keys` (:146-163) is NOT applied: a Column
+    carries a width, not a dtype, and the reference's sort is unstable, so its row order is no parity
+    target; sort the result on the key columns where that order is wanted."""
+    left, right = _as_frame(left), _as_frame(right)
+    wanted = output_columns(left, right, keys, targets, display)
+    sources = list(left.values()) + list(right.values())
+    where = {("left", name): i for i, name in enumerate(left)}
+    where.update({("right", name): len(left) + i for i, name in enumerate(right)})
+    side = {"left": 0, "right": 1}
+    plan = [(where[a], side[a[0]], None if b is None else where[b], 0 if b is None else side[b[0]]) for _, a, b in wanted]
+    left_rows, right_rows = np.asarray(diff.left_rows), np.asarray(diff.right_rows)
+    taken = take(sources, left_rows, right_rows, plan, ctx=ctx) if plan else []
+    contents = {name: col for (name, _, _), col in zip(wanted, taken)}
+    contents[STATUS_COLUMN] = _status_column(np.asarray(diff.status))
+    return contents
+
+
+def _status_column(status: np.ndarray) -> Column:
+    """The string column of STATUS_NAMES[status[i]], built without a Python loop over the rows."""
+    names = [name.encode() for name in STATUS_NAMES]
+    table = np.frombuffer(b"".join(names), dtype=np.uint8)
+    name_len = np.array([len(name) for name in names], dtype=np.int64)
+    name_at = np.cumsum(name_len) - name_len
+    s = status.astype(np.int64)
+    lens = name_len[s]
+    offsets = np.zeros(s.size + 1, dtype=np.int64)
+    np.cumsum(lens, out=offsets[1:])
+    within = np.arange(int(offsets[-1]), dtype=np.int64) - np.repeat(offsets[:-1], lens)
+    values = table[np.repeat(name_at[s], lens) + within]
+    wide = int(offsets[-1]) > np.iinfo(np.int32).max
+    return Column(OXH_COL_BYTES64 if wide else OXH_COL_BYTES32, s.size, values, offsets if wide else offsets.astype(np.int32))
+
+
+def diff_dfs_contents(left: Mapping, right: Mapping, keys: Sequence[str] = (), targets: Sequence[str] = (),
+                      display: Sequence[str] = (), ctx: Optional[_capi.Context] = None):
+    """diffs.rs:881-901 `diff_dfs` with its contents: (KeyedDiff, {name: Column}) -- `diff_dfs`, then
+    `diff_contents` with the keys and targets its smart defaults resolved. See `diff_contents` for the row
+    order (no `sort_df_on_keys`)."""
+    left, right = _as_frame(left), _as_frame(right)
+    resolved_keys, resolved_targets = _keys_targets_smart_defaults(left, right, keys, targets)
+    d = diff_dfs(left, right, keys=keys, targets=targets, ctx=ctx)
+    return d, diff_contents(left, right, d, resolved_keys, resolved_targets, display, ctx=ctx)
 
 
 def _buffer(buf, dtype) -> Optional[np.ndarray]:
@@ -437,3 +699,32 @@ def columns_from_arrow(table_or_batch) -> dict:
     any other type raises: cast it to string, which is what the reference's `to_string()` arm amounts to."""
     names = table_or_batch.schema.names
     return {name: _arrow_column(name, table_or_batch.column(i)) for i, name in enumerate(names)}
+
+
+def columns_to_arrow(columns: Mapping, schema):
+    """The inverse of `columns_from_arrow` for callers with pyarrow: a pyarrow Table over the buffers of
+    {name: Column} (host memory; what `take` and `diff_contents` return). schema: a pyarrow Schema naming
+    every column -- a Column carries a width, the schema says the type (int32 or float32, string or
+    binary). Nothing is copied but a bitmap that does not start at bit 0 (a sliced source, never a take's
+    output), which is repacked: an Arrow array has one offset for all its buffers, a Column one per bitmap."""
+    import pyarrow as pa
+
+    as_buffer = lambda a: None if a is None else pa.py_buffer(np.ascontiguousarray(a).view(np.uint8))  # noqa: E731
+
+    def bitmap(packed, bit0, n):
+        if packed is None or not bit0:
+            return as_buffer(packed)
+        return as_buffer(_pack(np.unpackbits(np.asarray(packed, dtype=np.uint8), bitorder="little")[bit0:bit0 + n]))
+
+    arrays = []
+    for field in schema:
+        c = columns[field.name]
+        n = int(c.nrows)
+        validity = bitmap(c.validity, int(c.validity_bit), n)
+        if c.kind == OXH_COL_BOOL:
+            buffers = [validity, bitmap(c.values, int(c.value_bit), n)]
+        else:
+            values = as_buffer(c.values) if c.values is not None and len(c.values) else pa.py_buffer(b"")
+            buffers = [validity, as_buffer(c.offsets), values] if c.kind in _BYTES else [validity, values]
+        arrays.append(pa.Array.from_buffers(field.type, n, buffers))
+    return pa.Table.from_arrays(arrays, schema=schema)
