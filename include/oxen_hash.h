@@ -584,6 +584,50 @@ int oxh_take_columns_host(oxh_ctx* ctx, uint32_t nsrc, const uint32_t* kinds, co
                           const uint32_t* plan, const uint64_t* value_capacity, void* const* out_values, void* const* out_offsets,
                           uint8_t* const* out_validity, uint64_t* value_bytes, uint32_t* written);
 
+/* ---------------------------------------------------------------- stable multi-column row sort
+ * join_diff.rs:107 sorts the joined frame with `sort_df_on_keys` (:146-163) before it selects the output
+ * columns, and `oxen df --sort` (core/df/tabular.rs:520-522) sorts a frame on one column. Here the sort is a
+ * device-wide stable radix sort over the key columns; its result is a permutation, directly usable as idx0
+ * of oxh_take_columns_*.
+ *
+ * The order. It restates polars' documented defaults (`SortMultipleOptions::new().with_order_descending(false)`:
+ * ascending, nulls_last = false); it is NOT pinned by a run of polars. Rows are compared key column by key
+ * column, in the order the caller lists the keys. Within one column: a null comes before every value;
+ * OXH_SORT_SIGNED: two's complement of the column's width (Int8, Int32, Int64, Datetime(ms));
+ * OXH_SORT_UNSIGNED: plain unsigned of the column's width; OXH_SORT_FLOAT (widths 4 and 8 only): numeric
+ * order, -0.0 equals +0.0, every NaN -- whatever its sign or payload -- equals every other NaN and is greater
+ * than +inf; OXH_COL_BOOL: false before true (the order class is ignored); byte columns: unsigned byte-wise
+ * lexicographic order, a proper prefix first, so "" < "a" < "a\0" < "a\0\0" < "b" and a null comes before ""
+ * (the order class is ignored). Rows equal on every key keep their input order: the sort is STABLE. The
+ * reference's sort is unstable; the stable result is one of those it may produce, and it is unique.
+ * (`sort_df_on_keys` sorts on the keys that are `is_primitive()`, restated from memory as numeric | Boolean |
+ * String | Binary: every kind a column here can have, so every key takes part. Unpinned as well.)
+ *
+ * Key columns are described exactly as oxh_row_hashes_* takes them (kinds, values, offsets, validity,
+ * bit_offsets[2c] / [2c+1]); orders[c] is one of the three classes. kinds, bit_offsets, orders, stats3 and
+ * the three pointer arrays are HOST arrays in both forms; what the pointers point to, and perm, is on the
+ * device in _device and on the host in _host. perm[i] (nrows u32) = the input row that stands at place i of
+ * the sorted frame. stats3 = {refinement rounds run, radix passes launched, rows that equal another row on
+ * every key}. Both forms block until complete and keep nothing (memory: 86 B per row on the device, leased
+ * for the call; the host form adds the key columns it copies and 4 B per row).
+ * OXH_ERR_INVALID, before OXH_ERR_NODEVICE (there is no CPU path): a NULL kinds, values, offsets, validity,
+ * bit_offsets or orders; nkeys == 0; an unknown kind, or an unknown order class of a fixed-width column;
+ * OXH_SORT_FLOAT on a width-1 column; more than 2^32 - 2 rows; with rows: NULL offsets of a byte column, NULL
+ * values (but for a byte column whose span is empty; the device form learns that on the device), a NULL perm;
+ * NULL stats3; then a NULL ctx. nrows == 0 after the checks is OXH_OK: stats3 is zeroed, nothing else is
+ * touched. A failed allocation is OXH_ERR_NOMEM with perm untouched. Offsets must not decrease or be
+ * negative: the host form checks them; the device form treats a bad pair as a cell of length 0 and returns
+ * OXH_ERR_INVALID. Neither form ever reads outside a named span. */
+#define OXH_SORT_SIGNED 0
+#define OXH_SORT_UNSIGNED 1
+#define OXH_SORT_FLOAT 2
+int oxh_sort_rows_device(oxh_ctx* ctx, uint64_t nrows, uint32_t nkeys, const uint32_t* kinds, const void* const* d_values,
+                         const void* const* d_offsets, const uint8_t* const* d_validity, const uint64_t* bit_offsets,
+                         const uint32_t* orders, uint32_t* d_perm, uint64_t* stats3, void* stream);
+int oxh_sort_rows_host(oxh_ctx* ctx, uint64_t nrows, uint32_t nkeys, const uint32_t* kinds, const void* const* values,
+                       const void* const* offsets, const uint8_t* const* validity, const uint64_t* bit_offsets,
+                       const uint32_t* orders, uint32_t* perm, uint64_t* stats3);
+
 /* ---------------------------------------------------------------- K2: merkle parent nodes */
 /* get_combined_hash (hasher.rs:67-80) x n on the device:
  * XXH3-128(content.to_le_bytes() || metadata.to_le_bytes()), inputs as (lo, hi) pairs. */

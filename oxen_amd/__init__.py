@@ -13,7 +13,8 @@ Modules:
   tabular   -- row hashes of a data frame from its columns and the row set-diff (`oxen diff` on
                tabular files: df_hash_rows, df_hash_rows_on_cols, compute_new_row_indices), and the
                keyed diff of two frames (keyed_diff_digests, diff_dfs) with its contents: the take of
-               the joined rows' columns on the device (take, diff_contents, diff_dfs_contents)
+               the joined rows' columns on the device (take, diff_contents, diff_dfs_contents), and the
+               stable multi-column row sort (sort_indices, sort_by; `sort=True` of the contents)
   procpool  -- file hashing sharded over reader processes (the open/close floor is per process)
   shard     -- multi-GPU sharding and the RCCL digest gather
   device    -- device-resident (HBM) batch entry points over torch buffers
@@ -29,7 +30,8 @@ _FROM_DEDUP = ("ChunkOverlap", "chunk_overlap", "chunk_overlap_device", "names_t
                "OxenChunker")
 # and from oxen_amd.tabular
 _FROM_TABULAR = ("KeyedDiff", "STATUS_NAMES", "keyed_diff_digests", "keyed_diff_digests_device", "diff_dfs",
-                 "take", "take_device", "diff_contents", "diff_dfs_contents", "output_columns", "columns_to_arrow")
+                 "take", "take_device", "diff_contents", "diff_dfs_contents", "output_columns", "columns_to_arrow",
+                 "sort_indices", "sort_indices_device", "sort_orders_from_arrow", "sort_by", "sort_diff_rows_device")
 
 
 def __getattr__(name):

@@ -46,6 +46,9 @@ OXH_DIFF_REMOVED = 2
 OXH_DIFF_MODIFIED = 3
 OXH_TAKE_NULL = 0xFFFFFFFF        # an absent index (the value of OXH_KEYED_DIFF_NONE)
 OXH_TAKE_NO_COLUMN = 0xFFFFFFFF   # no fallback source column
+OXH_SORT_SIGNED = 0     # two's complement of the column's width
+OXH_SORT_UNSIGNED = 1   # plain unsigned of the column's width
+OXH_SORT_FLOAT = 2      # numeric; -0.0 == +0.0; every NaN equal and above +inf (widths 4 and 8)
 
 _u64 = ctypes.c_uint64
 _u32 = ctypes.c_uint32
@@ -144,6 +147,10 @@ SIGNATURES = {
                                      ctypes.POINTER(_vp), _u64p, _u64p, _u64, _vp, _vp, _u32, ctypes.POINTER(_u32), _u64p,
                                      ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u64p,
                                      ctypes.POINTER(_u32)]),
+    "oxh_sort_rows_device": (_int, [_vp, _u64, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                    ctypes.POINTER(_vp), _u64p, ctypes.POINTER(_u32), _vp, _u64p, _vp]),
+    "oxh_sort_rows_host": (_int, [_vp, _u64, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                  ctypes.POINTER(_vp), _u64p, ctypes.POINTER(_u32), _vp, _u64p]),
     "oxh_comm_check": (_int, [_int]),
     "oxh_ctx_counters": (_int, [_vp, _u64p, _int]),
     "oxh_comm_unique_id": (_int, [ctypes.c_char_p]),

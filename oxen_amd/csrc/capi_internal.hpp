@@ -21,6 +21,9 @@
 //   take_columns.hip   the columns of the joined rows (oxh_take_columns_*): a take of Arrow columns by the keyed
 //                      diff's row indices, with a fallback source (coalesce); columns.hpp holds what it shares
 //                      with row_hash.hip (the column descriptor, the cell of a row, the host forms' staging)
+//   sort_rows.hip      the stable multi-column row sort (oxh_sort_rows_*): MSD refinement rounds over the key
+//                      columns' order-preserving key words (sort_keys.hpp), each round a few passes of the
+//                      device-wide stable radix pass it defines (stable_radix_pass)
 // There is no CPU hashing path: every digest this library returns was computed on the GPU.
 #pragma once
 
@@ -134,6 +137,20 @@ namespace oxh {
 // Callers: the keyed diff's pair offsets, the take's byte-column offsets (take_columns.hip).
 uint64_t scan_tiles(uint64_t n);
 int exclusive_scan_u32(const uint32_t* d_in, uint64_t n, uint64_t* d_out, unsigned long long* d_sums, hipStream_t st);
+}  // namespace oxh
+
+// ---------------------------------------------------------------- device-wide stable radix pass (sort_rows.hip)
+namespace oxh {
+// One stable pass over n (u64 key, u32 payload) pairs by the 8-bit digit (key >> shift) & 255, enqueued on
+// `st` (five launches: a per-tile histogram, exclusive_scan_u32 over it, the scatter; no workgroup waits for
+// another). Elements of equal digit keep their order. in and out must not overlap. Device scratch:
+// d_table 256 * radix_tiles(n) u32, d_scanned as many u64, d_sums scan_tiles(256 * radix_tiles(n)) + 1 words.
+// A destination outside the n places is never stored: d_err[0] |= 4 instead (the caller reads it back).
+// Callers: the row sort's rounds.
+uint64_t radix_tiles(uint64_t n);
+int stable_radix_pass(const uint64_t* d_key_in, const uint32_t* d_pay_in, uint64_t* d_key_out, uint32_t* d_pay_out, uint64_t n,
+                      uint32_t shift, uint32_t* d_table, uint64_t* d_scanned, unsigned long long* d_sums,
+                      unsigned long long* d_err, hipStream_t st);
 }  // namespace oxh
 
 namespace oxh::capi {

@@ -14,6 +14,10 @@ labelled added / removed / modified / unchanged, and the summary counts -- `keye
 the joined rows' indices, null indices and a fallback source (the keys' coalesce) included -- `take`,
 `take_device`, `diff_contents`, `diff_dfs_contents`, and `columns_to_arrow` back to pyarrow.
 
+`oxh_sort_rows_*` is the reference's `sort_df_on_keys` of that frame (join_diff.rs:146-163) and `oxen df --sort`:
+a stable multi-column sort of the rows on the device that returns a permutation -- `sort_indices`,
+`sort_indices_device`, `sort_by`, and `sort=True` of `diff_contents` / `diff_dfs_contents`.
+
 A frame is an ordered mapping from column name to `Column`. A row's bytes are, over the columns in the
 frame's order: nothing for a null, the raw little-endian bytes of Int8 / Int32 / Float32 / Int64 /
 Float64 / Datetime(ms), one byte 0 or 1 for a boolean, the UTF-8 bytes of a string. Every other dtype
@@ -29,7 +33,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import (OXH_COL_BOOL, OXH_COL_BYTES32, OXH_COL_BYTES64, OXH_COL_FIXED1, OXH_COL_FIXED4,  # noqa: F401
-                    OXH_COL_FIXED8)
+                    OXH_COL_FIXED8, OXH_SORT_FLOAT, OXH_SORT_SIGNED, OXH_SORT_UNSIGNED)
 
 _BYTES = (OXH_COL_BYTES32, OXH_COL_BYTES64)
 _WIDTH = {OXH_COL_FIXED1: 1, OXH_COL_FIXED4: 4, OXH_COL_FIXED8: 8}
@@ -610,15 +614,55 @@ def output_columns(left: Mapping, right: Mapping, keys: Sequence[str], targets: 
     return out
 
 
+def _sort_key_plan(left: Mapping, right: Mapping, names: Sequence[str]) -> list:
+    """The take plan of the sort keys of a keyed diff's contents over the sources [left columns..., right
+    columns...]: every name as `coalesce(name.right, name.left)` (join_diff.rs:95-102), the side a frame
+    lacks left out."""
+    where = {("left", name): i for i, name in enumerate(left)}
+    where.update({("right", name): len(left) + i for i, name in enumerate(right)})
+    plan = []
+    for name in names:
+        if name in right:
+            plan.append((where["right", name], 1, where["left", name] if name in left else None, 0))
+        elif name in left:
+            plan.append((where["left", name], 0, None, 0))
+        else:
+            raise _capi.OxenError(f"sort key {name!r} is a column of neither frame", _capi.OXH_ERR_INVALID)
+    return plan
+
+
+def _sort_names(sort, keys) -> list:
+    names = list(keys) if sort is True else list(sort)
+    if not names:
+        raise _capi.OxenError("sort needs at least one key column", _capi.OXH_ERR_INVALID)
+    return names
+
+
+def _sort_orders_for(names, orders):
+    """orders of `diff_contents`: None, a sequence parallel to the sort keys, or {name: order class}."""
+    if orders is None or not isinstance(orders, Mapping):
+        return orders
+    return [orders.get(name) for name in names]
+
+
 def diff_contents(left: Mapping, right: Mapping, diff: KeyedDiff, keys: Sequence[str], targets: Sequence[str],
-                  display: Sequence[str] = (), ctx: Optional[_capi.Context] = None) -> dict:
+                  display: Sequence[str] = (), ctx: Optional[_capi.Context] = None, sort=False, orders=None):
     """TabularDiff.contents of join_diff.rs `diff` after `diff_dfs`, as an ordered {name: Column}: the
     columns `output_columns` lists -- one `take` over both frames' columns through diff.left_rows /
     diff.right_rows, the keys coalesced right-then-left -- and `_oxen_diff_status`, a string column built
     from STATUS_NAMES on the host. keys / targets: the resolved ones (`diff_dfs_contents` passes them).
-    The rows come in the keyed diff's canonical order. `sort_df_on_keys` (:146-163) is NOT applied: a Column
-    carries a width, not a dtype, and the reference's sort is unstable, so its row order is no parity
-    target; sort the result on the key columns where that order is wanted."""
+
+    sort=False (the default): the rows come in the keyed diff's canonical order and the contents are returned.
+    sort=True applies `sort_df_on_keys` (join_diff.rs:107, :146-163) on every key, in the order `keys` lists
+    them; a list of names sorts on those keys. The order is this project's stable one (`sort_indices`):
+    ascending, nulls first, rows with equal keys in the canonical order -- one of the results the
+    reference's unstable sort may produce. The sort keys are the keys' `coalesce(right, left)` columns, one
+    take of just those, whether or not the output keeps them (the reference sorts before its `select`); the
+    permutation is applied to left_rows, right_rows and status, and the one take of the wide columns then
+    writes the contents in order. Returns (the KeyedDiff with the permuted rows, contents) so that status
+    and contents stay aligned. orders: the order class of each sort key (a sequence, or {name: class}); None
+    reads it from the columns' dtypes, which frames from `columns_from_arrow` do not carry
+    (`sort_orders_from_arrow`)."""
     left, right = _as_frame(left), _as_frame(right)
     wanted = output_columns(left, right, keys, targets, display)
     sources = list(left.values()) + list(right.values())
@@ -627,10 +671,36 @@ def diff_contents(left: Mapping, right: Mapping, diff: KeyedDiff, keys: Sequence
     side = {"left": 0, "right": 1}
     plan = [(where[a], side[a[0]], None if b is None else where[b], 0 if b is None else side[b[0]]) for _, a, b in wanted]
     left_rows, right_rows = np.asarray(diff.left_rows), np.asarray(diff.right_rows)
+    if sort is not False and sort is not None:
+        names = _sort_names(sort, keys)
+        key_columns = take(sources, left_rows, right_rows, _sort_key_plan(left, right, names), ctx=ctx)
+        perm, _ = sort_indices(key_columns, _sort_orders_for(names, orders), ctx=ctx)
+        left_rows, right_rows = left_rows[perm], right_rows[perm]
+        diff = diff._replace(left_rows=left_rows, right_rows=right_rows, status=np.asarray(diff.status)[perm])
     taken = take(sources, left_rows, right_rows, plan, ctx=ctx) if plan else []
     contents = {name: col for (name, _, _), col in zip(wanted, taken)}
     contents[STATUS_COLUMN] = _status_column(np.asarray(diff.status))
+    if sort is not False and sort is not None:
+        return diff, contents
     return contents
+
+
+def sort_diff_rows_device(left: Mapping, right: Mapping, diff: KeyedDiff, names: Sequence[str], orders=None, stream=None,
+                          ctx: Optional[_capi.Context] = None) -> KeyedDiff:
+    """The device steps of `diff_contents(sort=...)` over frames whose Columns hold device tensors and a
+    KeyedDiff from `keyed_diff_digests_device`: one `take_device` of the sort keys' coalesced columns,
+    `sort_indices_device`, and one `take_device` of left_rows, right_rows and status -- three fixed-width
+    columns -- through the permutation. Returns the KeyedDiff with the permuted rows (device tensors); a
+    `take_device` of the wide columns through them writes the contents in order. Blocks."""
+    names = list(names)
+    sources = list(left.values()) + list(right.values())
+    key_columns = take_device(sources, diff.left_rows, diff.right_rows, _sort_key_plan(left, right, names), stream=stream, ctx=ctx)
+    perm, _ = sort_indices_device(key_columns, _sort_orders_for(names, orders), stream=stream, ctx=ctx)
+    n = int(perm.numel())
+    rows = [Column(OXH_COL_FIXED4, n, diff.left_rows), Column(OXH_COL_FIXED4, n, diff.right_rows),
+            Column(OXH_COL_FIXED1, n, diff.status)]
+    l, r, s = take_device(rows, perm, stream=stream, ctx=ctx)
+    return diff._replace(left_rows=l.values, right_rows=r.values, status=s.values)
 
 
 def _status_column(status: np.ndarray) -> Column:
@@ -650,14 +720,137 @@ def _status_column(status: np.ndarray) -> Column:
 
 
 def diff_dfs_contents(left: Mapping, right: Mapping, keys: Sequence[str] = (), targets: Sequence[str] = (),
-                      display: Sequence[str] = (), ctx: Optional[_capi.Context] = None):
+                      display: Sequence[str] = (), ctx: Optional[_capi.Context] = None, sort=False, orders=None):
     """diffs.rs:881-901 `diff_dfs` with its contents: (KeyedDiff, {name: Column}) -- `diff_dfs`, then
-    `diff_contents` with the keys and targets its smart defaults resolved. See `diff_contents` for the row
-    order (no `sort_df_on_keys`)."""
+    `diff_contents` with the keys and targets its smart defaults resolved. sort / orders: as `diff_contents`
+    takes them -- False keeps the keyed diff's canonical order; True is `sort_df_on_keys` on every resolved
+    key in the caller's order, a list of names on those; the KeyedDiff returned then holds the sorted rows."""
     left, right = _as_frame(left), _as_frame(right)
     resolved_keys, resolved_targets = _keys_targets_smart_defaults(left, right, keys, targets)
     d = diff_dfs(left, right, keys=keys, targets=targets, ctx=ctx)
-    return d, diff_contents(left, right, d, resolved_keys, resolved_targets, display, ctx=ctx)
+    if sort is False or sort is None:
+        return d, diff_contents(left, right, d, resolved_keys, resolved_targets, display, ctx=ctx)
+    return diff_contents(left, right, d, resolved_keys, resolved_targets, display, ctx=ctx, sort=sort, orders=orders)
+
+
+# ---------------------------------------------------------------- stable multi-column row sort
+class SortStats(NamedTuple):
+    """stats3 of oxh_sort_rows_*: refinement rounds run, radix passes launched, rows that equal another row
+    on every key."""
+    rounds: int
+    passes: int
+    tied: int
+
+
+def _order_of(c: Column, k: int) -> int:
+    """The default order class of key column k from the dtype of its values. A Column carries a width, not a
+    dtype: raw uint8 storage (what `columns_from_arrow` makes) says nothing, and the call needs `orders`."""
+    if c.kind not in _WIDTH:
+        return OXH_SORT_SIGNED   # ignored for booleans and byte columns
+    dt = getattr(c.values, "dtype", None)
+    size = getattr(dt, "itemsize", None)
+    if isinstance(dt, np.dtype):
+        kind = dt.kind
+    elif dt is not None:   # a torch dtype
+        kind = "f" if dt.is_floating_point else ("i" if dt.is_signed else "u")
+    else:
+        kind = None
+    if kind is None or size != _WIDTH[c.kind] or (kind == "u" and size == 1) or kind not in "fiuM":
+        raise _capi.OxenError(f"sort key column {k} holds raw {dt} storage of a {_WIDTH[c.kind]}-byte cell: its dtype does not say "
+                              "how it is ordered; pass orders (OXH_SORT_SIGNED / OXH_SORT_UNSIGNED / OXH_SORT_FLOAT, "
+                              "sort_orders_from_arrow)", _capi.OXH_ERR_INVALID)
+    return {"f": OXH_SORT_FLOAT, "i": OXH_SORT_SIGNED, "M": OXH_SORT_SIGNED, "u": OXH_SORT_UNSIGNED}[kind]
+
+
+def _orders(cols, orders):
+    if orders is None:
+        orders = [None] * len(cols)
+    orders = list(orders)
+    if len(orders) != len(cols):
+        raise _capi.OxenError("orders has one entry per key column", _capi.OXH_ERR_INVALID)
+    words = [_order_of(c, k) if o is None else int(o) for k, (c, o) in enumerate(zip(cols, orders))]
+    return (ctypes.c_uint32 * max(len(words), 1))(*words)
+
+
+def sort_orders_from_arrow(schema, names) -> list:
+    """The order classes of the key columns `names` of a frame made by `columns_from_arrow`, from the pyarrow
+    schema: floats OXH_SORT_FLOAT, unsigned integers OXH_SORT_UNSIGNED, everything else OXH_SORT_SIGNED
+    (signed integers and timestamps; booleans, strings and binary ignore theirs)."""
+    import pyarrow as pa
+
+    out = []
+    for name in names:
+        t = schema.field(name).type
+        out.append(OXH_SORT_FLOAT if pa.types.is_floating(t) else OXH_SORT_UNSIGNED if pa.types.is_unsigned_integer(t)
+                   else OXH_SORT_SIGNED)
+    return out
+
+
+def sort_indices(columns: Sequence, orders=None, ctx: Optional[_capi.Context] = None):
+    """oxh_sort_rows_host: (perm, SortStats) -- perm[i] (uint32) = the row of the frame that stands at place i
+    when its rows are sorted on `columns` (key `Column`s, or what `column` takes, most significant first, in
+    host memory): ascending, a null before every value, -0.0 equal to +0.0, every NaN equal and last, byte
+    columns in unsigned byte order with a proper prefix first, rows equal on every key in input order (the
+    sort is stable). perm is usable as idx0 of `take`. orders: one OXH_SORT_* per key (None entries, or None
+    for all: from the dtype of `values` -- float, signed integer / datetime64, unsigned integer)."""
+    cols = _as_columns(columns)
+    nrows = cols[0].nrows if cols else 0
+    order_words = _orders(cols, orders)
+    keep = []
+
+    def ptr(a):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a)
+        keep.append(a)
+        return a.ctypes.data if a.size else None
+
+    perm = np.zeros(nrows, dtype=np.uint32)
+    stats = np.zeros(3, dtype=np.uint64)
+    _capi.check(_capi.lib().oxh_sort_rows_host(_handle(ctx), nrows, len(cols), *_tables(cols, ptr), order_words,
+                                               perm.ctypes.data if nrows else None, stats.ctypes.data_as(_capi._u64p)),
+                "oxh_sort_rows_host")
+    return perm, SortStats(*(int(s) for s in stats))
+
+
+def sort_indices_device(columns: Sequence[Column], orders=None, stream=None, ctx: Optional[_capi.Context] = None):
+    """oxh_sort_rows_device: `sort_indices` over `Column`s whose values / offsets / validity are torch tensors
+    on the device; (perm, SortStats) with perm an int32 device tensor holding the u32 words, as `take_device`
+    takes its indices. Blocks."""
+    import torch
+
+    from .device import _require_cuda, _stream
+
+    cols = list(columns)
+    nrows = cols[0].nrows if cols else 0
+    if any(c.nrows != nrows for c in cols):
+        raise _capi.OxenError("the columns of a frame have one row count", _capi.OXH_ERR_INVALID)
+    order_words = _orders(cols, orders)
+    tensors = [t for c in cols for t in (c.values, c.offsets, c.validity) if t is not None]
+    _require_cuda(*tensors)
+    if any(not t.is_contiguous() for t in tensors):
+        raise _capi.OxenError("column tensors must be contiguous", _capi.OXH_ERR_INVALID)
+    device = tensors[0].device if tensors else "cuda"
+    perm = torch.empty(nrows, dtype=torch.int32, device=device)
+    stats = np.zeros(3, dtype=np.uint64)
+    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()  # noqa: E731
+    _capi.check(_capi.lib().oxh_sort_rows_device(_handle(ctx), nrows, len(cols), *_tables(cols, ptr), order_words,
+                                                 perm.data_ptr() if nrows else None, stats.ctypes.data_as(_capi._u64p),
+                                                 _stream(stream)), "oxh_sort_rows_device")
+    return perm, SortStats(*(int(s) for s in stats))
+
+
+def sort_by(frame: Mapping, name: str, orders=None, ctx: Optional[_capi.Context] = None) -> dict:
+    """`oxen df --sort name` (core/df/tabular.rs:520-522): the frame with its rows sorted on column `name`,
+    as an ordered {name: Column} -- `sort_indices` of that column, then one `take` of every column through
+    the permutation. orders: the key's order class (or a one-entry sequence); None reads the dtype."""
+    frame = _as_frame(frame)
+    if name not in frame:
+        raise _capi.OxenError(f"sort column {name!r} is not in the frame", _capi.OXH_ERR_INVALID)
+    if orders is not None and not isinstance(orders, (list, tuple)):
+        orders = [orders]
+    perm, _ = sort_indices([frame[name]], orders, ctx=ctx)
+    return dict(zip(frame, take(list(frame.values()), perm, ctx=ctx)))
 
 
 def _buffer(buf, dtype) -> Optional[np.ndarray]:
