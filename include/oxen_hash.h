@@ -628,6 +628,62 @@ int oxh_sort_rows_host(oxh_ctx* ctx, uint64_t nrows, uint32_t nkeys, const uint3
                        const void* const* offsets, const uint8_t* const* validity, const uint64_t* bit_offsets,
                        const uint32_t* orders, uint32_t* perm, uint64_t* stats3);
 
+/* ---------------------------------------------------------------- rows grouped by equality: unique, unique_count, duplicates
+ * `oxen df --unique cols` (core/df/tabular.rs:424-427 `unique_df`: `df.unique(Some(columns),
+ * UniqueKeepStrategy::First)`), `--unique_count cols` (:429-433 `unique_count_df`: `group_by(cols).agg([len()])`)
+ * and `n_duped_rows` (:263-271: `select(cols).is_duplicated().sum()`) are three readings of one grouping of the
+ * rows by equality on the key columns. Here that grouping is one call on the device; with oxh_sort_rows_* and
+ * oxh_take_columns_* a caller replays `--unique label --sort image` without a host hash map in between.
+ *
+ * Equality. It restates polars' documented behaviour for `unique` / `group_by`; it is NOT pinned by a run of
+ * polars. Rows are equal when they are equal in every key column. Within a column a null equals a null and
+ * nothing else; fixed-width cells are equal when their bytes are, but under OXH_SORT_FLOAT (widths 4 and 8),
+ * where -0.0 equals +0.0 and every NaN equals every NaN whatever its sign or payload -- the canonical form
+ * the sort above orders by, from the same code; booleans are equal by value; byte cells when they have the same
+ * length and the same bytes ("" is not null). Equality is decided on a 128-bit digest (XXH3-128) of an
+ * injective image of the row's key -- every cell tagged null / present, a byte cell behind its length -- as
+ * everywhere in this library; the undelimited row bytes of oxh_row_hashes_* cannot serve (("ab","c") and
+ * ("a","bc"), (null, 5) and (5, null), null and "" collide there, as in the reference's diff).
+ *
+ * Key columns are described exactly as oxh_sort_rows_* takes them (kinds, values, offsets, validity,
+ * bit_offsets[2c] / [2c+1], orders[c] one of OXH_SORT_*: only OXH_SORT_FLOAT changes equality, but the array is
+ * taken and validated as the sort does, so a frame's sort plan is reusable as it is). kinds, bit_offsets, orders,
+ * stats4 and the three pointer arrays are HOST arrays in both forms; what the pointers point to, and the four
+ * outputs, are on the device in _device and on the host in _host. Outputs, u32 each, every one of them may be
+ * NULL on its own (it is then not written):
+ *   group[i]       (nrows) the smallest row whose key equals row i's: group[i] <= i, group[group[i]] == group[i];
+ *   count[i]       (nrows) the rows of row i's group;
+ *   first_idx[g], first_count[g]   for g < groups: the rows with group[i] == i, ascending, and their groups'
+ *                  sizes. The caller provides nrows entries each; entries from `groups` on are untouched.
+ *                  first_idx is the selection of unique(keep = First) with the first occurrences in input order
+ *                  (polars' maintain_order form; the reference's order is unspecified and its tests sort
+ *                  afterwards: this order is one it may produce, and it is unique), usable as idx0 of
+ *                  oxh_take_columns_*.
+ * stats4 (host, required) = {groups, rows whose group has two or more rows (is_duplicated().sum(), n_duped_rows),
+ * the largest group, rows whose key image went through the long path (above 240 encoded bytes)}.
+ * Both forms block until complete and keep nothing: a private index and a lease of device scratch end with the
+ * call, and no oxh_dedup_index_* handle of the context is touched (memory: 40 B per row leased, plus the index's
+ * 32-48 B per row: 72-88 B per row, and the images of the long rows; the host form adds the key columns it
+ * copies and 16 B per row).
+ * OXH_ERR_INVALID, before OXH_ERR_NODEVICE (there is no CPU path): the sort's list in the sort's order -- a NULL
+ * kinds, values, offsets, validity, bit_offsets or orders; nkeys == 0; an unknown kind, or an unknown order class
+ * of a fixed-width column; OXH_SORT_FLOAT on a width-1 column; more than 2^32 - 2 rows; with rows: NULL offsets of
+ * a byte column, NULL values (but for a byte column whose span is empty; the device form learns that on the
+ * device) -- then NULL stats4; then a NULL ctx. nrows == 0 after the checks is OXH_OK: stats4 is zeroed, nothing
+ * else is touched. A failed allocation is OXH_ERR_NOMEM with the outputs untouched. Offsets must not decrease or
+ * be negative: the host form checks them (nothing is written); the device form treats a bad pair as a cell of
+ * length 0, finishes -- the outputs and stats4 are those of the frame with that cell empty -- and returns
+ * OXH_ERR_INVALID. Neither form ever reads outside a named span. An id from the index that is not a row at or
+ * before its own is never used as an index: the call returns OXH_ERR_HIP. */
+int oxh_group_rows_device(oxh_ctx* ctx, uint64_t nrows, uint32_t nkeys, const uint32_t* kinds, const void* const* d_values,
+                          const void* const* d_offsets, const uint8_t* const* d_validity, const uint64_t* bit_offsets,
+                          const uint32_t* orders, uint32_t* d_group, uint32_t* d_count, uint32_t* d_first_idx,
+                          uint32_t* d_first_count, uint64_t* stats4, void* stream);
+int oxh_group_rows_host(oxh_ctx* ctx, uint64_t nrows, uint32_t nkeys, const uint32_t* kinds, const void* const* values,
+                        const void* const* offsets, const uint8_t* const* validity, const uint64_t* bit_offsets,
+                        const uint32_t* orders, uint32_t* group, uint32_t* count, uint32_t* first_idx, uint32_t* first_count,
+                        uint64_t* stats4);
+
 /* ---------------------------------------------------------------- K2: merkle parent nodes */
 /* get_combined_hash (hasher.rs:67-80) x n on the device:
  * XXH3-128(content.to_le_bytes() || metadata.to_le_bytes()), inputs as (lo, hi) pairs. */

@@ -14,7 +14,9 @@ Modules:
                tabular files: df_hash_rows, df_hash_rows_on_cols, compute_new_row_indices), and the
                keyed diff of two frames (keyed_diff_digests, diff_dfs) with its contents: the take of
                the joined rows' columns on the device (take, diff_contents, diff_dfs_contents), and the
-               stable multi-column row sort (sort_indices, sort_by; `sort=True` of the contents)
+               stable multi-column row sort (sort_indices, sort_by; `sort=True` of the contents), and the
+               rows grouped by equality on key columns (group_rows, unique, unique_count, is_duplicated,
+               n_duped_rows)
   procpool  -- file hashing sharded over reader processes (the open/close floor is per process)
   shard     -- multi-GPU sharding and the RCCL digest gather
   device    -- device-resident (HBM) batch entry points over torch buffers
@@ -31,7 +33,9 @@ _FROM_DEDUP = ("ChunkOverlap", "chunk_overlap", "chunk_overlap_device", "names_t
 # and from oxen_amd.tabular
 _FROM_TABULAR = ("KeyedDiff", "STATUS_NAMES", "keyed_diff_digests", "keyed_diff_digests_device", "diff_dfs",
                  "take", "take_device", "diff_contents", "diff_dfs_contents", "output_columns", "columns_to_arrow",
-                 "sort_indices", "sort_indices_device", "sort_orders_from_arrow", "sort_by", "sort_diff_rows_device")
+                 "sort_indices", "sort_indices_device", "sort_orders_from_arrow", "sort_by", "sort_diff_rows_device",
+                 "RowGroups", "GroupStats", "group_rows", "group_rows_device", "unique", "unique_count", "is_duplicated",
+                 "n_duped_rows")
 
 
 def __getattr__(name):

@@ -24,6 +24,9 @@
 //   sort_rows.hip      the stable multi-column row sort (oxh_sort_rows_*): MSD refinement rounds over the key
 //                      columns' order-preserving key words (sort_keys.hpp), each round a few passes of the
 //                      device-wide stable radix pass it defines (stable_radix_pass)
+//   group_rows.hip     the rows of a frame grouped by equality on key columns (oxh_group_rows_*): the digests of an
+//                      injective key image of every row (row_hash.hip's kernels, instantiated for that image), the
+//                      index's public entries, then a count, the scan and an emit
 // There is no CPU hashing path: every digest this library returns was computed on the GPU.
 #pragma once
 
@@ -137,6 +140,25 @@ namespace oxh {
 // Callers: the keyed diff's pair offsets, the take's byte-column offsets (take_columns.hip).
 uint64_t scan_tiles(uint64_t n);
 int exclusive_scan_u32(const uint32_t* d_in, uint64_t n, uint64_t* d_out, unsigned long long* d_sums, hipStream_t st);
+}  // namespace oxh
+
+// ---------------------------------------------------------------- runs of equal neighbours in a wave
+// (callers: the keyed diff's count and bucket kernels, keyed_diff.hip; the grouping's count, group_rows.hip)
+namespace oxh {
+// A wave's runs of equal neighbouring tags (a lane that is not live belongs to none). head: the lane is the
+// first of its run; len: the run's length (head lanes); rank: the lane's place in its run; head_lane: where
+// the run starts. Every lane of the wave calls it.
+__device__ __forceinline__ void wave_runs(unsigned long long tag, unsigned lane, bool& head, uint32_t& len, uint32_t& rank,
+                                          unsigned& head_lane) {
+    const unsigned long long before = (unsigned long long)__shfl_up((long long)tag, 1, 64);
+    head = lane == 0 || before != tag;
+    const unsigned long long heads = __ballot(head);
+    const unsigned long long above = lane == 63 ? 0 : heads >> (lane + 1);
+    len = above ? (uint32_t)__builtin_ctzll(above) + 1 : 64 - lane;
+    const unsigned long long upto = lane == 63 ? heads : heads & ((2ull << lane) - 1);  // bit 0 is always set
+    head_lane = 63 - (unsigned)__builtin_clzll(upto);
+    rank = lane - head_lane;
+}
 }  // namespace oxh
 
 // ---------------------------------------------------------------- device-wide stable radix pass (sort_rows.hip)

@@ -150,21 +150,6 @@ struct KeyedArgs {
 
 __device__ __forceinline__ bool keyed_bit(const uint8_t* p, uint64_t bit) { return !p || ((p[bit >> 3] >> (bit & 7)) & 1); }
 
-// A wave's runs of equal neighbouring tags (a lane that is not live belongs to none). head: the lane is the
-// first of its run; len: the run's length (head lanes); rank: the lane's place in its run; head_lane: where
-// the run starts. Every lane of the wave calls it.
-__device__ __forceinline__ void wave_runs(unsigned long long tag, unsigned lane, bool& head, uint32_t& len, uint32_t& rank,
-                                          unsigned& head_lane) {
-    const unsigned long long before = (unsigned long long)__shfl_up((long long)tag, 1, 64);
-    head = lane == 0 || before != tag;
-    const unsigned long long heads = __ballot(head);
-    const unsigned long long above = lane == 63 ? 0 : heads >> (lane + 1);
-    len = above ? (uint32_t)__builtin_ctzll(above) + 1 : 64 - lane;
-    const unsigned long long upto = lane == 63 ? heads : heads & ((2ull << lane) - 1);  // bit 0 is always set
-    head_lane = 63 - (unsigned)__builtin_clzll(upto);
-    rank = lane - head_lane;
-}
-
 // grp[0] / grp[1] of every group, and grp[2] = 1 + a right row of it. The adds of a run of equal
 // neighbours (a region of one key) are one add of the run's length, as the index's insert spares its probes.
 __global__ __launch_bounds__(256) void keyed_count_kernel(KeyedArgs a) {

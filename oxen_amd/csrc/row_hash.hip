@@ -42,14 +42,20 @@ constexpr unsigned long long kRowErrPlan = 4;  // beside kRowErrOffsets, kRowErr
 // ctrl words of one call
 constexpr int kCtrlMax = 0, kCtrlLong = 1, kCtrlLongBytes = 2, kCtrlErr = 3, kCtrlCursor = 4 /* and 5 */, kCtrlWords = 8;
 
+// The kernels below are written once for the two images of columns.hpp (image_cell): KEYED = false hashes
+// the reference's row bytes, KEYED = true the grouping's key image (group_rows.hip), whose lengths count the
+// tags and the length prefixes.
+template <bool KEYED>
 __device__ __forceinline__ uint64_t row_length(const RowCol* __restrict__ cols, uint32_t ncols, uint64_t r, unsigned long long& bad) {
-    uint64_t len = 0, start = 0;
-    for (uint32_t k = 0; k < ncols; ++k) len += row_cell(cols[k], r, start, bad);
+    uint64_t len = 0;
+    ImageCell cell;
+    for (uint32_t k = 0; k < ncols; ++k) len += image_cell<KEYED>(cols[k], r, cell, bad);
     return len;
 }
 
 // ctrl[kCtrlMax] = the largest row length, ctrl[kCtrlLong] / [kCtrlLongBytes] = the rows above short_max
 // and their bytes. Grid-stride, so the reduction costs a few thousand atomics whatever nrows is.
+template <bool KEYED>
 __global__ __launch_bounds__(256) void row_length_kernel(const RowCol* __restrict__ cols, uint32_t ncols, uint64_t nrows,
                                                          uint32_t short_max, unsigned long long* __restrict__ ctrl) {
     __shared__ unsigned long long part[4][3];
@@ -57,7 +63,7 @@ __global__ __launch_bounds__(256) void row_length_kernel(const RowCol* __restric
     unsigned long long bad = 0;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < nrows; r += stride) {
-        const uint64_t len = row_length(cols, ncols, r, bad);
+        const uint64_t len = row_length<KEYED>(cols, ncols, r, bad);
         most = len > most ? len : most;
         if (len > short_max) {
             nlong += 1;
@@ -95,6 +101,7 @@ __global__ __launch_bounds__(256) void row_length_kernel(const RowCol* __restric
 
 // Rows [row0, nrows) of at most `cap` bytes, one lane per row; `stride` (bytes, an odd number of dwords,
 // at least cap) apart in dynamic LDS. A row above cap is a long row and is left to the long path.
+template <bool KEYED>
 __global__ __launch_bounds__(256) void row_hash_short_kernel(const RowCol* __restrict__ cols, uint32_t ncols, uint64_t row0,
                                                              uint64_t nrows, uint32_t stride, uint32_t cap,
                                                              uint64_t* __restrict__ out,
@@ -107,42 +114,11 @@ __global__ __launch_bounds__(256) void row_hash_short_kernel(const RowCol* __res
     unsigned long long bad = 0;
     for (uint32_t k = 0; k < ncols; ++k) {
         const RowCol c = cols[k];
-        uint64_t start = 0;
-        const uint64_t len = row_cell(c, r, start, bad);
+        ImageCell cell;
+        const uint64_t len = image_cell<KEYED>(c, r, cell, bad);
         if (len > cap - pos) return;  // a long row (pos <= cap always)
-        const uint32_t n = (uint32_t)len;
-        uint8_t* dst = slot + pos;
-        if (n == 0) continue;
-        switch (c.kind) {
-            case OXH_COL_FIXED1: dst[0] = c.values[r]; break;
-            case OXH_COL_BOOL: dst[0] = row_bit(c.values, c.vbit + r) ? 1 : 0; break;
-            case OXH_COL_FIXED4: {
-                const uint32_t v = ld32u(c.values + 4 * r);
-                __builtin_memcpy(dst, &v, 4);
-                break;
-            }
-            case OXH_COL_FIXED8: {
-                const uint64_t v = ld64u(c.values + 8 * r);
-                __builtin_memcpy(dst, &v, 8);
-                break;
-            }
-            default: {  // exactly the n bytes of the span, the widest pieces first
-                const uint8_t* src = c.values + start;
-                uint32_t b = 0;
-                for (; b + 8 <= n; b += 8) {
-                    const uint64_t v = ld64u(src + b);
-                    __builtin_memcpy(dst + b, &v, 8);
-                }
-                if (b + 4 <= n) {
-                    const uint32_t v = ld32u(src + b);
-                    __builtin_memcpy(dst + b, &v, 4);
-                    b += 4;
-                }
-                for (; b < n; ++b) dst[b] = src[b];
-                break;
-            }
-        }
-        pos += n;
+        image_put_lane<KEYED>(slot + pos, c, r, cell);
+        pos += (uint32_t)len;
     }
     if (bad) __hip_atomic_fetch_or(&ctrl[kCtrlErr], bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const U128 h = xxh3_lane_short(slot, pos);
@@ -154,6 +130,7 @@ __global__ __launch_bounds__(256) void row_hash_short_kernel(const RowCol* __res
 // prefix sum of (1, length) over the workgroup's rows -- ballot and shuffles in the wave, the four wave
 // totals through LDS -- on top of what one atomic add per workgroup and counter returns. Which workgroup
 // comes first is not fixed; the digests are scattered back by row, so the result is.
+template <bool KEYED>
 __global__ __launch_bounds__(256) void row_long_plan_kernel(const RowCol* __restrict__ cols, uint32_t ncols, uint64_t row0,
                                                             uint64_t nrows, uint32_t short_max, uint64_t cap_rows,
                                                             uint64_t cap_bytes, uint64_t* __restrict__ long_row,
@@ -163,7 +140,7 @@ __global__ __launch_bounds__(256) void row_long_plan_kernel(const RowCol* __rest
     const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint64_t r = row0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     unsigned long long bad = 0;
-    const uint64_t len = r < nrows ? row_length(cols, ncols, r, bad) : 0;  // the error word was set by the length pass
+    const uint64_t len = r < nrows ? row_length<KEYED>(cols, ncols, r, bad) : 0;  // the error word was set by the length pass
     const bool is_long = len > short_max;
     const unsigned long long who = __ballot(is_long);
     const uint64_t rank = __popcll(who & ((1ull << lane) - 1));
@@ -199,6 +176,7 @@ __global__ __launch_bounds__(256) void row_long_plan_kernel(const RowCol* __rest
 
 // One wave per long row: its cells, 8 bytes per lane and step, to arena[long_off .. + long_len).
 // (The lists were zeroed: an entry the plan did not fill is row 0 with length 0 and copies nothing.)
+template <bool KEYED>
 __global__ __launch_bounds__(256) void row_long_gather_kernel(const RowCol* __restrict__ cols, uint32_t ncols, uint64_t nlong,
                                                               const uint64_t* __restrict__ long_row,
                                                               const uint64_t* __restrict__ long_off,
@@ -212,22 +190,10 @@ __global__ __launch_bounds__(256) void row_long_gather_kernel(const RowCol* __re
     unsigned long long bad = 0;
     for (uint32_t k = 0; k < ncols; ++k) {
         const RowCol c = cols[k];
-        uint64_t start = 0;
-        const uint64_t n = row_cell(c, r, start, bad);
+        ImageCell cell;
+        const uint64_t n = image_cell<KEYED>(c, r, cell, bad);
         if (n > limit - pos) return;  // never past the row's place (pos <= limit always)
-        if (c.kind == OXH_COL_BOOL) {
-            if (n && lane == 0) dst[pos] = row_bit(c.values, c.vbit + r) ? 1 : 0;
-        } else {
-            const uint8_t* src = c.values + (c.kind == OXH_COL_BYTES32 || c.kind == OXH_COL_BYTES64 ? start : r * n);
-            // whole 8-byte pieces across the lanes (512 B per wave-instruction, any alignment), then the
-            // last n % 8 bytes one lane each: exactly the n bytes of the cell
-            const uint64_t whole = n & ~7ull;
-            for (uint64_t b = 8ull * lane; b < whole; b += 512) {
-                const uint64_t v = ld64u(src + b);
-                __builtin_memcpy(dst + pos + b, &v, 8);
-            }
-            if (whole + lane < n) dst[pos + whole + lane] = src[whole + lane];
-        }
+        image_put_wave<KEYED>(dst + pos, c, r, cell, lane);
         pos += n;
     }
 }
@@ -344,92 +310,30 @@ int device_enter(oxh_ctx* ctx) {
     return OXH_OK;
 }
 
-int row_error(unsigned long long e) {
+int row_error(unsigned long long e, bool keyed = false) {
     if (!e) return OXH_OK;
-    if (e & oxh::kRowErrPlan) return fail(OXH_ERR_HIP, "row hashes: the long rows changed between the length pass and the plan");
-    if (e & oxh::kRowErrOffsets) return fail(OXH_ERR_INVALID, "row hashes: a byte column's offsets decrease or are negative");
-    return fail(OXH_ERR_INVALID, "row hashes: a byte column has bytes but no values");
+    const std::string who = keyed ? "group rows" : "row hashes";
+    if (e & oxh::kRowErrPlan) return fail(OXH_ERR_HIP, who + ": the long rows changed between the length pass and the plan");
+    if (e & oxh::kRowErrOffsets) return fail(OXH_ERR_INVALID, who + ": a byte column's offsets decrease or are negative");
+    return fail(OXH_ERR_INVALID, who + ": a byte column has bytes but no values");
 }
 
 // The three steps over device-resident columns; complete on return.
 int row_hashes_run(uint64_t nrows, uint32_t ncols, const uint32_t* kinds, const void* const* d_values,
                    const void* const* d_offsets, const uint8_t* const* d_validity, const uint64_t* bit_offsets, uint64_t* d_out,
                    hipStream_t st) {
-    using oxh::RowCol;
-    const bool gather_all = g_variant.load() == kVariantGatherAll;
-    const uint32_t short_max = gather_all ? 0 : oxh::kRowShortMax;
-    const size_t ctrl_at = (ncols * sizeof(RowCol) + 63) & ~(size_t)63, bytes = ctrl_at + oxh::kCtrlWords * 8;
-    CallBlock call;
-    int rc = call.make(bytes, "row hashes");
+    RowImageCall call;
+    int rc = call.measure(false, nrows, ncols, kinds, nullptr, d_values, d_offsets, d_validity, bit_offsets, st);
     if (rc) return rc;
-    RowCol* h_cols = (RowCol*)call.h;
-    for (uint32_t c = 0; c < ncols; ++c) {
-        h_cols[c].values = (const uint8_t*)d_values[c];
-        h_cols[c].offsets = is_bytes(kinds[c]) ? (const uint8_t*)d_offsets[c] : nullptr;
-        h_cols[c].validity = d_validity[c];
-        h_cols[c].vbit = bit_offsets[2 * c];
-        h_cols[c].nbit = bit_offsets[2 * c + 1];
-        h_cols[c].kind = kinds[c];
+    if (!call.nlong) return call.hash(d_out, nullptr, st);
+    oxh::ScratchLease lease(st);  // ends (and waits for the stream) before the call's block is freed
+    void* base = nullptr;
+    if (lease.get(call.scratch_bytes(), &base) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(st);
+        return fail(OXH_ERR_NOMEM, "row hashes: arena of " + std::to_string(call.long_bytes) + " B for " + std::to_string(call.nlong) + " long rows");
     }
-    const RowCol* d_cols = (const RowCol*)call.d;
-    unsigned long long* d_ctrl = (unsigned long long*)(call.d + ctrl_at);
-    const unsigned long long* h_ctrl = (const unsigned long long*)(call.h + ctrl_at);
-    HIP_TRY(hipMemcpyAsync(call.d, call.h, bytes, hipMemcpyHostToDevice, st));
-    oxh::row_length_kernel<<<stride_grid(nrows), 256, 0, st>>>(d_cols, ncols, nrows, short_max, d_ctrl);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(call.h + ctrl_at, d_ctrl, oxh::kCtrlWords * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if ((rc = row_error(h_ctrl[oxh::kCtrlErr]))) return rc;
-    const uint64_t longest = h_ctrl[oxh::kCtrlMax], nlong = h_ctrl[oxh::kCtrlLong], long_bytes = h_ctrl[oxh::kCtrlLongBytes];
-    STEP("row hashes: %llu rows, longest %llu B, %llu long rows of %llu B", (unsigned long long)nrows,
-         (unsigned long long)longest, (unsigned long long)nlong, (unsigned long long)long_bytes);
-
-    if (nlong < nrows) {
-        // slots as long as the longest short row can be, an odd number of dwords apart: the 64 lanes of a
-        // wave on different banks, and more workgroups per CU on the common 30-100 B rows than 244 B gives
-        const uint32_t cap = (uint32_t)std::min<uint64_t>(longest, short_max);
-        const uint32_t stride = 4 * (std::max<uint32_t>(1, (cap + 3) / 4) | 1);
-        for (uint64_t at = 0; at < nrows; at += kLaunchRows) {
-            const uint64_t end = std::min(nrows, at + kLaunchRows);
-            oxh::row_hash_short_kernel<<<grid_for(end - at), 256, 256 * stride, st>>>(d_cols, ncols, at, end, stride, cap, d_out,
-                                                                                    d_ctrl);
-            HIP_TRY(hipGetLastError());
-        }
-    }
-    if (nlong) {
-        // [long_row | long_off | long_len | digests 2 | arena], the lists zeroed
-        oxh::ScratchLease lease(st);
-        const uint64_t lists = 5 * nlong * 8, arena_at = (lists + 255) & ~255ull;
-        void* base = nullptr;
-        if (lease.get(arena_at + long_bytes + 256, &base) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipStreamSynchronize(st);
-            return fail(OXH_ERR_NOMEM, "row hashes: arena of " + std::to_string(long_bytes) + " B for " + std::to_string(nlong) + " long rows");
-        }
-        uint64_t *long_row = (uint64_t*)base, *long_off = long_row + nlong, *long_len = long_off + nlong, *dig = long_len + nlong;
-        uint8_t* arena = (uint8_t*)base + arena_at;
-        HIP_TRY(hipMemsetAsync(base, 0, 3 * nlong * 8, st));
-        for (uint64_t at = 0; at < nrows; at += kLaunchRows) {
-            const uint64_t end = std::min(nrows, at + kLaunchRows);
-            oxh::row_long_plan_kernel<<<grid_for(end - at), 256, 0, st>>>(d_cols, ncols, at, end, short_max, nlong, long_bytes,
-                                                                         long_row, long_off, long_len, d_ctrl);
-            HIP_TRY(hipGetLastError());
-        }
-        oxh::row_long_gather_kernel<<<(unsigned)((nlong + 3) / 4), 256, 0, st>>>(d_cols, ncols, nlong, long_row, long_off, long_len,
-                                                                                arena);
-        HIP_TRY(hipGetLastError());
-        rc = gather_all ? launch_lane(arena, long_off, long_len, nlong, dig, st)
-                        : launch_wave(arena, long_off, long_len, nlong, dig, st, ItemShape::Packed);
-        if (rc) return rc;
-        oxh::row_long_scatter_kernel<<<grid_for(nlong), 256, 0, st>>>(long_row, dig, nlong, nrows, d_out);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(call.h + ctrl_at, d_ctrl, oxh::kCtrlWords * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));  // before the lease ends
-        return row_error(h_ctrl[oxh::kCtrlErr]);
-    }
-    HIP_TRY(hipMemcpyAsync(call.h + ctrl_at, d_ctrl, oxh::kCtrlWords * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return row_error(h_ctrl[oxh::kCtrlErr]);
+    return call.hash(d_out, base, st);
 }
 
 // ---------------------------------------------------------------- row diff
@@ -491,6 +395,109 @@ int row_diff_run(oxh_ctx* ctx, const uint64_t* d_base, uint64_t nbase, const uin
 }
 
 }  // namespace
+
+namespace oxh::capi {
+
+int RowImageCall::measure(bool keyed_image, uint64_t rows, uint32_t cols, const uint32_t* kinds, const uint32_t* orders,
+                          const void* const* d_values, const void* const* d_offsets, const uint8_t* const* d_validity,
+                          const uint64_t* bit_offsets, hipStream_t st) {
+    using oxh::RowCol;
+    keyed = keyed_image, nrows = rows, ncols = cols;
+    gather_all = g_variant.load() == kVariantGatherAll;
+    short_max = gather_all ? 0 : oxh::kRowShortMax;
+    ctrl_at = (ncols * sizeof(RowCol) + 63) & ~(size_t)63;
+    const size_t bytes = ctrl_at + oxh::kCtrlWords * 8;
+    int rc = block.make(bytes, keyed ? "group rows" : "row hashes");
+    if (rc) return rc;
+    RowCol* h_cols = (RowCol*)block.h;
+    for (uint32_t c = 0; c < ncols; ++c) {
+        h_cols[c].values = (const uint8_t*)d_values[c];
+        h_cols[c].offsets = is_bytes(kinds[c]) ? (const uint8_t*)d_offsets[c] : nullptr;
+        h_cols[c].validity = d_validity[c];
+        h_cols[c].vbit = bit_offsets[2 * c];
+        h_cols[c].nbit = bit_offsets[2 * c + 1];
+        h_cols[c].kind = kinds[c];
+        h_cols[c].order = orders ? orders[c] : 0;
+    }
+    const RowCol* d_cols = (const RowCol*)block.d;
+    unsigned long long* d_ctrl = (unsigned long long*)(block.d + ctrl_at);
+    const unsigned long long* h_ctrl = (const unsigned long long*)(block.h + ctrl_at);
+    HIP_TRY(hipMemcpyAsync(block.d, block.h, bytes, hipMemcpyHostToDevice, st));
+    if (keyed)
+        oxh::row_length_kernel<true><<<stride_grid(nrows), 256, 0, st>>>(d_cols, ncols, nrows, short_max, d_ctrl);
+    else
+        oxh::row_length_kernel<false><<<stride_grid(nrows), 256, 0, st>>>(d_cols, ncols, nrows, short_max, d_ctrl);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(block.h + ctrl_at, d_ctrl, oxh::kCtrlWords * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if ((rc = row_error(h_ctrl[oxh::kCtrlErr], keyed))) {
+        if (!keyed) return rc;
+        deferred = rc;  // the bad cells are empty cells: the call finishes and says so at the end
+    }
+    longest = h_ctrl[oxh::kCtrlMax], nlong = h_ctrl[oxh::kCtrlLong], long_bytes = h_ctrl[oxh::kCtrlLongBytes];
+    STEP("%s: %llu rows, longest %llu B, %llu long rows of %llu B", keyed ? "group rows" : "row hashes", (unsigned long long)nrows,
+         (unsigned long long)longest, (unsigned long long)nlong, (unsigned long long)long_bytes);
+    return OXH_OK;
+}
+
+// [long_row | long_off | long_len | digests 2 | arena]
+uint64_t RowImageCall::scratch_bytes() const { return nlong ? ((5 * nlong * 8 + 255) & ~255ull) + long_bytes + 256 : 0; }
+
+int RowImageCall::hash(uint64_t* d_out, void* scratch, hipStream_t st) {
+    using oxh::RowCol;
+    const RowCol* d_cols = (const RowCol*)block.d;
+    unsigned long long* d_ctrl = (unsigned long long*)(block.d + ctrl_at);
+    const unsigned long long* h_ctrl = (const unsigned long long*)(block.h + ctrl_at);
+    if (nlong < nrows) {
+        // slots as long as the longest short row can be, an odd number of dwords apart: the 64 lanes of a
+        // wave on different banks, and more workgroups per CU on the common 30-100 B rows than 244 B gives
+        const uint32_t cap = (uint32_t)std::min<uint64_t>(longest, short_max);
+        const uint32_t stride = 4 * (std::max<uint32_t>(1, (cap + 3) / 4) | 1);
+        for (uint64_t at = 0; at < nrows; at += kLaunchRows) {
+            const uint64_t end = std::min(nrows, at + kLaunchRows);
+            if (keyed)
+                oxh::row_hash_short_kernel<true><<<grid_for(end - at), 256, 256 * stride, st>>>(d_cols, ncols, at, end, stride, cap, d_out, d_ctrl);
+            else
+                oxh::row_hash_short_kernel<false><<<grid_for(end - at), 256, 256 * stride, st>>>(d_cols, ncols, at, end, stride, cap, d_out, d_ctrl);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    if (nlong) {
+        // the lists zeroed
+        void* base = scratch;
+        const uint64_t lists = 5 * nlong * 8, arena_at = (lists + 255) & ~255ull;
+        uint64_t *long_row = (uint64_t*)base, *long_off = long_row + nlong, *long_len = long_off + nlong, *dig = long_len + nlong;
+        uint8_t* arena = (uint8_t*)base + arena_at;
+        HIP_TRY(hipMemsetAsync(base, 0, 3 * nlong * 8, st));
+        for (uint64_t at = 0; at < nrows; at += kLaunchRows) {
+            const uint64_t end = std::min(nrows, at + kLaunchRows);
+            if (keyed)
+                oxh::row_long_plan_kernel<true><<<grid_for(end - at), 256, 0, st>>>(d_cols, ncols, at, end, short_max, nlong, long_bytes,
+                                                                                   long_row, long_off, long_len, d_ctrl);
+            else
+                oxh::row_long_plan_kernel<false><<<grid_for(end - at), 256, 0, st>>>(d_cols, ncols, at, end, short_max, nlong, long_bytes,
+                                                                                    long_row, long_off, long_len, d_ctrl);
+            HIP_TRY(hipGetLastError());
+        }
+        if (keyed)
+            oxh::row_long_gather_kernel<true><<<(unsigned)((nlong + 3) / 4), 256, 0, st>>>(d_cols, ncols, nlong, long_row, long_off, long_len, arena);
+        else
+            oxh::row_long_gather_kernel<false><<<(unsigned)((nlong + 3) / 4), 256, 0, st>>>(d_cols, ncols, nlong, long_row, long_off, long_len, arena);
+        HIP_TRY(hipGetLastError());
+        int rc = gather_all ? launch_lane(arena, long_off, long_len, nlong, dig, st)
+                            : launch_wave(arena, long_off, long_len, nlong, dig, st, ItemShape::Packed);
+        if (rc) return rc;
+        oxh::row_long_scatter_kernel<<<grid_for(nlong), 256, 0, st>>>(long_row, dig, nlong, nrows, d_out);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(block.h + ctrl_at, d_ctrl, oxh::kCtrlWords * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));  // before a lease ends
+    const int rc = row_error(h_ctrl[oxh::kCtrlErr], keyed);
+    if (keyed && (rc == OXH_OK || rc == OXH_ERR_INVALID)) return OXH_OK;  // `deferred` says it
+    return rc;
+}
+
+}  // namespace oxh::capi
 
 extern "C" {
 

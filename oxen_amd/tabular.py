@@ -18,6 +18,10 @@ the joined rows' indices, null indices and a fallback source (the keys' coalesce
 a stable multi-column sort of the rows on the device that returns a permutation -- `sort_indices`,
 `sort_indices_device`, `sort_by`, and `sort=True` of `diff_contents` / `diff_dfs_contents`.
 
+`oxh_group_rows_*` groups the rows of a frame by equality on key columns, which is what `oxen df --unique`,
+`--unique_count` (core/df/tabular.rs:424-433) and `n_duped_rows` (:263-271) read off -- `group_rows`,
+`group_rows_device`, `unique`, `unique_count`, `is_duplicated`, `n_duped_rows`.
+
 A frame is an ordered mapping from column name to `Column`. A row's bytes are, over the columns in the
 frame's order: nothing for a null, the raw little-endian bytes of Int8 / Int32 / Float32 / Int64 /
 Float64 / Datetime(ms), one byte 0 or 1 for a boolean, the UTF-8 bytes of a string. Every other dtype
@@ -851,6 +855,127 @@ def sort_by(frame: Mapping, name: str, orders=None, ctx: Optional[_capi.Context]
         orders = [orders]
     perm, _ = sort_indices([frame[name]], orders, ctx=ctx)
     return dict(zip(frame, take(list(frame.values()), perm, ctx=ctx)))
+
+
+# ---------------------------------------------------------------- rows grouped by equality on key columns
+class GroupStats(NamedTuple):
+    """stats4 of oxh_group_rows_*: the groups, the rows whose group has two or more rows (`is_duplicated().sum()`,
+    the reference's `n_duped_rows`), the largest group, the rows whose key image took the long path."""
+    groups: int
+    duplicated: int
+    largest: int
+    long_rows: int
+
+
+class RowGroups(NamedTuple):
+    """The grouping of a frame's rows by equality on key columns. group[i]: the smallest row whose key equals
+    row i's; count[i]: the rows of row i's group; first_idx: the rows with group[i] == i, ascending -- the
+    selection of `unique(keep="first", maintain_order=True)`, usable as idx0 of `take` -- and first_count their
+    groups' sizes, both of length stats.groups. uint32 (numpy), or int32 device tensors holding the u32 words."""
+    group: Any
+    count: Any
+    first_idx: Any
+    first_count: Any
+    stats: GroupStats
+
+
+def group_rows(columns: Sequence, orders=None, ctx: Optional[_capi.Context] = None) -> RowGroups:
+    """oxh_group_rows_host over key `Column`s (or what `column` takes) in host memory. Rows are equal when they
+    are equal in every key column: a null equals a null and nothing else, "" is not null, fixed-width cells by
+    their bytes -- under OXH_SORT_FLOAT -0.0 equals +0.0 and every NaN every NaN --, byte cells by length and
+    bytes (polars' documented `unique` / `group_by` behaviour, not pinned by a run of polars). orders: as
+    `sort_indices` takes them (None: from the dtype of `values`); only OXH_SORT_FLOAT changes the result."""
+    cols = _as_columns(columns)
+    nrows = cols[0].nrows if cols else 0
+    order_words = _orders(cols, orders)
+    keep = []
+
+    def ptr(a):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a)
+        keep.append(a)
+        return a.ctypes.data if a.size else None
+
+    outs = [np.zeros(nrows, dtype=np.uint32) for _ in range(4)]
+    stats = np.zeros(4, dtype=np.uint64)
+    _capi.check(_capi.lib().oxh_group_rows_host(_handle(ctx), nrows, len(cols), *_tables(cols, ptr), order_words,
+                                                *[o.ctypes.data if nrows else None for o in outs],
+                                                stats.ctypes.data_as(_capi._u64p)), "oxh_group_rows_host")
+    s = GroupStats(*(int(x) for x in stats))
+    return RowGroups(outs[0], outs[1], outs[2][:s.groups], outs[3][:s.groups], s)
+
+
+def group_rows_device(columns: Sequence[Column], orders=None, stream=None, ctx: Optional[_capi.Context] = None) -> RowGroups:
+    """oxh_group_rows_device: `group_rows` over `Column`s whose values / offsets / validity are torch tensors on
+    the device; the four arrays are int32 device tensors holding the u32 words, first_idx / first_count views of
+    length stats.groups (first_idx as `take_device` takes its indices). Blocks."""
+    import torch
+
+    from .device import _require_cuda, _stream
+
+    cols = list(columns)
+    nrows = cols[0].nrows if cols else 0
+    if any(c.nrows != nrows for c in cols):
+        raise _capi.OxenError("the columns of a frame have one row count", _capi.OXH_ERR_INVALID)
+    order_words = _orders(cols, orders)
+    tensors = [t for c in cols for t in (c.values, c.offsets, c.validity) if t is not None]
+    _require_cuda(*tensors)
+    if any(not t.is_contiguous() for t in tensors):
+        raise _capi.OxenError("column tensors must be contiguous", _capi.OXH_ERR_INVALID)
+    device = tensors[0].device if tensors else "cuda"
+    outs = [torch.empty(nrows, dtype=torch.int32, device=device) for _ in range(4)]
+    stats = np.zeros(4, dtype=np.uint64)
+    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()  # noqa: E731
+    _capi.check(_capi.lib().oxh_group_rows_device(_handle(ctx), nrows, len(cols), *_tables(cols, ptr), order_words,
+                                                  *[ptr(o) for o in outs], stats.ctypes.data_as(_capi._u64p), _stream(stream)),
+                "oxh_group_rows_device")
+    s = GroupStats(*(int(x) for x in stats))
+    return RowGroups(outs[0], outs[1], outs[2][:s.groups], outs[3][:s.groups], s)
+
+
+def _key_columns(frame: Mapping, columns) -> tuple:
+    frame = _as_frame(frame)
+    names = [columns] if isinstance(columns, str) else list(columns)
+    if not names:
+        raise _capi.OxenError("grouping needs at least one key column", _capi.OXH_ERR_INVALID)
+    for name in names:
+        if name not in frame:
+            raise _capi.OxenError(f"key column {name!r} is not in the frame", _capi.OXH_ERR_INVALID)
+    return frame, names
+
+
+def unique(frame: Mapping, columns, ctx: Optional[_capi.Context] = None, orders=None) -> dict:
+    """`oxen df --unique columns` (core/df/tabular.rs:424-427 `unique_df`): every column of the frame at the
+    first row of each distinct key, the first occurrences in input order -- `group_rows` of the named columns,
+    then one `take` through first_idx. columns: a name or a list of names. orders: None (from the dtypes), a
+    sequence parallel to `columns`, or {name: order class}."""
+    frame, names = _key_columns(frame, columns)
+    g = group_rows([frame[name] for name in names], _sort_orders_for(names, orders), ctx=ctx)
+    return dict(zip(frame, take(list(frame.values()), g.first_idx, ctx=ctx)))
+
+
+def unique_count(frame: Mapping, columns, ctx: Optional[_capi.Context] = None, orders=None) -> dict:
+    """`oxen df --unique_count columns` (core/df/tabular.rs:429-433 `unique_count_df`): the named columns at the
+    first row of each distinct key, plus `count`, the rows of that key -- UInt32 (OXH_COL_FIXED4), as polars'
+    `len()` is. The groups come in the order of their first rows (the reference's order is unspecified)."""
+    frame, names = _key_columns(frame, columns)
+    g = group_rows([frame[name] for name in names], _sort_orders_for(names, orders), ctx=ctx)
+    out = dict(zip(names, take([frame[name] for name in names], g.first_idx, ctx=ctx)))
+    out["count"] = Column(OXH_COL_FIXED4, g.stats.groups, np.ascontiguousarray(g.first_count, dtype=np.uint32))
+    return out
+
+
+def is_duplicated(frame: Mapping, columns, ctx: Optional[_capi.Context] = None, orders=None) -> np.ndarray:
+    """polars' `select(columns).is_duplicated()`: a boolean per row, True where another row has the same key."""
+    frame, names = _key_columns(frame, columns)
+    return group_rows([frame[name] for name in names], _sort_orders_for(names, orders), ctx=ctx).count > 1
+
+
+def n_duped_rows(frame: Mapping, columns, ctx: Optional[_capi.Context] = None, orders=None) -> int:
+    """core/df/tabular.rs:263-271 `n_duped_rows`: `select(columns).is_duplicated().sum()`."""
+    frame, names = _key_columns(frame, columns)
+    return group_rows([frame[name] for name in names], _sort_orders_for(names, orders), ctx=ctx).stats.duplicated
 
 
 def _buffer(buf, dtype) -> Optional[np.ndarray]:
