@@ -684,6 +684,85 @@ int oxh_group_rows_host(oxh_ctx* ctx, uint64_t nrows, uint32_t nkeys, const uint
                         const uint32_t* orders, uint32_t* group, uint32_t* count, uint32_t* first_idx, uint32_t* first_count,
                         uint64_t* stats4);
 
+/* ---------------------------------------------------------------- row filter: `oxen df --filter` as selection indices
+ * `oxen df --filter "label == dog && min_x > 0.5"` (core/df/tabular.rs:404-422 `filter_df`, :391-402
+ * `filter_from_val`, the parser in core/df/filter.rs, the literal typing of :332-361 `val_from_str_and_dtype`)
+ * is the step of `transform_lazy` in front of `unique`, `unique_count` and `sort`. Here it is one call on the
+ * device whose result is the ascending array of the selected rows, directly usable as idx0 of
+ * oxh_take_columns_*, and / or an Arrow bitmap of them.
+ *
+ * A filter is nterms terms `column OP literal`, OP one of == != < <= > >=, joined by nterms - 1 logical operators
+ * && / ||. The operators are FOLDED LEFT TO RIGHT WITH NO PRECEDENCE: `a || b && c` is `(a || b) && c`, which is
+ * what `filter_df` builds (`expr = expr.and(chain)` / `expr.or(chain)` in a loop).
+ *
+ * Semantics. They restate polars' documented behaviour; they are NOT pinned by a run of polars.
+ *   Null cells: a term on a null cell is null, for every operator, != included (polars' `neq`, not `neq_missing`).
+ *   Three-valued logic: && and || are Kleene's -- null && false = false, null || true = true, otherwise a null is
+ *     contagious. A row is selected exactly when the folded result is TRUE; null and false rows are dropped.
+ *   Fixed-width columns compare by the canonical word of the cell (the sort's and the grouping's, from the same
+ *     code) against the same word of the literal: signed or unsigned by the column's order class;
+ *     OXH_SORT_FLOAT in numeric order with -0.0 == +0.0, every NaN equal to every NaN and greater than +inf
+ *     (polars' total-order comparisons).
+ *   Booleans compare false < true.
+ *   Byte columns compare unsigned byte-wise lexicographically, a proper prefix first; "" is a value, not null.
+ *   Literals are typed by the column, as `val_from_str_and_dtype` does. The reference panics on Int8 / Int16 /
+ *     UInt* columns (in `lit_from_any`), on Datetime, and on an unknown field; this library accepts every kind
+ *     and order class a column can have, and returns an error where the reference would panic on an unknown
+ *     field or an unparsable literal (the typing itself is the caller's: oxen_amd.tabular.filter_terms).
+ *
+ * Columns are described exactly as oxh_sort_rows_* takes them (ncols of them: kinds, values, offsets, validity,
+ * bit_offsets[2c] / [2c+1], orders[c]) and validated by the same rules in the same order; only the columns a
+ * term names are read. HOST arrays in both forms, beside those: term_col[t] (an index below ncols), term_op[t]
+ * (OXH_FILTER_EQ ..), term_word[t] (the literal of a fixed-width term: its little-endian bytes, zero-extended;
+ * of a boolean term: 0 / 1; unused for a byte term), lit_bytes and lit_offsets (nterms + 1 entries: a byte
+ * term's literal is lit_bytes[lit_offsets[t] .. lit_offsets[t+1]); a term of another kind has an empty span),
+ * logical (nterms - 1 entries of OXH_FILTER_AND / OXH_FILTER_OR; may be NULL when nterms == 1) and stats2.
+ * What the column pointers point to, idx and mask are on the device in _device and on the host in _host.
+ * Outputs, every one of which may be NULL but stats2:
+ *   idx    u32: the selected rows, ascending. The caller provides nrows entries; entries from `selected` on are
+ *          untouched. Usable as idx0 of oxh_take_columns_*.
+ *   mask   8 * ceil(nrows / 64) bytes, 8-byte aligned: an Arrow bitmap, LSB first, bit i = row i is selected;
+ *          the bits past nrows are zero. Usable as the values of a boolean column.
+ *   stats2 (host, required) = {selected rows, rows whose folded result is null}.
+ * Both forms block until complete and keep nothing (memory, leased for the call: 4.6 KiB of control words and
+ * literals; with idx 12 B per 64 rows -- the selected rows of every 64-row block and their scan -- plus 8 B per 64
+ * rows where mask is NULL: under 0.32 B per row; the host form adds the columns the terms name, as it copies them,
+ * 4 B per row of idx and the mask).
+ * OXH_ERR_INVALID, before OXH_ERR_NODEVICE (there is no CPU path), in this order: the sort's list in the sort's
+ * order over the ncols columns (a NULL kinds, values, offsets, validity, bit_offsets or orders; ncols == 0; an
+ * unknown kind, or an unknown order class of a fixed-width column; OXH_SORT_FLOAT on a width-1 column; more than
+ * 2^32 - 2 rows; with rows: NULL offsets of a byte column, NULL values -- but for a byte column whose span is
+ * empty; the device form learns that on the device); nterms == 0 or above OXH_FILTER_MAX_TERMS; a NULL term_col,
+ * term_op, term_word or lit_offsets, or a NULL logical with nterms > 1; a term_col not below ncols; an unknown
+ * operator or logical operator; a term_word above 1 for a boolean column; lit_offsets that decrease or pass
+ * OXH_FILTER_MAX_LITERAL_BYTES; NULL lit_bytes with a non-empty literal; NULL stats2; then a NULL ctx.
+ * nrows == 0 after the checks is OXH_OK: stats2 is zeroed, nothing else is touched. A failed allocation is
+ * OXH_ERR_NOMEM with the outputs untouched. Offsets must not decrease or be negative: the host form checks them
+ * (nothing is written); the device form treats a bad pair as a cell of length 0 (an empty byte cell, not a null),
+ * finishes -- the outputs and stats2 are those of the frame with that cell empty -- and returns
+ * OXH_ERR_INVALID. Neither form ever reads outside a named span. A place from the scan is checked against the
+ * selected rows and the row before it is stored through; a bad one makes the call return OXH_ERR_HIP. */
+#define OXH_FILTER_EQ 0
+#define OXH_FILTER_NE 1
+#define OXH_FILTER_LT 2
+#define OXH_FILTER_LE 3
+#define OXH_FILTER_GT 4
+#define OXH_FILTER_GE 5
+#define OXH_FILTER_AND 0
+#define OXH_FILTER_OR 1
+#define OXH_FILTER_MAX_TERMS 16
+#define OXH_FILTER_MAX_LITERAL_BYTES 4096   /* all byte literals of one call together */
+int oxh_filter_rows_device(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const uint32_t* kinds, const void* const* d_values,
+                           const void* const* d_offsets, const uint8_t* const* d_validity, const uint64_t* bit_offsets,
+                           const uint32_t* orders, uint32_t nterms, const uint32_t* term_col, const uint32_t* term_op,
+                           const uint64_t* term_word, const uint8_t* lit_bytes, const uint64_t* lit_offsets,
+                           const uint32_t* logical, uint32_t* d_idx, uint64_t* d_mask, uint64_t* stats2, void* stream);
+int oxh_filter_rows_host(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const uint32_t* kinds, const void* const* values,
+                         const void* const* offsets, const uint8_t* const* validity, const uint64_t* bit_offsets,
+                         const uint32_t* orders, uint32_t nterms, const uint32_t* term_col, const uint32_t* term_op,
+                         const uint64_t* term_word, const uint8_t* lit_bytes, const uint64_t* lit_offsets,
+                         const uint32_t* logical, uint32_t* idx, uint64_t* mask, uint64_t* stats2);
+
 /* ---------------------------------------------------------------- K2: merkle parent nodes */
 /* get_combined_hash (hasher.rs:67-80) x n on the device:
  * XXH3-128(content.to_le_bytes() || metadata.to_le_bytes()), inputs as (lo, hi) pairs. */

@@ -16,7 +16,7 @@ Modules:
                the joined rows' columns on the device (take, diff_contents, diff_dfs_contents), and the
                stable multi-column row sort (sort_indices, sort_by; `sort=True` of the contents), and the
                rows grouped by equality on key columns (group_rows, unique, unique_count, is_duplicated,
-               n_duped_rows)
+               n_duped_rows), and the rows a `--filter` selects (parse_filter, filter_terms, filter_rows, filter_df)
   procpool  -- file hashing sharded over reader processes (the open/close floor is per process)
   shard     -- multi-GPU sharding and the RCCL digest gather
   device    -- device-resident (HBM) batch entry points over torch buffers
@@ -35,7 +35,8 @@ _FROM_TABULAR = ("KeyedDiff", "STATUS_NAMES", "keyed_diff_digests", "keyed_diff_
                  "take", "take_device", "diff_contents", "diff_dfs_contents", "output_columns", "columns_to_arrow",
                  "sort_indices", "sort_indices_device", "sort_orders_from_arrow", "sort_by", "sort_diff_rows_device",
                  "RowGroups", "GroupStats", "group_rows", "group_rows_device", "unique", "unique_count", "is_duplicated",
-                 "n_duped_rows")
+                 "n_duped_rows", "FilterExpr", "FilterStats", "RowFilter", "parse_filter", "filter_terms", "filter_rows",
+                 "filter_rows_device", "filter_df")
 
 
 def __getattr__(name):

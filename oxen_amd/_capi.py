@@ -49,6 +49,16 @@ OXH_TAKE_NO_COLUMN = 0xFFFFFFFF   # no fallback source column
 OXH_SORT_SIGNED = 0     # two's complement of the column's width
 OXH_SORT_UNSIGNED = 1   # plain unsigned of the column's width
 OXH_SORT_FLOAT = 2      # numeric; -0.0 == +0.0; every NaN equal and above +inf (widths 4 and 8)
+OXH_FILTER_EQ = 0       # the operators of a filter term, `column OP literal`
+OXH_FILTER_NE = 1
+OXH_FILTER_LT = 2
+OXH_FILTER_LE = 3
+OXH_FILTER_GT = 4
+OXH_FILTER_GE = 5
+OXH_FILTER_AND = 0      # the logical operators between terms, folded left to right
+OXH_FILTER_OR = 1
+OXH_FILTER_MAX_TERMS = 16
+OXH_FILTER_MAX_LITERAL_BYTES = 4096   # all byte literals of one call together
 
 _u64 = ctypes.c_uint64
 _u32 = ctypes.c_uint32
@@ -155,6 +165,12 @@ SIGNATURES = {
                                      ctypes.POINTER(_vp), _u64p, ctypes.POINTER(_u32), _vp, _vp, _vp, _vp, _u64p, _vp]),
     "oxh_group_rows_host": (_int, [_vp, _u64, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                                    ctypes.POINTER(_vp), _u64p, ctypes.POINTER(_u32), _vp, _vp, _vp, _vp, _u64p]),
+    "oxh_filter_rows_device": (_int, [_vp, _u64, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                      ctypes.POINTER(_vp), _u64p, ctypes.POINTER(_u32), _u32, ctypes.POINTER(_u32),
+                                      ctypes.POINTER(_u32), _u64p, _vp, _u64p, ctypes.POINTER(_u32), _vp, _vp, _u64p, _vp]),
+    "oxh_filter_rows_host": (_int, [_vp, _u64, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                    ctypes.POINTER(_vp), _u64p, ctypes.POINTER(_u32), _u32, ctypes.POINTER(_u32),
+                                    ctypes.POINTER(_u32), _u64p, _vp, _u64p, ctypes.POINTER(_u32), _vp, _vp, _u64p]),
     "oxh_comm_check": (_int, [_int]),
     "oxh_ctx_counters": (_int, [_vp, _u64p, _int]),
     "oxh_comm_unique_id": (_int, [ctypes.c_char_p]),

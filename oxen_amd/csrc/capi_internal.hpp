@@ -27,6 +27,9 @@
 //   group_rows.hip     the rows of a frame grouped by equality on key columns (oxh_group_rows_*): the digests of an
 //                      injective key image of every row (row_hash.hip's kernels, instantiated for that image), the
 //                      index's public entries, then a count, the scan and an emit
+//   filter_rows.hip    the rows a filter selects (oxh_filter_rows_*): the terms of filter_terms.hpp evaluated and
+//                      folded per row into a mask word and a count per 64-row block, the scan over those counts,
+//                      then an emit of the selected rows' indices
 // There is no CPU hashing path: every digest this library returns was computed on the GPU.
 #pragma once
 
@@ -137,7 +140,8 @@ int launch_lane(const uint8_t* arena, const uint64_t* offs, const uint64_t* lens
 namespace oxh {
 // d_out[i] = d_in[0] + ... + d_in[i-1] over n u32, as u64, enqueued on `st` (three launches; no workgroup
 // waits for another). d_sums: scan_tiles(n) + 1 words of device scratch; the last receives the total.
-// Callers: the keyed diff's pair offsets, the take's byte-column offsets (take_columns.hip).
+// Callers: the keyed diff's pair offsets, the take's byte-column offsets (take_columns.hip), the grouping's
+// first occurrences (group_rows.hip), the filter's per-block counts (filter_rows.hip).
 uint64_t scan_tiles(uint64_t n);
 int exclusive_scan_u32(const uint32_t* d_in, uint64_t n, uint64_t* d_out, unsigned long long* d_sums, hipStream_t st);
 }  // namespace oxh

@@ -24,6 +24,8 @@ struct ScratchCache {
     uint64_t size = 0;
     hipStream_t aux = nullptr;  // a second stream for the lease holder (created on first use)
     hipEvent_t ev[4] = {};
+    void* pinned = nullptr;  // a small pinned host block for the lease holder (made on first use, kept)
+    uint64_t pinned_size = 0;
 };
 
 // Two buffers per device, so two calls on different streams (say FastCDC chunking and the K1L
@@ -83,6 +85,20 @@ class ScratchLease {
         return hipSuccess;
     }
     uint64_t size() const { return cache_->size; }
+    // At least `bytes` of pinned host memory, valid until the lease ends and kept with the buffer: a call's
+    // few control words and small tables, so that a short call allocates nothing once it has run.
+    hipError_t pinned(uint64_t bytes, void** out) {
+        if (cache_->pinned_size < bytes) {
+            if (cache_->pinned) (void)hipHostFree(cache_->pinned);
+            cache_->pinned = nullptr;
+            cache_->pinned_size = 0;
+            const hipError_t e = hipHostMalloc(&cache_->pinned, bytes, hipHostMallocDefault);
+            if (e != hipSuccess) return e;
+            cache_->pinned_size = bytes;
+        }
+        *out = cache_->pinned;
+        return hipSuccess;
+    }
     // A stream of this scratch buffer's own, for work the caller overlaps with its stream, and four
     // events to order the two (created on first use, kept with the buffer).
     hipError_t aux(hipStream_t* s, hipEvent_t** ev) {

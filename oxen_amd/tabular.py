@@ -22,6 +22,11 @@ a stable multi-column sort of the rows on the device that returns a permutation 
 `--unique_count` (core/df/tabular.rs:424-433) and `n_duped_rows` (:263-271) read off -- `group_rows`,
 `group_rows_device`, `unique`, `unique_count`, `is_duplicated`, `n_duped_rows`.
 
+`oxh_filter_rows_*` is `oxen df --filter` (core/df/tabular.rs:404-422 `filter_df`, the parser of
+core/df/filter.rs): the rows for which terms `column OP literal`, joined by && / || and folded left to right,
+give true, as ascending row indices for the take and / or an Arrow bitmap -- `parse_filter`, `filter_terms`,
+`filter_rows`, `filter_rows_device`, `filter_df`.
+
 A frame is an ordered mapping from column name to `Column`. A row's bytes are, over the columns in the
 frame's order: nothing for a null, the raw little-endian bytes of Int8 / Int32 / Float32 / Int64 /
 Float64 / Datetime(ms), one byte 0 or 1 for a boolean, the UTF-8 bytes of a string. Every other dtype
@@ -31,6 +36,7 @@ byte column (polars' Display is not restated here). Cells are not delimited, as 
 from __future__ import annotations
 
 import ctypes
+import re
 from typing import Any, Mapping, NamedTuple, Optional, Sequence
 
 import numpy as np
@@ -976,6 +982,259 @@ def n_duped_rows(frame: Mapping, columns, ctx: Optional[_capi.Context] = None, o
     """core/df/tabular.rs:263-271 `n_duped_rows`: `select(columns).is_duplicated().sum()`."""
     frame, names = _key_columns(frame, columns)
     return group_rows([frame[name] for name in names], _sort_orders_for(names, orders), ctx=ctx).stats.duplicated
+
+
+# ---------------------------------------------------------------- row filter: `oxen df --filter`
+FILTER_OPS = {"==": _capi.OXH_FILTER_EQ, "!=": _capi.OXH_FILTER_NE, "<": _capi.OXH_FILTER_LT, "<=": _capi.OXH_FILTER_LE,
+              ">": _capi.OXH_FILTER_GT, ">=": _capi.OXH_FILTER_GE}
+FILTER_LOGICAL = {"&&": _capi.OXH_FILTER_AND, "||": _capi.OXH_FILTER_OR}
+_FILTER_OP_SEARCH = ("!=", ">=", "<=", "==", ">", "<")   # filter.rs:130-137: the longer operators first
+_INT_LITERAL = re.compile(r"[+-]?[0-9]+\Z")
+# Rust's f64 / f32 FromStr: no underscores, no blanks; inf, infinity and nan in any letter case
+_FLOAT_LITERAL = re.compile(r"[+-]?(?:inf|infinity|nan|(?:[0-9]+\.?[0-9]*|\.[0-9]+)(?:e[+-]?[0-9]+)?)\Z", re.IGNORECASE)
+
+
+class FilterExpr(NamedTuple):
+    """A parsed `--filter`: terms = [(field, op, value)] with op one of == != < <= > >= and value still a
+    string; logical = the "&&" / "||" between them, one fewer. They are folded left to right, no precedence."""
+    terms: list
+    logical: list
+
+
+class FilterStats(NamedTuple):
+    """stats2 of oxh_filter_rows_*: the selected rows, and the rows whose folded result is null (dropped)."""
+    selected: int
+    null_rows: int
+
+
+class RowFilter(NamedTuple):
+    """The rows a filter selects. idx: those rows, ascending, of length stats.selected, usable as idx0 of `take`
+    (uint32 numpy, or an int32 device tensor holding the u32 words); mask: an Arrow bitmap of them, LSB first,
+    8 * ceil(nrows / 64) bytes with the bits past nrows zero, usable as a boolean column's values (uint8). Either
+    is None when it was not asked for."""
+    idx: Any
+    mask: Any
+    stats: FilterStats
+
+
+def parse_filter(expr: str) -> FilterExpr:
+    """core/df/filter.rs:97-158 `parse`, restated: split at the earliest "&&" / "||" again and again, trim every
+    sub-expression, look in it for the operators in the order != >= <= == > < by containment, split on the first
+    one found, trim, and take parts 0 and 1 as field and value. An empty string is an error, as there; so is a
+    sub-expression without an operator, which the reference drops and then panics on."""
+    if not isinstance(expr, str) or expr == "":
+        raise _capi.OxenError(f"cannot parse the filter {expr!r}", _capi.OXH_ERR_INVALID)
+    rest, subs, logical = expr, [], []
+    while True:
+        found = [(at, op) for op in ("&&", "||") for at in [rest.find(op)] if at >= 0]
+        if not found:
+            break
+        at, op = min(found)
+        subs.append(rest[:at].strip())
+        logical.append(op)
+        rest = rest[at + len(op):]
+    subs.append(rest.strip())
+    terms = []
+    for sub in subs:
+        op = next((o for o in _FILTER_OP_SEARCH if o in sub), None)
+        if op is None:
+            raise _capi.OxenError(f"the filter's sub-expression {sub!r} has no operator (== != < <= > >=)", _capi.OXH_ERR_INVALID)
+        parts = [p.strip() for p in sub.split(op)]
+        terms.append((parts[0], op, parts[1]))
+    return FilterExpr(terms, logical)
+
+
+def _round_to_f32(text: str) -> np.float32:
+    """The f32 nearest to the decimal `text`, ties to even, as Rust's `f32::from_str` gives it -- not the f64
+    nearest to it rounded once more."""
+    from fractions import Fraction
+
+    d = float(text)
+    with np.errstate(over="ignore"):
+        near = np.float32(d)
+    if not np.isfinite(d) or d == 0.0:     # inf, nan, and what overflows or underflows f64 does so in f32
+        return near
+    exact = Fraction(text)
+    top = Fraction(float(np.finfo(np.float32).max))
+    if abs(exact) >= top + Fraction(2) ** 103:   # half an ulp above the largest f32: infinity
+        return np.float32(np.copysign(np.inf, d))
+    near = np.float32(np.copysign(float(top), d)) if np.isinf(near) else near
+    best = None
+    with np.errstate(over="ignore"):
+        around = (np.nextafter(near, np.float32(-np.inf)), near, np.nextafter(near, np.float32(np.inf)))
+    for cand in around:
+        if not np.isfinite(cand):
+            continue
+        key = (abs(Fraction(float(cand)) - exact), int(cand.view(np.uint32)) & 1)   # the distance, then the even mantissa
+        if best is None or key < best[0]:
+            best = (key, cand)
+    return -abs(best[1]) if d < 0 else abs(best[1])   # a tiny value that rounds to zero keeps its sign
+
+
+def _filter_literal(c: Column, order: int, value: str, what: str):
+    """The literal of one term typed by its column (core/df/tabular.rs:332-361 `val_from_str_and_dtype`): an int
+    (the ABI's term_word) or bytes (a byte column's literal)."""
+    import struct
+
+    def bad(expected):
+        return _capi.OxenError(f"{what}: {value!r} is not {expected}", _capi.OXH_ERR_INVALID)
+
+    if c.kind in _BYTES:
+        return value.encode("utf-8")
+    if c.kind == OXH_COL_BOOL:
+        if value not in ("true", "false"):
+            raise bad("a boolean (true / false)")
+        return int(value == "true")
+    width = _WIDTH[c.kind]
+    if order == OXH_SORT_FLOAT:
+        if not _FLOAT_LITERAL.match(value):
+            raise bad("a float")
+        if width == 8:
+            return struct.unpack("<Q", struct.pack("<d", float(value)))[0]
+        return int(_round_to_f32(value).view(np.uint32))
+    if not _INT_LITERAL.match(value):
+        raise bad("an integer")
+    v, bits = int(value), 8 * width
+    lo, hi = (0, (1 << bits) - 1) if order == OXH_SORT_UNSIGNED else (-(1 << (bits - 1)), (1 << (bits - 1)) - 1)
+    if not lo <= v <= hi:
+        raise bad(f"in the range of a{'n unsigned' if order == OXH_SORT_UNSIGNED else ' signed'} {bits}-bit column")
+    return v & ((1 << bits) - 1)
+
+
+def _filter_orders(cols, orders, named) -> list:
+    """One order class per column: a column a term names reads its dtype where none is given (`_order_of`); the
+    others are not read by the call and default to OXH_SORT_SIGNED."""
+    orders = [None] * len(cols) if orders is None else list(orders)
+    if len(orders) != len(cols):
+        raise _capi.OxenError("orders has one entry per column", _capi.OXH_ERR_INVALID)
+    return [int(o) if o is not None else (_order_of(c, k) if k in named else OXH_SORT_SIGNED)
+            for k, (c, o) in enumerate(zip(cols, orders))]
+
+
+def filter_terms(frame: Mapping, expr, orders=None) -> tuple:
+    """(terms, logical) as `filter_rows` takes them, from a `--filter` string or a `FilterExpr`: every field
+    resolved to the index of its column in the frame, every literal typed by that column -- booleans exactly
+    `true` / `false`; integers `[+-]?[0-9]+` that fit the column's width and signedness; floats as Rust's
+    `FromStr` reads them, rounded to f32 for a 4-byte column; the UTF-8 bytes for a byte column. An unknown
+    field or an unparsable literal raises OxenError (OXH_ERR_INVALID), where the reference would panic. orders:
+    None (from the dtypes), a sequence parallel to the frame's columns, or {name: order class}."""
+    frame = _as_frame(frame)
+    parsed = expr if isinstance(expr, FilterExpr) else parse_filter(expr)
+    names = list(frame)
+    if len(parsed.logical) != len(parsed.terms) - 1:
+        raise _capi.OxenError("a filter has one logical operator fewer than terms", _capi.OXH_ERR_INVALID)
+    for field, op, _ in parsed.terms:
+        if field not in frame:
+            raise _capi.OxenError(f"filter field {field!r} is not in the frame", _capi.OXH_ERR_INVALID)
+        if op not in FILTER_OPS:
+            raise _capi.OxenError(f"unknown filter operator {op!r}", _capi.OXH_ERR_INVALID)
+    for op in parsed.logical:
+        if op not in FILTER_LOGICAL:
+            raise _capi.OxenError(f"unknown logical operator {op!r}", _capi.OXH_ERR_INVALID)
+    named = {names.index(field) for field, _, _ in parsed.terms}
+    per_column = [orders.get(name) for name in names] if isinstance(orders, Mapping) else orders
+    order_of = _filter_orders(list(frame.values()), per_column, named)
+    terms = []
+    for field, op, value in parsed.terms:
+        k = names.index(field)
+        terms.append((k, FILTER_OPS[op], _filter_literal(frame[field], order_of[k], value, f"filter term {field} {op} {value}")))
+    return terms, [FILTER_LOGICAL[op] for op in parsed.logical]
+
+
+def _filter_tables(cols, terms, logical, orders):
+    """The term arrays of the ABI, and the columns' order words. terms: (column index, OXH_FILTER_* operator,
+    literal) with the literal an int (term_word) or bytes; logical: OXH_FILTER_AND / OXH_FILTER_OR, one fewer."""
+    terms, logical = list(terms), [int(x) for x in logical]
+    if terms and len(logical) != len(terms) - 1:
+        raise _capi.OxenError("a filter has one logical operator fewer than terms", _capi.OXH_ERR_INVALID)
+    named = {int(t[0]) for t in terms if 0 <= int(t[0]) < len(cols)}
+    order_words = (ctypes.c_uint32 * max(len(cols), 1))(*_filter_orders(cols, orders, named))
+    n = len(terms)
+    col = (ctypes.c_uint32 * max(n, 1))(*[int(t[0]) for t in terms])
+    op = (ctypes.c_uint32 * max(n, 1))(*[int(t[1]) for t in terms])
+    words = [0 if isinstance(t[2], (bytes, bytearray)) else int(t[2]) for t in terms]
+    word = (ctypes.c_uint64 * max(n, 1))(*words)
+    literals = [bytes(t[2]) if isinstance(t[2], (bytes, bytearray)) else b"" for t in terms]
+    lit_offsets = (ctypes.c_uint64 * (n + 1))(*np.cumsum([0] + [len(b) for b in literals]).tolist())
+    lit = b"".join(literals)
+    lit_bytes = ctypes.create_string_buffer(lit, len(lit)) if lit else None
+    log = (ctypes.c_uint32 * max(len(logical), 1))(*logical)
+    return order_words, (n, col, op, word, lit_bytes, lit_offsets, log)
+
+
+def filter_rows(columns: Sequence, terms, logical=(), orders=None, want_mask: bool = False, ctx: Optional[_capi.Context] = None,
+                want_idx: bool = True) -> RowFilter:
+    """oxh_filter_rows_host over the `Column`s of a frame (or what `column` takes) in host memory: the rows for
+    which the terms `column OP literal`, folded left to right by `logical` with no precedence, give TRUE. A term
+    on a null cell is null for every operator; && and || are Kleene's; null and false rows are dropped. Fixed-width
+    cells compare by the sort's canonical word (OXH_SORT_FLOAT: -0.0 == +0.0, every NaN equal and above +inf),
+    booleans false < true, byte cells unsigned byte-wise with a proper prefix first (polars' documented behaviour,
+    not pinned by a run of polars). terms / logical: what `filter_terms` returns. orders: one OXH_SORT_* per
+    column, None entries (or None) reading the dtype of a column a term names."""
+    cols = _as_columns(columns)
+    nrows = cols[0].nrows if cols else 0
+    order_words, term_tables = _filter_tables(cols, terms, logical, orders)
+    keep = []
+
+    def ptr(a):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a)
+        keep.append(a)
+        return a.ctypes.data if a.size else None
+
+    idx = np.zeros(nrows, dtype=np.uint32) if want_idx else None
+    mask = np.zeros(-(-nrows // 64), dtype=np.uint64) if want_mask else None
+    stats = np.zeros(2, dtype=np.uint64)
+    _capi.check(_capi.lib().oxh_filter_rows_host(_handle(ctx), nrows, len(cols), *_tables(cols, ptr), order_words, *term_tables,
+                                                 idx.ctypes.data if want_idx and nrows else None,
+                                                 mask.ctypes.data if want_mask and nrows else None,
+                                                 stats.ctypes.data_as(_capi._u64p)), "oxh_filter_rows_host")
+    s = FilterStats(*(int(x) for x in stats))
+    return RowFilter(idx[:s.selected] if want_idx else None, mask.view(np.uint8) if want_mask else None, s)
+
+
+def filter_rows_device(columns: Sequence[Column], terms, logical=(), orders=None, want_mask: bool = False, stream=None,
+                       ctx: Optional[_capi.Context] = None, want_idx: bool = True) -> RowFilter:
+    """oxh_filter_rows_device: `filter_rows` over `Column`s whose values / offsets / validity are torch tensors on
+    the device; idx is a view of length stats.selected of an int32 device tensor holding the u32 words (as
+    `take_device` takes its indices), mask a uint8 device tensor. Blocks."""
+    import torch
+
+    from .device import _require_cuda, _stream
+
+    cols = list(columns)
+    nrows = cols[0].nrows if cols else 0
+    if any(c.nrows != nrows for c in cols):
+        raise _capi.OxenError("the columns of a frame have one row count", _capi.OXH_ERR_INVALID)
+    order_words, term_tables = _filter_tables(cols, terms, logical, orders)
+    tensors = [t for c in cols for t in (c.values, c.offsets, c.validity) if t is not None]
+    _require_cuda(*tensors)
+    if any(not t.is_contiguous() for t in tensors):
+        raise _capi.OxenError("column tensors must be contiguous", _capi.OXH_ERR_INVALID)
+    device = tensors[0].device if tensors else "cuda"
+    idx = torch.empty(nrows, dtype=torch.int32, device=device) if want_idx else None
+    mask = torch.empty(-(-nrows // 64), dtype=torch.int64, device=device) if want_mask else None
+    stats = np.zeros(2, dtype=np.uint64)
+    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()  # noqa: E731
+    _capi.check(_capi.lib().oxh_filter_rows_device(_handle(ctx), nrows, len(cols), *_tables(cols, ptr), order_words, *term_tables,
+                                                   ptr(idx), ptr(mask), stats.ctypes.data_as(_capi._u64p), _stream(stream)),
+                "oxh_filter_rows_device")
+    s = FilterStats(*(int(x) for x in stats))
+    return RowFilter(idx[:s.selected] if want_idx else None, mask.view(torch.uint8) if want_mask else None, s)
+
+
+def filter_df(frame: Mapping, expr, ctx: Optional[_capi.Context] = None, orders=None) -> dict:
+    """`oxen df --filter expr` (core/df/tabular.rs:404-422 `filter_df`): the frame's rows for which the filter
+    gives true, in input order, as an ordered {name: Column} -- `filter_terms`, `filter_rows`, then one `take` of
+    every column through idx. The result feeds `unique`, `unique_count` and `sort_by` as it is. expr: a
+    `--filter` string or a `FilterExpr`; orders: as `filter_terms` takes them."""
+    frame = _as_frame(frame)
+    names = list(frame)
+    terms, logical = filter_terms(frame, expr, orders)
+    per_column = [orders.get(name) for name in names] if isinstance(orders, Mapping) else orders
+    selected = filter_rows(list(frame.values()), terms, logical, per_column, ctx=ctx)
+    return dict(zip(frame, take(list(frame.values()), selected.idx, ctx=ctx)))
 
 
 def _buffer(buf, dtype) -> Optional[np.ndarray]:
