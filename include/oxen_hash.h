@@ -763,6 +763,106 @@ int oxh_filter_rows_host(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const uin
                          const uint64_t* term_word, const uint8_t* lit_bytes, const uint64_t* lit_offsets,
                          const uint32_t* logical, uint32_t* idx, uint64_t* mask, uint64_t* stats2);
 
+/* ---------------------------------------------------------------- embedding similarity: mean query, cosine, ranked rows
+ * `oxen df --find-embedding-where "id = 42" --sort-by-similarity-to embedding` and the server's nearest-neighbour
+ * endpoint (repositories/workspaces/data_frames/embeddings.rs: `embedding_from_query` :297-328 selects the rows of
+ * a WHERE clause and `get_avg_embedding` :569-641 averages their vectors; `build_similarity_query_sql` :331-358
+ * computes `array_cosine_similarity(column, query::FLOAT[d])` for every row and orders by it DESC; `query` /
+ * `nearest_neighbors` :413-567 cut one page out with LIMIT / OFFSET). The reference does this in DuckDB on the
+ * CPU. Here the three steps are three calls on the device, and each takes or returns what its neighbours do:
+ * the mean takes the idx of oxh_filter_rows_*, the similarity returns a permutation, the take gathers the page's
+ * own embedding column by the same u32 indices as oxh_take_columns_*.
+ *
+ * The column. nrows vectors of exactly dim float32 values (dim >= 1), in one of three layouts:
+ *   OXH_EMB_FIXED    Arrow FixedSizeList<float32>[dim]: row r's floats start at values + r * dim; offsets is not read;
+ *   OXH_EMB_LIST32 / OXH_EMB_LIST64   Arrow List / LargeList of float32: nrows + 1 int32 / int64 offsets that count
+ *                    ELEMENTS of values.
+ * validity (may be NULL) is an Arrow bitmap whose bit validity_bit is row 0's; a null row is a null vector.
+ * values needs 4-byte alignment only: a sliced array or an odd dim puts rows at any multiple of 4 bytes, and
+ * every row is read correctly at any of them (4-byte loads up to the row's first 16-byte boundary, 16-byte loads
+ * from there). Float64 lists and null ELEMENTS inside a vector are not representable here (`get_avg_embedding`
+ * rejects the first with ExpectedF32, DuckDB's array functions error on the second): the caller refuses them.
+ * In a list layout a VALID row whose length is not dim is never read; the call finishes, stats4 says how many
+ * such rows there are and which is the first, and the call returns OXH_ERR_INVALID (the reference's
+ * EmbeddingLengthMismatch). A null row's offsets are not looked at. No read ever goes through a decreasing or
+ * negative pair of offsets or past a row's own span: the host forms check the offsets before anything is copied
+ * (nothing is written), the device forms skip such a row, finish and return OXH_ERR_INVALID.
+ *
+ * Every entry takes the column as (layout, nrows, dim, values, offsets, validity, validity_bit); stats4 is a HOST
+ * array in both forms; everything else a pointer names is on the device in _device and on the host in _host.
+ * stats4 = {rows used (valid and of length dim), null rows, valid rows of another length, the smallest such row
+ * -- nrows when there is none}, counted over the rows the call names. All forms block until complete and keep
+ * nothing; their scratch is leased for the call. A host form copies to one device block only the span its rows
+ * name (a list column: the elements [offsets[first], offsets[last + 1])), at the caller's phase within 16 bytes,
+ * and leaves the caller's output arrays untouched unless it returns OXH_OK.
+ * OXH_ERR_INVALID, before OXH_ERR_NODEVICE (there is no CPU path), in this order: an unknown layout; dim == 0;
+ * more than 2^32 - 2 rows; with rows: values not 4-byte aligned, NULL values (in the host form of a list column:
+ * only when its span is not empty), NULL offsets of a list column, in the host form offsets that are negative or
+ * decrease; then the entry's own arguments (below); NULL stats4; in the host form an index that is not a row;
+ * then a NULL ctx. nrows == 0 (the take: nout == 0) after the checks is OXH_OK: stats4 is zeroed, nothing else
+ * is touched. A failed allocation is OXH_ERR_NOMEM with the outputs untouched.
+ *
+ * oxh_embedding_mean_*: out[d] (dim floats) = the mean of element d over the rows idx[0 .. nidx) -- ascending u32
+ * row indices, exactly what oxh_filter_rows_* writes; on the device in _device. Null rows among them are skipped
+ * and counted. With no row used out is untouched and the call is still OXH_OK (the caller says "no rows
+ * found"). An index >= nrows is OXH_ERR_INVALID and that row is never read. Arithmetic: float32 sums, then one
+ * division by the count as float32; no floating-point atomics. The rows are partitioned by nidx alone -- chunks
+ * of 64 idx entries dealt round-robin to min(ceil(nidx / 64), 1024) workgroups, whose partial sums a second
+ * kernel adds in workgroup order -- so the result is bit-identical from run to run and between the two forms.
+ * Own arguments: more than 2^32 - 2 indices; with rows and indices a NULL idx or out.
+ * The reference pushes only `array.value(0)` of every record batch, so with one batch it uses the first matching
+ * row alone; here the mean is over ALL matching rows, which is what its comment and its name say. The two
+ * agree where the clause matches one row.
+ *
+ * oxh_embedding_similarity_*: for every row the cosine similarity with `query` (dim floats; on the device in
+ * _device). The semantics restate DuckDB's `array_cosine_similarity` and `ORDER BY .. DESC` from memory; they
+ * are NOT pinned by a run of DuckDB:
+ *   dot = sum x*q, nx = sum x*x, nq = sum q*q, each summed in float32 in an unspecified order;
+ *   sim = dot / sqrtf(nx * nq) with IEEE divide and square root, then clamped to [-1, 1] by comparisons that let a
+ *   NaN through: a zero row or a zero query gives NaN, NaN and inf elements propagate as IEEE says;
+ *   a null row (and a row that is not read, above) gives a null similarity: validity bit 0, sim 0.0f.
+ * Outputs: sim (nrows float32); sim_validity (ceil(nrows / 8) bytes, an Arrow bitmap from bit 0, the bits past
+ * nrows zero; may be NULL when the column has no validity, and is all ones when given then); order_key (nrows
+ * u32, may be NULL); perm (nrows u32, may be NULL, needs order_key).
+ *   order_key is the DESCENDING order as an ascending unsigned key: for a valid row the bitwise NOT of the row
+ *   sort's float32 word of sim (OXH_SORT_FLOAT, the same code), for a null row 0xFFFFFFFF. Ascending on it: NaNs
+ *   first (DuckDB ranks NaN above every number), then +1 .. -1 with -0.0 equal to +0.0, then the nulls (DuckDB's
+ *   default NULLS LAST). The largest valid key is 0xFF800000 (-inf): no valid key equals the null key.
+ *   perm is the STABLE ascending sort of order_key -- equal similarities keep input order -- by oxh_sort_rows_device
+ *   over that one OXH_COL_FIXED4 / OXH_SORT_UNSIGNED column; perm[i] = the row at place i, usable as idx0 of
+ *   oxh_take_columns_* and as idx of oxh_embedding_take_*. In the device form perm is written even when the call
+ *   returns OXH_ERR_INVALID for rows of another length (they rank as nulls).
+ * Own arguments: perm without order_key; with rows a NULL query or sim, a column with validity and a NULL
+ * sim_validity.
+ *
+ * oxh_embedding_take_*: the page's own embedding column. idx: nout u32 row indices, OXH_TAKE_NULL = absent. The
+ * output is always in the fixed layout: out_values nout * dim floats, out_validity ceil(nout / 8) bytes from bit
+ * 0 with the bits past nout zero, always written. An absent index, a null source row and a row that is not read
+ * give dim zeros and validity bit 0 (stats4 counts all three as null rows but the last). An index that is neither
+ * absent nor below nrows is OXH_ERR_INVALID; nothing is read through it.
+ * Own arguments: more than 2^32 - 2 output rows; with output rows a NULL idx, out_values or out_validity. */
+#define OXH_EMB_FIXED 0
+#define OXH_EMB_LIST32 1
+#define OXH_EMB_LIST64 2
+int oxh_embedding_mean_device(oxh_ctx* ctx, uint32_t layout, uint64_t nrows, uint32_t dim, const void* d_values, const void* d_offsets,
+                              const uint8_t* d_validity, uint64_t validity_bit, const uint32_t* d_idx, uint64_t nidx, void* d_out,
+                              uint64_t* stats4, void* stream);
+int oxh_embedding_mean_host(oxh_ctx* ctx, uint32_t layout, uint64_t nrows, uint32_t dim, const void* values, const void* offsets,
+                            const uint8_t* validity, uint64_t validity_bit, const uint32_t* idx, uint64_t nidx, void* out,
+                            uint64_t* stats4);
+int oxh_embedding_similarity_device(oxh_ctx* ctx, uint32_t layout, uint64_t nrows, uint32_t dim, const void* d_values, const void* d_offsets,
+                                    const uint8_t* d_validity, uint64_t validity_bit, const void* d_query, void* d_sim,
+                                    uint8_t* d_sim_validity, uint32_t* d_order_key, uint32_t* d_perm, uint64_t* stats4, void* stream);
+int oxh_embedding_similarity_host(oxh_ctx* ctx, uint32_t layout, uint64_t nrows, uint32_t dim, const void* values, const void* offsets,
+                                  const uint8_t* validity, uint64_t validity_bit, const void* query, void* sim, uint8_t* sim_validity,
+                                  uint32_t* order_key, uint32_t* perm, uint64_t* stats4);
+int oxh_embedding_take_device(oxh_ctx* ctx, uint32_t layout, uint64_t nrows, uint32_t dim, const void* d_values, const void* d_offsets,
+                              const uint8_t* d_validity, uint64_t validity_bit, const uint32_t* d_idx, uint64_t nout, void* d_out_values,
+                              uint8_t* d_out_validity, uint64_t* stats4, void* stream);
+int oxh_embedding_take_host(oxh_ctx* ctx, uint32_t layout, uint64_t nrows, uint32_t dim, const void* values, const void* offsets,
+                            const uint8_t* validity, uint64_t validity_bit, const uint32_t* idx, uint64_t nout, void* out_values,
+                            uint8_t* out_validity, uint64_t* stats4);
+
 /* ---------------------------------------------------------------- K2: merkle parent nodes */
 /* get_combined_hash (hasher.rs:67-80) x n on the device:
  * XXH3-128(content.to_le_bytes() || metadata.to_le_bytes()), inputs as (lo, hi) pairs. */

@@ -16,7 +16,9 @@ Modules:
                the joined rows' columns on the device (take, diff_contents, diff_dfs_contents), and the
                stable multi-column row sort (sort_indices, sort_by; `sort=True` of the contents), and the
                rows grouped by equality on key columns (group_rows, unique, unique_count, is_duplicated,
-               n_duped_rows), and the rows a `--filter` selects (parse_filter, filter_terms, filter_rows, filter_df)
+               n_duped_rows), and the rows a `--filter` selects (parse_filter, filter_terms, filter_rows, filter_df),
+               and the embedding query: mean of the selected vectors, cosine similarity of every row, the ranked
+               page (embedding_mean, cosine_similarity, embedding_take, nearest_neighbors, sort_by_similarity)
   procpool  -- file hashing sharded over reader processes (the open/close floor is per process)
   shard     -- multi-GPU sharding and the RCCL digest gather
   device    -- device-resident (HBM) batch entry points over torch buffers
@@ -36,7 +38,10 @@ _FROM_TABULAR = ("KeyedDiff", "STATUS_NAMES", "keyed_diff_digests", "keyed_diff_
                  "sort_indices", "sort_indices_device", "sort_orders_from_arrow", "sort_by", "sort_diff_rows_device",
                  "RowGroups", "GroupStats", "group_rows", "group_rows_device", "unique", "unique_count", "is_duplicated",
                  "n_duped_rows", "FilterExpr", "FilterStats", "RowFilter", "parse_filter", "filter_terms", "filter_rows",
-                 "filter_rows_device", "filter_df")
+                 "filter_rows_device", "filter_df", "Embedding", "EmbeddingStats", "Similarity", "embedding", "embedding_from_arrow",
+                 "embedding_to_arrow", "embedding_mean", "embedding_mean_device", "cosine_similarity", "cosine_similarity_device",
+                 "embedding_take", "embedding_take_device", "page_rows", "nearest_neighbors", "nearest_neighbors_device",
+                 "sort_by_similarity", "sort_by_similarity_device")
 
 
 def __getattr__(name):

@@ -59,6 +59,9 @@ OXH_FILTER_AND = 0      # the logical operators between terms, folded left to ri
 OXH_FILTER_OR = 1
 OXH_FILTER_MAX_TERMS = 16
 OXH_FILTER_MAX_LITERAL_BYTES = 4096   # all byte literals of one call together
+OXH_EMB_FIXED = 0       # the layouts of an embedding column: Arrow FixedSizeList<float32>[dim]
+OXH_EMB_LIST32 = 1      # Arrow List<float32>: int32 offsets in elements
+OXH_EMB_LIST64 = 2      # Arrow LargeList<float32>: int64 offsets in elements
 
 _u64 = ctypes.c_uint64
 _u32 = ctypes.c_uint32
@@ -171,6 +174,12 @@ SIGNATURES = {
     "oxh_filter_rows_host": (_int, [_vp, _u64, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                                     ctypes.POINTER(_vp), _u64p, ctypes.POINTER(_u32), _u32, ctypes.POINTER(_u32),
                                     ctypes.POINTER(_u32), _u64p, _vp, _u64p, ctypes.POINTER(_u32), _vp, _vp, _u64p]),
+    "oxh_embedding_mean_device": (_int, [_vp, _u32, _u64, _u32, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _u64p, _vp]),
+    "oxh_embedding_mean_host": (_int, [_vp, _u32, _u64, _u32, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _u64p]),
+    "oxh_embedding_similarity_device": (_int, [_vp, _u32, _u64, _u32, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64p, _vp]),
+    "oxh_embedding_similarity_host": (_int, [_vp, _u32, _u64, _u32, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64p]),
+    "oxh_embedding_take_device": (_int, [_vp, _u32, _u64, _u32, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64p, _vp]),
+    "oxh_embedding_take_host": (_int, [_vp, _u32, _u64, _u32, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64p]),
     "oxh_comm_check": (_int, [_int]),
     "oxh_ctx_counters": (_int, [_vp, _u64p, _int]),
     "oxh_comm_unique_id": (_int, [ctypes.c_char_p]),

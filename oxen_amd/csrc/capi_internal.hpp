@@ -30,6 +30,10 @@
 //   filter_rows.hip    the rows a filter selects (oxh_filter_rows_*): the terms of filter_terms.hpp evaluated and
 //                      folded per row into a mask word and a count per 64-row block, the scan over those counts,
 //                      then an emit of the selected rows' indices
+//   embedding.hip      the embedding query over a column of float32 vectors (oxh_embedding_*): the mean of the
+//                      selected rows by per-workgroup partial sums added in a fixed order, the cosine similarity of
+//                      every row with its descending order key, the row sort above for the permutation, the take
+//                      of a page's vectors
 // There is no CPU hashing path: every digest this library returns was computed on the GPU.
 #pragma once
 

@@ -27,6 +27,12 @@ core/df/filter.rs): the rows for which terms `column OP literal`, joined by && /
 give true, as ascending row indices for the take and / or an Arrow bitmap -- `parse_filter`, `filter_terms`,
 `filter_rows`, `filter_rows_device`, `filter_df`.
 
+`oxh_embedding_*` is the embedding query (repositories/workspaces/data_frames/embeddings.rs `query`,
+`nearest_neighbors`, `get_avg_embedding`): the mean of the vectors the filter selects, the cosine similarity of
+every row with it, the rows ranked from the most similar on and one page of them with its own vectors --
+`Embedding`, `embedding`, `embedding_from_arrow`, `embedding_mean`, `cosine_similarity`, `embedding_take`,
+`nearest_neighbors`, `sort_by_similarity`, each with a `_device` twin.
+
 A frame is an ordered mapping from column name to `Column`. A row's bytes are, over the columns in the
 frame's order: nothing for a null, the raw little-endian bytes of Int8 / Int32 / Float32 / Int64 /
 Float64 / Datetime(ms), one byte 0 or 1 for a boolean, the UTF-8 bytes of a string. Every other dtype
@@ -1305,3 +1311,346 @@ def columns_to_arrow(columns: Mapping, schema):
             buffers = [validity, as_buffer(c.offsets), values] if c.kind in _BYTES else [validity, values]
         arrays.append(pa.Array.from_buffers(field.type, n, buffers))
     return pa.Table.from_arrays(arrays, schema=schema)
+
+
+# ---------------------------------------------------------------- embedding similarity: mean query, cosine, ranked rows
+class Embedding(NamedTuple):
+    """A column of `nrows` vectors of exactly `dim` float32 values as `oxh_embedding_*` takes it (numpy arrays for
+    the host forms, torch tensors on the device for the device forms). layout: OXH_EMB_FIXED (row r's floats
+    start at values[r * dim]), OXH_EMB_LIST32 / OXH_EMB_LIST64 (nrows + 1 int32 / int64 offsets that count
+    elements of values); values: float32, one-dimensional; validity: an Arrow validity bitmap (uint8) or None
+    for no nulls -- a null row is a null vector; validity_bit: the bit of row 0 in validity."""
+    layout: int
+    dim: int
+    nrows: int
+    values: Any
+    offsets: Any = None
+    validity: Any = None
+    validity_bit: int = 0
+
+
+class EmbeddingStats(NamedTuple):
+    """stats4 of oxh_embedding_*: rows used (valid and of length dim), null rows, valid rows of another length,
+    the smallest such row (nrows when there is none)."""
+    used: int
+    null_rows: int
+    wrong_length: int
+    first_wrong: int
+
+
+class Similarity(NamedTuple):
+    """What `cosine_similarity` returns: sim (float32 per row, 0.0 for a null), validity (an Arrow bitmap from bit
+    0, uint8; None when the column has no validity), order_key (uint32: the descending order as an ascending
+    key), perm (uint32: the rows from the most similar on -- NaNs, then +1 .. -1, then nulls, ties in input
+    order), stats. order_key and perm are None when the order was not asked for."""
+    sim: Any
+    validity: Any
+    order_key: Any
+    perm: Any
+    stats: EmbeddingStats
+
+
+def embedding(values_2d, validity=None) -> Embedding:
+    """An Embedding in the fixed layout from an (nrows, dim) array of float32 (anything else is cast).
+    validity: a boolean mask (True = present) or None."""
+    a = np.ascontiguousarray(values_2d, dtype=np.float32)
+    if a.ndim != 2 or a.shape[1] < 1:
+        raise _capi.OxenError("an embedding column is an (nrows, dim) array with dim >= 1", _capi.OXH_ERR_INVALID)
+    return Embedding(_capi.OXH_EMB_FIXED, int(a.shape[1]), int(a.shape[0]), a.reshape(-1), None,
+                     None if validity is None else _pack(validity), 0)
+
+
+def embedding_from_arrow(array, dim: Optional[int] = None) -> Embedding:
+    """An Embedding over the buffers of a pyarrow FixedSizeList / List / LargeList array of float32: sliced and
+    chunked arrays included (only a chunked array's chunks are copied), the child array's own offset honoured.
+    dim: the vectors' length for the list layouts (None: that of the first valid row); a valid row of another
+    length is what the calls refuse. Float64 children (`get_avg_embedding`'s ExpectedF32), null elements inside
+    a vector and every other type raise OxenError (OXH_ERR_INVALID)."""
+    import pyarrow as pa
+
+    if isinstance(array, pa.ChunkedArray):
+        array = array.combine_chunks() if array.num_chunks != 1 else array.chunk(0)
+    t, n, off = array.type, len(array), array.offset
+    fixed, wide = pa.types.is_fixed_size_list(t), pa.types.is_large_list(t)
+    if not (fixed or wide or pa.types.is_list(t)):
+        raise _capi.OxenError(f"Arrow type {t} is not a list of float32", _capi.OXH_ERR_INVALID)
+    if t.value_type != pa.float32():
+        raise _capi.OxenError(f"an embedding holds float32 values, not {t.value_type} (the reference's ExpectedF32)", _capi.OXH_ERR_INVALID)
+    bufs = array.buffers()
+    validity = _buffer(bufs[0], np.uint8) if array.null_count else None
+    vbit = off if validity is not None else 0
+    child = array.values   # the whole child array, before the parent's offset
+    data = _buffer(child.buffers()[1], np.float32)
+    data = np.zeros(0, dtype=np.float32) if data is None else data[child.offset:child.offset + len(child)]
+    present = np.ones(n, dtype=bool) if validity is None else np.unpackbits(validity, bitorder="little")[vbit:vbit + n].astype(bool)
+    if fixed:
+        d = int(t.list_size)
+        lo, hi = off * d, (off + n) * d
+        layout, offsets, values = _capi.OXH_EMB_FIXED, None, data[lo:hi]
+        lengths = np.full(n, d, dtype=np.int64)
+    else:
+        odt = np.int64 if wide else np.int32
+        offsets = _buffer(bufs[1], odt)
+        offsets = offsets[off:off + n + 1] if offsets is not None else np.zeros(n + 1, dtype=odt)
+        layout, values = (_capi.OXH_EMB_LIST64 if wide else _capi.OXH_EMB_LIST32), data
+        lo, hi = (int(offsets[0]), int(offsets[-1])) if n else (0, 0)
+        lengths = np.diff(offsets.astype(np.int64))
+        d = int(dim) if dim is not None else (int(lengths[present][0]) if present.any() else 1)
+    if d < 1:
+        raise _capi.OxenError("an embedding has at least one element per row", _capi.OXH_ERR_INVALID)
+    if child.null_count and hi > lo and child.slice(lo, hi - lo).null_count:
+        # a null row's own slots may be null; an element of a valid row may not
+        element_valid = child.slice(lo, hi - lo).is_valid().to_numpy(zero_copy_only=False)
+        if lengths.min() < 0 or int(lengths.sum()) != hi - lo or (~element_valid & np.repeat(present, lengths)).any():
+            raise _capi.OxenError("null elements inside a vector are not supported", _capi.OXH_ERR_INVALID)
+    return Embedding(layout, d, n, values, offsets, validity, vbit)
+
+
+def embedding_to_arrow(emb: Embedding):
+    """A pyarrow FixedSizeList<float32>[dim] array over the buffers of a fixed-layout Embedding in host memory with
+    its validity at bit 0 (what `embedding_take` returns)."""
+    import pyarrow as pa
+
+    if emb.layout != _capi.OXH_EMB_FIXED or emb.validity_bit:
+        raise _capi.OxenError("embedding_to_arrow takes the fixed layout with validity from bit 0", _capi.OXH_ERR_INVALID)
+    child = pa.Array.from_buffers(pa.float32(), emb.nrows * emb.dim, [None, pa.py_buffer(np.ascontiguousarray(emb.values, dtype=np.float32))])
+    validity = None if emb.validity is None else pa.py_buffer(np.ascontiguousarray(emb.validity))
+    return pa.Array.from_buffers(pa.list_(pa.float32(), emb.dim), emb.nrows, [validity], children=[child])
+
+
+def _embedding_args(emb: Embedding, ptr):
+    return (int(emb.layout), int(emb.nrows), int(emb.dim), ptr(emb.values), ptr(emb.offsets) if emb.layout != _capi.OXH_EMB_FIXED else None,
+            ptr(emb.validity), int(emb.validity_bit))
+
+
+def _host_ptr(keep):
+    def ptr(a):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a)
+        keep.append(a)
+        return a.ctypes.data if a.size else None
+    return ptr
+
+
+def _embedding_tensors(emb: Embedding, *more):
+    from .device import _require_cuda
+
+    tensors = [t for t in (emb.values, emb.offsets, emb.validity) + more if t is not None]
+    _require_cuda(*tensors)
+    if any(not t.is_contiguous() for t in tensors):
+        raise _capi.OxenError("embedding tensors must be contiguous", _capi.OXH_ERR_INVALID)
+    return tensors[0].device if tensors else "cuda"
+
+
+_device_ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()  # noqa: E731
+
+
+def _no_rows(stats: EmbeddingStats):
+    if stats.used == 0:
+        raise _capi.OxenError("no rows found: the query selects no row with an embedding", _capi.OXH_ERR_INVALID)
+
+
+def embedding_mean(emb: Embedding, idx, ctx: Optional[_capi.Context] = None):
+    """oxh_embedding_mean_host: (mean, EmbeddingStats) -- the element-wise float32 mean of the rows idx (ascending
+    u32 row indices: what `filter_rows` returns) of an Embedding in host memory, null rows skipped. The reference's
+    `get_avg_embedding`, over ALL matching rows (it pushes only the first row of every record batch; the two
+    agree where one row matches). Bit-identical from run to run and with the device form. Raises the reference's
+    "no rows found" when no row is used."""
+    i = np.ascontiguousarray(idx, dtype=np.uint32)
+    keep = []
+    ptr = _host_ptr(keep)
+    out = np.zeros(emb.dim, dtype=np.float32)
+    stats = np.zeros(4, dtype=np.uint64)
+    _capi.check(_capi.lib().oxh_embedding_mean_host(_handle(ctx), *_embedding_args(emb, ptr), ptr(i), i.size, out.ctypes.data,
+                                                    stats.ctypes.data_as(_capi._u64p)), "oxh_embedding_mean_host")
+    s = EmbeddingStats(*(int(x) for x in stats))
+    _no_rows(s)
+    return out, s
+
+
+def embedding_mean_device(emb: Embedding, idx, stream=None, ctx: Optional[_capi.Context] = None):
+    """oxh_embedding_mean_device: `embedding_mean` over an Embedding of device tensors and idx as a 32-bit device
+    tensor (the idx of `filter_rows_device` as it is); the mean is a float32 device tensor. Blocks."""
+    import torch
+
+    from .device import _stream
+
+    device = _embedding_tensors(emb, idx)
+    if idx.element_size() != 4 or idx.dim() != 1:
+        raise _capi.OxenError("idx is a one-dimensional 32-bit tensor", _capi.OXH_ERR_INVALID)
+    out = torch.empty(emb.dim, dtype=torch.float32, device=device)
+    stats = np.zeros(4, dtype=np.uint64)
+    _capi.check(_capi.lib().oxh_embedding_mean_device(_handle(ctx), *_embedding_args(emb, _device_ptr), _device_ptr(idx), idx.numel(),
+                                                      out.data_ptr(), stats.ctypes.data_as(_capi._u64p), _stream(stream)),
+                "oxh_embedding_mean_device")
+    s = EmbeddingStats(*(int(x) for x in stats))
+    _no_rows(s)
+    return out, s
+
+
+def cosine_similarity(emb: Embedding, query, want_order: bool = True, ctx: Optional[_capi.Context] = None) -> Similarity:
+    """oxh_embedding_similarity_host: the cosine similarity of every row of an Embedding in host memory with
+    `query` (dim float32) -- dot / sqrtf(nx * nq) in float32, clamped to [-1, 1]; a zero row or query gives NaN; a
+    null row a null similarity -- and, with want_order, the descending order: order_key and the stable perm (NaNs
+    first, then +1 .. -1, nulls last, ties in input order). Restates DuckDB's `array_cosine_similarity` and
+    `ORDER BY .. DESC`; not pinned by a run of DuckDB."""
+    q = np.ascontiguousarray(query, dtype=np.float32).reshape(-1)
+    if q.size != emb.dim:
+        raise _capi.OxenError(f"the query has {q.size} elements, the column's vectors {emb.dim}", _capi.OXH_ERR_INVALID)
+    n = int(emb.nrows)
+    keep = []
+    ptr = _host_ptr(keep)
+    sim = np.zeros(n, dtype=np.float32)
+    validity = np.zeros(-(-n // 8), dtype=np.uint8) if emb.validity is not None else None
+    key = np.zeros(n, dtype=np.uint32) if want_order else None
+    perm = np.zeros(n, dtype=np.uint32) if want_order else None
+    stats = np.zeros(4, dtype=np.uint64)
+    addr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+    _capi.check(_capi.lib().oxh_embedding_similarity_host(_handle(ctx), *_embedding_args(emb, ptr), ptr(q), addr(sim), addr(validity),
+                                                          addr(key), addr(perm), stats.ctypes.data_as(_capi._u64p)),
+                "oxh_embedding_similarity_host")
+    return Similarity(sim, validity, key, perm, EmbeddingStats(*(int(x) for x in stats)))
+
+
+def cosine_similarity_device(emb: Embedding, query, want_order: bool = True, stream=None, ctx: Optional[_capi.Context] = None) -> Similarity:
+    """oxh_embedding_similarity_device: `cosine_similarity` over an Embedding of device tensors and a float32 device
+    query; sim is a float32 device tensor, validity uint8, order_key and perm int32 tensors holding the u32 words
+    (perm as `take_device` takes its indices). Blocks."""
+    import torch
+
+    from .device import _stream
+
+    device = _embedding_tensors(emb, query)
+    if query.dtype != torch.float32 or query.numel() != emb.dim:
+        raise _capi.OxenError(f"the query is {emb.dim} float32 values", _capi.OXH_ERR_INVALID)
+    n = int(emb.nrows)
+    sim = torch.empty(n, dtype=torch.float32, device=device)
+    validity = torch.empty(-(-n // 8), dtype=torch.uint8, device=device) if emb.validity is not None else None
+    key = torch.empty(n, dtype=torch.int32, device=device) if want_order else None
+    perm = torch.empty(n, dtype=torch.int32, device=device) if want_order else None
+    stats = np.zeros(4, dtype=np.uint64)
+    _capi.check(_capi.lib().oxh_embedding_similarity_device(_handle(ctx), *_embedding_args(emb, _device_ptr), _device_ptr(query),
+                                                            _device_ptr(sim), _device_ptr(validity), _device_ptr(key), _device_ptr(perm),
+                                                            stats.ctypes.data_as(_capi._u64p), _stream(stream)),
+                "oxh_embedding_similarity_device")
+    return Similarity(sim, validity, key, perm, EmbeddingStats(*(int(x) for x in stats)))
+
+
+def embedding_take(emb: Embedding, idx, ctx: Optional[_capi.Context] = None) -> Embedding:
+    """oxh_embedding_take_host: the rows idx (u32 with OXH_TAKE_NULL, or signed with a negative value, for an absent
+    row) of an Embedding in host memory as a fresh Embedding in the fixed layout, validity always present from bit
+    0; an absent index and a null source row give zeros and a null."""
+    i = _host_index(idx)
+    keep = []
+    ptr = _host_ptr(keep)
+    values = np.zeros(i.size * emb.dim, dtype=np.float32)
+    validity = np.zeros(-(-i.size // 8), dtype=np.uint8)
+    stats = np.zeros(4, dtype=np.uint64)
+    addr = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+    _capi.check(_capi.lib().oxh_embedding_take_host(_handle(ctx), *_embedding_args(emb, ptr), ptr(i), i.size, addr(values), addr(validity),
+                                                    stats.ctypes.data_as(_capi._u64p)), "oxh_embedding_take_host")
+    return Embedding(_capi.OXH_EMB_FIXED, emb.dim, int(i.size), values, None, validity, 0)
+
+
+def embedding_take_device(emb: Embedding, idx, stream=None, ctx: Optional[_capi.Context] = None) -> Embedding:
+    """oxh_embedding_take_device: `embedding_take` over an Embedding of device tensors and idx as a 32-bit device
+    tensor holding the u32 words (-1 is OXH_TAKE_NULL); a fixed-layout Embedding over fresh device tensors. Blocks."""
+    import torch
+
+    from .device import _stream
+
+    device = _embedding_tensors(emb, idx)
+    if idx.element_size() != 4 or idx.dim() != 1:
+        raise _capi.OxenError("idx is a one-dimensional 32-bit tensor", _capi.OXH_ERR_INVALID)
+    n = int(idx.numel())
+    values = torch.empty(n * emb.dim, dtype=torch.float32, device=device)
+    validity = torch.empty(-(-n // 8), dtype=torch.uint8, device=device)
+    stats = np.zeros(4, dtype=np.uint64)
+    _capi.check(_capi.lib().oxh_embedding_take_device(_handle(ctx), *_embedding_args(emb, _device_ptr), _device_ptr(idx), n, _device_ptr(values),
+                                                      _device_ptr(validity), stats.ctypes.data_as(_capi._u64p), _stream(stream)),
+                "oxh_embedding_take_device")
+    return Embedding(_capi.OXH_EMB_FIXED, emb.dim, n, values, None, validity, 0)
+
+
+def page_rows(nrows: int, page_size: int, page_num: int = 1) -> tuple:
+    """(first, count) of `LIMIT page_size OFFSET (page_num - 1) * page_size` over nrows ranked rows, clipped to the
+    frame; page_num 0 means 1 (embeddings.rs `nearest_neighbors`)."""
+    nrows, page_size, page_num = int(nrows), int(page_size), int(page_num)
+    if nrows < 0 or page_size < 0 or page_num < 0:
+        raise _capi.OxenError("nrows, page_size and page_num are not negative", _capi.OXH_ERR_INVALID)
+    first = min((max(page_num, 1) - 1) * page_size, nrows)
+    return first, min(page_size, nrows - first)
+
+
+def _check_frame_rows(frame, emb):
+    for name, c in frame.items():
+        if c.nrows != emb.nrows:
+            raise _capi.OxenError(f"column {name!r} has {c.nrows} rows, the embedding column {emb.nrows}", _capi.OXH_ERR_INVALID)
+
+
+def nearest_neighbors(frame: Mapping, emb: Embedding, query, page_size: int, page_num: int = 1, name: str = "similarity",
+                      ctx: Optional[_capi.Context] = None, embedding_name: str = "embedding") -> dict:
+    """embeddings.rs `nearest_neighbors` (:413-567) over a frame and its embedding column in host memory: the
+    similarity of every row with `query`, the rows ranked from the most similar on, and page `page_num` of
+    `page_size` rows (0 means 1; clipped to the frame) as an ordered dict -- the frame's columns through `take`,
+    `embedding_name`: the page's own vectors (`embedding_take`, a fixed-layout Embedding), and `name`: a float32
+    Column with its validity."""
+    frame = _as_frame(frame)
+    _check_frame_rows(frame, emb)
+    ranked = cosine_similarity(emb, query, ctx=ctx)
+    first, count = page_rows(emb.nrows, page_size, page_num)
+    rows = ranked.perm[first:first + count]
+    sim = Column(OXH_COL_FIXED4, emb.nrows, ranked.sim, None, ranked.validity, 0, 0)
+    taken = take(list(frame.values()) + [sim], rows, ctx=ctx)
+    page = dict(zip(frame, taken))
+    page[embedding_name] = embedding_take(emb, rows, ctx=ctx)
+    page[name] = taken[-1]
+    return page
+
+
+def nearest_neighbors_device(frame: Mapping, emb: Embedding, query, page_size: int, page_num: int = 1, name: str = "similarity",
+                             stream=None, ctx: Optional[_capi.Context] = None, embedding_name: str = "embedding") -> dict:
+    """`nearest_neighbors` over device tensors: similarity, the sort, the page's rows (a view of perm), the take of
+    the columns and of the vectors all stay on the device; only counts and sizes cross the link. Blocks."""
+    frame = dict(frame)
+    _check_frame_rows(frame, emb)
+    ranked = cosine_similarity_device(emb, query, stream=stream, ctx=ctx)
+    first, count = page_rows(emb.nrows, page_size, page_num)
+    rows = ranked.perm[first:first + count]
+    sim = Column(OXH_COL_FIXED4, emb.nrows, ranked.sim, None, ranked.validity, 0, 0)
+    taken = take_device(list(frame.values()) + [sim], rows, stream=stream, ctx=ctx)
+    page = dict(zip(frame, taken))
+    page[embedding_name] = embedding_take_device(emb, rows, stream=stream, ctx=ctx)
+    page[name] = taken[-1]
+    return page
+
+
+def sort_by_similarity(frame: Mapping, emb: Embedding, where, page_size: int, page_num: int = 1, name: str = "similarity",
+                       ctx: Optional[_capi.Context] = None, orders=None, embedding_name: str = "embedding") -> dict:
+    """embeddings.rs `query` (`oxen df --find-embedding-where where --sort-by-similarity-to column`): the rows `where`
+    selects, the mean of their vectors, then `nearest_neighbors` of that mean. Two differences from the reference:
+    `where` is this project's `--filter` grammar (`filter_terms`: `id == 42`, `label == dog && score > 0.5`), not
+    SQL; and the mean is over ALL the selected rows, where the reference's `get_avg_embedding` takes only the
+    first row of every record batch (its comment and name say average) -- the two agree where one row matches.
+    Raises "no rows found" when the clause selects no row with an embedding."""
+    frame = _as_frame(frame)
+    _check_frame_rows(frame, emb)
+    terms, logical = filter_terms(frame, where, orders)
+    per_column = [orders.get(n) for n in frame] if isinstance(orders, Mapping) else orders
+    selected = filter_rows(list(frame.values()), terms, logical, per_column, ctx=ctx)
+    mean, _ = embedding_mean(emb, selected.idx, ctx=ctx)
+    return nearest_neighbors(frame, emb, mean, page_size, page_num, name, ctx=ctx, embedding_name=embedding_name)
+
+
+def sort_by_similarity_device(frame: Mapping, emb: Embedding, where, page_size: int, page_num: int = 1, name: str = "similarity",
+                              stream=None, ctx: Optional[_capi.Context] = None, orders=None, embedding_name: str = "embedding") -> dict:
+    """`sort_by_similarity` over device tensors: the filter's idx, the mean, the similarities, the permutation and
+    the page stay on the device from end to end; nothing row-shaped is copied to the host. Blocks."""
+    frame = dict(frame)
+    _check_frame_rows(frame, emb)
+    terms, logical = filter_terms(frame, where, orders)
+    per_column = [orders.get(n) for n in frame] if isinstance(orders, Mapping) else orders
+    selected = filter_rows_device(list(frame.values()), terms, logical, per_column, stream=stream, ctx=ctx)
+    mean, _ = embedding_mean_device(emb, selected.idx, stream=stream, ctx=ctx)
+    return nearest_neighbors_device(frame, emb, mean, page_size, page_num, name, stream=stream, ctx=ctx, embedding_name=embedding_name)
