@@ -584,6 +584,73 @@ int oxh_take_columns_host(oxh_ctx* ctx, uint32_t nsrc, const uint32_t* kinds, co
                           const uint32_t* plan, const uint64_t* value_capacity, void* const* out_values, void* const* out_offsets,
                           uint8_t* const* out_validity, uint64_t* value_bytes, uint32_t* written);
 
+/* ---------------------------------------------------------------- concat: row ranges of frames, one after the other
+ * The first and the last steps of `oxen df`'s chain (core/df/tabular.rs:443-589 `transform_lazy` /
+ * `transform_slice_lazy`): `--vstack` is polars' vertical concat of frames (:449-463), `--slice`, `--head`,
+ * `--tail` (:571-636) and the page of every data-frame view (opts/df_opts.rs:62-72 `SliceRange::for_page`) are
+ * one row range of one frame. Both are the same operation on Arrow columns: write the rows
+ * [first, first + count) of one or more source frames, one after the other, as fresh buffers that start at
+ * bit / offset 0. A contiguous range needs no gather by row index: this call copies.
+ *
+ * Sources: nparts parts of ncols columns each; kinds[c] (OXH_COL_*) is shared by all parts. Column c of part p
+ * is entry p * ncols + c of values, offsets and validity, described as oxh_row_hashes_* takes a column, with
+ * its bit offsets at bit_offsets[2 * (p * ncols + c)] (OXH_COL_BOOL values) and [.. + 1] (validity).
+ * part_rows[p] is the height of part p; first[p] / count[p] are the rows taken from it; count NULL = whole
+ * parts (first is then not read). Parts may alias each other: the same frame taken twice is legal. A NULL
+ * validity = all rows valid. kinds, bit_offsets, part_rows, first, count, value_capacity, value_bytes, written
+ * and the six pointer arrays are HOST arrays in both forms; what the pointers point to is on the device in
+ * _device and on the host in _host.
+ *
+ * Output: ncols columns of N = sum(count) rows in the take's layout (Arrow buffers that start at bit / offset
+ * 0): out_validity[c] is ceil(N / 8) bytes, always written, pad bits 0, a part without validity contributing
+ * ones. Fixed-width values: N * width bytes. Booleans: ceil(N / 8) bytes, pad bits 0. Byte columns: N + 1
+ * offsets of the column's own width from 0 in out_offsets[c]; the bytes [offsets[first], offsets[first + count])
+ * of each part follow one another in out_values[c] with no gap, and the output offsets are the source offsets
+ * rebased. Values are copied AS THEY ARE, under null cells too: a null cell keeps whatever value or span its
+ * source had, as Arrow's own concat does; only validity and pad bits are normalised. This differs from
+ * oxh_take_columns_*, which zeroes and empties null cells; sources in the take's canonical form (null cells 0
+ * and empty) give canonical output, and every output of this library is canonical. A BYTES32 output of more
+ * than 2^31 - 1 bytes is OXH_ERR_INVALID (pass the column as BYTES64); nothing is written.
+ *
+ * Capacity (the take's contract unchanged): value_capacity[c] = the room of out_values[c] of a byte column.
+ * value_bytes[c] = what column c's values need, filled on every successful call. The outputs are written ONLY
+ * when every byte column fits, then *written = 1; otherwise *written = 0, no output array is touched and the
+ * call is still OXH_OK: call again with value_bytes. out_values, out_offsets and out_validity all NULL
+ * (value_capacity is then not read) is the sizes-only call. The device form finds the byte totals from one
+ * small read-back of offsets[first] and offsets[first + count] per part and byte column, and writes the
+ * bit-packed outputs (validity, boolean values) a 64-row word at a time: they must be 8-byte aligned.
+ *
+ * Both forms block until complete and keep nothing; their tables live in the context's scratch, so a second
+ * call allocates nothing in the device form. The host form reads the sizes from its own offsets, copies to
+ * the device only the taken ranges (as oxh_row_hashes_host copies only what the rows name), runs the device
+ * path into a second block and copies the outputs back.
+ * OXH_ERR_INVALID, before OXH_ERR_NODEVICE (there is no CPU path), in this order: a NULL kinds, values,
+ * offsets, validity, bit_offsets or part_rows, or a NULL first with a count; nparts == 0 or ncols == 0; nparts
+ * above OXH_CONCAT_MAX_PARTS; an unknown kind; first[p] + count[p] > part_rows[p]; a part_rows[p] or N above
+ * 2^32 - 2; NULL value_bytes or written; a byte column with rows taken and no offsets; a column of another
+ * kind with rows taken and no values; some but not all of the three output arrays NULL, outputs without
+ * value_capacity, a NULL or (device form) misaligned output of a column that needs it; in the host form,
+ * offsets that are negative or decrease inside a taken range, bytes without values; then a NULL ctx. N == 0 is
+ * OXH_OK: sizes 0, and out_offsets[c] of a byte column gets its single 0 when outputs are given.
+ * In the device form a byte column whose taken range holds bytes but that has no values is OXH_ERR_INVALID
+ * after the read-back, nothing written. A negative or decreasing pair of offsets inside a taken range is
+ * treated as in the other device forms -- nothing outside [offsets[first], offsets[first + count]) is read, and
+ * nothing at all of a part whose span is itself negative or decreasing (its cells all have length 0); inside
+ * a good span the offset AFTER a bad pair is written as the rebased offset before it, so that cell has length
+ * 0, and every rebased offset is clamped into the part's span -- the call finishes, fills value_bytes and
+ * written, and returns OXH_ERR_INVALID. A failed allocation is OXH_ERR_NOMEM with the outputs untouched. */
+#define OXH_CONCAT_MAX_PARTS 65536
+int oxh_concat_columns_device(oxh_ctx* ctx, uint32_t nparts, uint32_t ncols, const uint32_t* kinds, const void* const* d_values,
+                              const void* const* d_offsets, const uint8_t* const* d_validity, const uint64_t* bit_offsets,
+                              const uint64_t* part_rows, const uint64_t* first, const uint64_t* count, const uint64_t* value_capacity,
+                              void* const* d_out_values, void* const* d_out_offsets, uint8_t* const* d_out_validity,
+                              uint64_t* value_bytes, uint32_t* written, void* stream);
+int oxh_concat_columns_host(oxh_ctx* ctx, uint32_t nparts, uint32_t ncols, const uint32_t* kinds, const void* const* values,
+                            const void* const* offsets, const uint8_t* const* validity, const uint64_t* bit_offsets,
+                            const uint64_t* part_rows, const uint64_t* first, const uint64_t* count, const uint64_t* value_capacity,
+                            void* const* out_values, void* const* out_offsets, uint8_t* const* out_validity, uint64_t* value_bytes,
+                            uint32_t* written);
+
 /* ---------------------------------------------------------------- stable multi-column row sort
  * join_diff.rs:107 sorts the joined frame with `sort_df_on_keys` (:146-163) before it selects the output
  * columns, and `oxen df --sort` (core/df/tabular.rs:520-522) sorts a frame on one column. Here the sort is a

@@ -41,7 +41,9 @@ _FROM_TABULAR = ("KeyedDiff", "STATUS_NAMES", "keyed_diff_digests", "keyed_diff_
                  "filter_rows_device", "filter_df", "Embedding", "EmbeddingStats", "Similarity", "embedding", "embedding_from_arrow",
                  "embedding_to_arrow", "embedding_mean", "embedding_mean_device", "cosine_similarity", "cosine_similarity_device",
                  "embedding_take", "embedding_take_device", "page_rows", "nearest_neighbors", "nearest_neighbors_device",
-                 "sort_by_similarity", "sort_by_similarity_device")
+                 "sort_by_similarity", "sort_by_similarity_device", "concat", "concat_device", "slice_range", "parse_slice",
+                 "slice_rows", "slice_rows_device", "head", "head_device", "tail", "tail_device", "page", "page_device", "vstack",
+                 "vstack_device")
 
 
 def __getattr__(name):

@@ -46,6 +46,7 @@ OXH_DIFF_REMOVED = 2
 OXH_DIFF_MODIFIED = 3
 OXH_TAKE_NULL = 0xFFFFFFFF        # an absent index (the value of OXH_KEYED_DIFF_NONE)
 OXH_TAKE_NO_COLUMN = 0xFFFFFFFF   # no fallback source column
+OXH_CONCAT_MAX_PARTS = 65536      # the most parts of one oxh_concat_columns_* call
 OXH_SORT_SIGNED = 0     # two's complement of the column's width
 OXH_SORT_UNSIGNED = 1   # plain unsigned of the column's width
 OXH_SORT_FLOAT = 2      # numeric; -0.0 == +0.0; every NaN equal and above +inf (widths 4 and 8)
@@ -160,6 +161,12 @@ SIGNATURES = {
                                      ctypes.POINTER(_vp), _u64p, _u64p, _u64, _vp, _vp, _u32, ctypes.POINTER(_u32), _u64p,
                                      ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u64p,
                                      ctypes.POINTER(_u32)]),
+    "oxh_concat_columns_device": (_int, [_vp, _u32, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                         ctypes.POINTER(_vp), _u64p, _u64p, _u64p, _u64p, _u64p, ctypes.POINTER(_vp),
+                                         ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u64p, ctypes.POINTER(_u32), _vp]),
+    "oxh_concat_columns_host": (_int, [_vp, _u32, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                       ctypes.POINTER(_vp), _u64p, _u64p, _u64p, _u64p, _u64p, ctypes.POINTER(_vp),
+                                       ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u64p, ctypes.POINTER(_u32)]),
     "oxh_sort_rows_device": (_int, [_vp, _u64, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                                     ctypes.POINTER(_vp), _u64p, ctypes.POINTER(_u32), _vp, _u64p, _vp]),
     "oxh_sort_rows_host": (_int, [_vp, _u64, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_vp), ctypes.POINTER(_vp),

@@ -17,12 +17,12 @@ LIB = os.path.join(HERE, "liboxen_hash.so")
 SOURCES = [os.path.join(CSRC, f) for f in (
     "xxh3_kernels.hip", "capi_dispatch.hip", "capi_context.hip", "staging.hip", "large_items.hip", "xxh3_stream.hip",
     "engine.hip", "modified.hip", "publish.hip", "fastcdc.hip", "fastcdc_scan.hip", "fastcdc_walk.hip", "dedup_index.hip",
-    "row_hash.hip", "keyed_diff.hip", "take_columns.hip", "sort_rows.hip", "group_rows.hip", "filter_rows.hip",
+    "row_hash.hip", "keyed_diff.hip", "take_columns.hip", "concat_columns.hip", "sort_rows.hip", "group_rows.hip", "filter_rows.hip",
     "embedding.hip", "reader_pool.cpp", "comm.cpp", "fastcdc_host.cpp")]
 DEPS = SOURCES + [os.path.join(CSRC, h) for h in ("capi_internal.hpp", "xxh3_device.hpp", "fastcdc_gear.h", "fastcdc_plan.hpp",
                                                  "fastcdc_device.hpp", "pool.hpp", "scratch.hpp", "reader_pool.hpp",
                                                  "env.hpp", "keyed_diff_host.hpp", "columns.hpp",
-                                                 "take_columns_host.hpp", "sort_rows_host.hpp", "sort_keys.hpp",
+                                                 "take_columns_host.hpp", "concat_columns_host.hpp", "sort_rows_host.hpp", "sort_keys.hpp",
                                                  "group_rows_host.hpp", "filter_rows_host.hpp", "filter_terms.hpp",
                                                  "embedding_host.hpp")] + [os.path.join(ROOT, "include", "oxen_hash.h")]
 HELPER_SRC = os.path.join(CSRC, "hash_helper.cpp")
@@ -63,6 +63,8 @@ KEYED_TEST_SRC = os.path.join(ROOT, "tests", "native", "keyed_diff_host_test.cpp
 KEYED_TEST = os.path.join(ROOT, "tests", "native", "keyed_diff_host_test")  # tests only: the keyed diff's host pieces
 TAKE_TEST_SRC = os.path.join(ROOT, "tests", "native", "take_columns_host_test.cpp")
 TAKE_TEST = os.path.join(ROOT, "tests", "native", "take_columns_host_test")  # tests only: the take's host pieces
+CONCAT_TEST_SRC = os.path.join(ROOT, "tests", "native", "concat_columns_host_test.cpp")
+CONCAT_TEST = os.path.join(ROOT, "tests", "native", "concat_columns_host_test")  # tests only: the concat's host pieces
 SORT_TEST_SRC = os.path.join(ROOT, "tests", "native", "sort_rows_host_test.cpp")
 SORT_TEST = os.path.join(ROOT, "tests", "native", "sort_rows_host_test")  # tests only: the row sort's host pieces and key words
 GROUP_TEST_SRC = os.path.join(ROOT, "tests", "native", "group_rows_host_test.cpp")
@@ -88,7 +90,7 @@ def build_host(force: bool = False, verbose: bool = False) -> str:
     (tests/native/test_hasher.cpp, commit_tree_cli.cpp), which link against liboxen_hash.so; and the
     stand-alone CPU tests of the FastCDC planner (tests/native/cdc_plan_test.cpp), of the keyed diff's
     host pieces (tests/native/keyed_diff_host_test.cpp), of the take's (tests/native/take_columns_host_test.cpp), of
-    the row sort's host pieces and key words (tests/native/sort_rows_host_test.cpp), of the grouping's host pieces
+    the concat's (tests/native/concat_columns_host_test.cpp), of the row sort's host pieces and key words (tests/native/sort_rows_host_test.cpp), of the grouping's host pieces
     (tests/native/group_rows_host_test.cpp), of the filter's terms and host pieces
     (tests/native/filter_rows_host_test.cpp) and of the embedding query's host pieces and order key
     (tests/native/embedding_host_test.cpp)."""
@@ -117,6 +119,8 @@ def build_host(force: bool = False, verbose: bool = False) -> str:
          ["g++", "-std=c++17", "-O2", "-Wall", "-o", KEYED_TEST + ".tmp", KEYED_TEST_SRC]),
         (TAKE_TEST, [TAKE_TEST_SRC, os.path.join(CSRC, "take_columns_host.hpp"), os.path.join(CSRC, "columns.hpp"), hdr],
          ["g++", "-std=c++17", "-O2", "-Wall", "-o", TAKE_TEST + ".tmp", TAKE_TEST_SRC]),
+        (CONCAT_TEST, [CONCAT_TEST_SRC, os.path.join(CSRC, "concat_columns_host.hpp"), os.path.join(CSRC, "columns.hpp"), hdr],
+         ["g++", "-std=c++17", "-O2", "-Wall", "-o", CONCAT_TEST + ".tmp", CONCAT_TEST_SRC]),
         (SORT_TEST, [SORT_TEST_SRC, os.path.join(CSRC, "sort_rows_host.hpp"), os.path.join(CSRC, "sort_keys.hpp"),
                      os.path.join(CSRC, "columns.hpp"), hdr],
          ["g++", "-std=c++17", "-O2", "-Wall", "-o", SORT_TEST + ".tmp", SORT_TEST_SRC]),

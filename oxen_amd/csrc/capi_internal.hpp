@@ -21,6 +21,9 @@
 //   take_columns.hip   the columns of the joined rows (oxh_take_columns_*): a take of Arrow columns by the keyed
 //                      diff's row indices, with a fallback source (coalesce); columns.hpp holds what it shares
 //                      with row_hash.hip (the column descriptor, the cell of a row, the host forms' staging)
+//   concat_columns.hip row ranges of one or more frames written one after the other (oxh_concat_columns_*): vstack,
+//                      slice, head, tail and the page slice as copies -- a word-per-lane funnel over the bit-packed
+//                      buffers, 16-byte destination-aligned copies and an offsets rebase over host-built item lists
 //   sort_rows.hip      the stable multi-column row sort (oxh_sort_rows_*): MSD refinement rounds over the key
 //                      columns' order-preserving key words (sort_keys.hpp), each round a few passes of the
 //                      device-wide stable radix pass it defines (stable_radix_pass)

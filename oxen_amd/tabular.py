@@ -33,6 +33,11 @@ every row with it, the rows ranked from the most similar on and one page of them
 `Embedding`, `embedding`, `embedding_from_arrow`, `embedding_mean`, `cosine_similarity`, `embedding_take`,
 `nearest_neighbors`, `sort_by_similarity`, each with a `_device` twin.
 
+`oxh_concat_columns_*` is the first and the last step of `oxen df`'s chain (core/df/tabular.rs:443-589): `--vstack`
+(polars' vertical concat) and `--slice` / `--head` / `--tail` / the page of a data-frame view are row ranges of one
+or more frames written one after the other, as copies -- `concat`, `concat_device`, `slice_range`, `parse_slice`,
+`slice_rows`, `head`, `tail`, `page`, `vstack`, each frame function with a `_device` twin.
+
 A frame is an ordered mapping from column name to `Column`. A row's bytes are, over the columns in the
 frame's order: nothing for a null, the raw little-endian bytes of Int8 / Int32 / Float32 / Int64 /
 Float64 / Datetime(ms), one byte 0 or 1 for a boolean, the UTF-8 bytes of a string. Every other dtype
@@ -1654,3 +1659,240 @@ def sort_by_similarity_device(frame: Mapping, emb: Embedding, where, page_size: 
     selected = filter_rows_device(list(frame.values()), terms, logical, per_column, stream=stream, ctx=ctx)
     mean, _ = embedding_mean_device(emb, selected.idx, stream=stream, ctx=ctx)
     return nearest_neighbors_device(frame, emb, mean, page_size, page_num, name, stream=stream, ctx=ctx, embedding_name=embedding_name)
+
+
+# ---------------------------------------------------------------- concat: vstack, slice, head, tail, page
+_SLICE_NUMBER = re.compile(r"[+-]?[0-9]+\Z")   # what Rust's i64::from_str takes
+
+
+def _concat_parts(parts, ranges):
+    """(parts as lists of Column, kinds, part_rows, first, count) of a concat; the Python argument checks."""
+    parts = [list(p) for p in parts]
+    if not parts or not parts[0]:
+        raise _capi.OxenError("concat needs at least one part of at least one column", _capi.OXH_ERR_INVALID)
+    if len(parts) > _capi.OXH_CONCAT_MAX_PARTS:
+        raise _capi.OxenError(f"concat takes at most OXH_CONCAT_MAX_PARTS = {_capi.OXH_CONCAT_MAX_PARTS} parts", _capi.OXH_ERR_INVALID)
+    kinds = [int(c.kind) for c in parts[0]]
+    for p, cols in enumerate(parts):
+        if [int(c.kind) for c in cols] != kinds:
+            raise _capi.OxenError(f"part {p} has other column kinds than part 0", _capi.OXH_ERR_INVALID)
+        if any(c.nrows != cols[0].nrows for c in cols):
+            raise _capi.OxenError(f"the columns of part {p} have one row count", _capi.OXH_ERR_INVALID)
+    rows = [int(cols[0].nrows) for cols in parts]
+    if ranges is None:
+        return parts, kinds, rows, None, None
+    ranges = [(int(f), int(n)) for f, n in ranges]
+    if len(ranges) != len(parts):
+        raise _capi.OxenError("one (first, count) per part", _capi.OXH_ERR_INVALID)
+    for p, ((f, n), have) in enumerate(zip(ranges, rows)):
+        if f < 0 or n < 0 or f + n > have:
+            raise _capi.OxenError(f"part {p}: rows [{f}, {f + n}) of {have}", _capi.OXH_ERR_INVALID)
+    return parts, kinds, rows, [f for f, _ in ranges], [n for _, n in ranges]
+
+
+def _concat_head(parts, kinds, rows, first, count, ptr):
+    """The ABI's arguments from nparts on to count."""
+    flat = [c for cols in parts for c in cols]
+    u64s = lambda v: None if v is None else (ctypes.c_uint64 * max(len(v), 1))(*v)   # noqa: E731
+    return (len(parts), len(kinds), *_tables(flat, ptr), u64s(rows), u64s(first), u64s(count))
+
+
+def _concat_result(parts, kinds, n, outs, view, i32, i64):
+    result = []
+    for c, (kind, (values, offsets, validity)) in enumerate(zip(kinds, outs)):
+        src = parts[0][c].values
+        if kind in _WIDTH and getattr(src, "dtype", None) is not None and view(src) == _WIDTH[kind]:
+            values = values.view(src.dtype)
+        offs = offsets.view(i32 if kind == OXH_COL_BYTES32 else i64) if kind in _BYTES else None
+        result.append(Column(kind, n, values, offs, validity, 0, 0))
+    return result
+
+
+def concat(parts: Sequence, ranges=None, ctx: Optional[_capi.Context] = None) -> list:
+    """oxh_concat_columns_host: rows [first, first + count) of each part, one part after the other. parts: a
+    sequence of column sequences (`Column`s in host memory, the same kinds in the same order in every part; a
+    part may be given twice); ranges: one (first, count) per part, None = whole parts. Returns the output
+    `Column`s over fresh numpy buffers that start at bit / offset 0, validity always present, pad bits 0. Values
+    are copied as they are, under null cells too (Arrow's own concat; the take zeroes them): sources in the
+    take's canonical form give canonical output. The sizes-only call, the allocation, then the call that writes."""
+    parts = [[c if isinstance(c, Column) else column(c) for c in p] for p in parts]
+    parts, kinds, rows, first, count = _concat_parts(parts, ranges)
+    n = sum(rows if count is None else count)
+    keep = []
+
+    def ptr(a):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a)
+        keep.append(a)
+        return a.ctypes.data if a.size else None
+
+    ncols = len(kinds)
+    value_bytes = (ctypes.c_uint64 * ncols)()
+    written = ctypes.c_uint32(0)
+    head = (_handle(ctx), *_concat_head(parts, kinds, rows, first, count, ptr))
+    L = _capi.lib()
+    _capi.check(L.oxh_concat_columns_host(*head, None, None, None, None, value_bytes, ctypes.byref(written)), "oxh_concat_columns_host")
+    outs = [[np.zeros(size, dtype=np.uint8) for size in sizes] for sizes in _take_sizes(kinds, n, value_bytes)]
+    capacity = (ctypes.c_uint64 * ncols)(*[o[0].size for o in outs])
+    arrays = [_pointers([o[k].ctypes.data if o[k].size else None for o in outs]) for k in range(3)]
+    _capi.check(L.oxh_concat_columns_host(*head, capacity, *arrays, value_bytes, ctypes.byref(written)), "oxh_concat_columns_host")
+    if not written.value:
+        raise _capi.OxenError("oxh_concat_columns_host: the columns changed between the two calls", _capi.OXH_ERR_INVALID)
+    return _concat_result(parts, kinds, n, outs, lambda a: a.dtype.itemsize, np.int32, np.int64)
+
+
+def concat_device(parts: Sequence, ranges=None, stream=None, ctx: Optional[_capi.Context] = None) -> list:
+    """oxh_concat_columns_device: `concat` over `Column`s whose values / offsets / validity are torch tensors on
+    the device. Nothing row-shaped crosses the link: the tables of pointers go up, two offsets per part and byte
+    column come back. Returns `Column`s over fresh device tensors. Blocks."""
+    import torch
+
+    from .device import _require_cuda, _stream
+
+    parts, kinds, rows, first, count = _concat_parts(parts, ranges)
+    tensors = [t for cols in parts for c in cols for t in (c.values, c.offsets, c.validity) if t is not None]
+    _require_cuda(*tensors)
+    if any(not t.is_contiguous() for t in tensors):
+        raise _capi.OxenError("column tensors must be contiguous", _capi.OXH_ERR_INVALID)
+    device = tensors[0].device if tensors else "cuda"
+    n = sum(rows if count is None else count)
+    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()  # noqa: E731
+    ncols = len(kinds)
+    value_bytes = (ctypes.c_uint64 * ncols)()
+    written = ctypes.c_uint32(0)
+    head = (_handle(ctx), *_concat_head(parts, kinds, rows, first, count, ptr))
+    L, st = _capi.lib(), _stream(stream)
+    _capi.check(L.oxh_concat_columns_device(*head, None, None, None, None, value_bytes, ctypes.byref(written), st),
+                "oxh_concat_columns_device")
+    # not zero-filled: the call writes every byte (take_device says why)
+    outs = [[torch.empty(size, dtype=torch.uint8, device=device) for size in sizes] for sizes in _take_sizes(kinds, n, value_bytes)]
+    capacity = (ctypes.c_uint64 * ncols)(*[o[0].numel() for o in outs])
+    arrays = [_pointers([ptr(o[k]) for o in outs]) for k in range(3)]
+    _capi.check(L.oxh_concat_columns_device(*head, capacity, *arrays, value_bytes, ctypes.byref(written), st),
+                "oxh_concat_columns_device")
+    if not written.value:
+        raise _capi.OxenError("oxh_concat_columns_device: the columns changed between the two calls", _capi.OXH_ERR_INVALID)
+    return _concat_result(parts, kinds, n, outs, lambda t: t.element_size(), torch.int32, torch.int64)
+
+
+def slice_range(nrows: int, offset: int, length: int) -> tuple:
+    """(first, count) of polars' `slice(offset, length)` over nrows rows: a negative offset counts from the end;
+    start = offset + nrows if offset < 0 else offset, stop = start + length, both clamped to [0, nrows]. Restated
+    from polars' documented behaviour (the examples of `DataFrame.slice`); NOT pinned by a run of polars."""
+    nrows, offset, length = int(nrows), int(offset), int(length)
+    if nrows < 0 or length < 0:
+        raise _capi.OxenError("nrows and length are not negative", _capi.OXH_ERR_INVALID)
+    start = offset + nrows if offset < 0 else offset
+    stop = start + length
+    start, stop = min(max(start, 0), nrows), min(max(stop, 0), nrows)
+    return start, stop - start
+
+
+def parse_slice(text: str) -> tuple:
+    """`--slice 0..10` as (start, end), with SliceRange's three refusals (opts/df_opts.rs:43-58, 93-108): not two
+    whole numbers (i64) separated by the first '..'; a negative start; start >= end."""
+    def invalid(reason):
+        return _capi.OxenError(f"invalid data frame parameter slice = {text!r}: {reason}", _capi.OXH_ERR_INVALID)
+
+    start, sep, end = str(text).partition("..")
+    if not sep or not _SLICE_NUMBER.match(start) or not _SLICE_NUMBER.match(end):
+        raise invalid("expected two whole numbers separated by '..', as '0..10'")
+    start, end = int(start), int(end)
+    if not -2 ** 63 <= start < 2 ** 63 or not -2 ** 63 <= end < 2 ** 63:
+        raise invalid("expected two whole numbers separated by '..', as '0..10'")
+    if start < 0:
+        raise invalid("start must not be negative")
+    if start >= end:
+        raise invalid("start must be less than end")
+    return start, end
+
+
+def _frame_rows(frame: dict) -> int:
+    cols = list(frame.values())
+    if not cols:
+        raise _capi.OxenError("a frame has at least one column", _capi.OXH_ERR_INVALID)
+    if any(c.nrows != cols[0].nrows for c in cols):
+        raise _capi.OxenError("the columns of a frame have one row count", _capi.OXH_ERR_INVALID)
+    return int(cols[0].nrows)
+
+
+def _slice_frame(frame, first_count, call, **kw) -> dict:
+    return dict(zip(frame, call([list(frame.values())], [first_count], **kw)))
+
+
+def slice_rows(frame: Mapping, offset: int, length: int, ctx: Optional[_capi.Context] = None) -> dict:
+    """`oxen df --slice start..end` is slice_rows(frame, start, end - start) (core/df/tabular.rs:571-589): the
+    rows `slice_range` names, through `concat`, as an ordered dict."""
+    frame = _as_frame(frame)
+    return _slice_frame(frame, slice_range(_frame_rows(frame), offset, length), concat, ctx=ctx)
+
+
+def slice_rows_device(frame: Mapping, offset: int, length: int, stream=None, ctx: Optional[_capi.Context] = None) -> dict:
+    """`slice_rows` over a frame of device `Column`s, through `concat_device`."""
+    frame = dict(frame)
+    return _slice_frame(frame, slice_range(_frame_rows(frame), offset, length), concat_device, stream=stream, ctx=ctx)
+
+
+def head(frame: Mapping, n: int, ctx: Optional[_capi.Context] = None) -> dict:
+    """`oxen df --head n`: slice(0, n)."""
+    return slice_rows(frame, 0, n, ctx=ctx)
+
+
+def head_device(frame: Mapping, n: int, stream=None, ctx: Optional[_capi.Context] = None) -> dict:
+    return slice_rows_device(frame, 0, n, stream=stream, ctx=ctx)
+
+
+def tail(frame: Mapping, n: int, ctx: Optional[_capi.Context] = None) -> dict:
+    """`oxen df --tail n`: slice(-n, n)."""
+    return slice_rows(frame, -int(n), n, ctx=ctx)
+
+
+def tail_device(frame: Mapping, n: int, stream=None, ctx: Optional[_capi.Context] = None) -> dict:
+    return slice_rows_device(frame, -int(n), n, stream=stream, ctx=ctx)
+
+
+def page(frame: Mapping, page_size: int, page_num: int = 1, ctx: Optional[_capi.Context] = None) -> dict:
+    """Page `page_num` of `page_size` rows of a data-frame view, the rows `page_rows` names (page_num 0 means 1,
+    clipped to the frame)."""
+    frame = _as_frame(frame)
+    return _slice_frame(frame, page_rows(_frame_rows(frame), page_size, page_num), concat, ctx=ctx)
+
+
+def page_device(frame: Mapping, page_size: int, page_num: int = 1, stream=None, ctx: Optional[_capi.Context] = None) -> dict:
+    frame = dict(frame)
+    return _slice_frame(frame, page_rows(_frame_rows(frame), page_size, page_num), concat_device, stream=stream, ctx=ctx)
+
+
+def _vstack_frames(frames) -> list:
+    frames = [dict(f) for f in frames]
+    if not frames:
+        raise _capi.OxenError("vstack needs at least one frame", _capi.OXH_ERR_INVALID)
+    names = list(frames[0])
+    for k, f in enumerate(frames[1:], 1):
+        if list(f) != names:
+            where = next((i for i, (a, b) in enumerate(zip(names, f)) if a != b), min(len(names), len(f)))
+            have = list(f)[where] if where < len(f) else None
+            want = names[where] if where < len(names) else None
+            raise _capi.OxenError(f"vstack: frame {k} has column {have!r} where frame 0 has {want!r} (column {where}): the frames "
+                                  "must have the same columns in the same order", _capi.OXH_ERR_INVALID)
+        for name in names:
+            if int(f[name].kind) != int(frames[0][name].kind):
+                raise _capi.OxenError(f"vstack: column {name!r} of frame {k} has kind {int(f[name].kind)}, of frame 0 "
+                                      f"{int(frames[0][name].kind)}", _capi.OXH_ERR_INVALID)
+    return frames
+
+
+def vstack(frames: Sequence[Mapping], ctx: Optional[_capi.Context] = None) -> dict:
+    """`oxen df --vstack` (core/df/tabular.rs:449-463, polars' vertical concat): the frames' rows one frame after
+    the other. The frames must have the same names in the same order and equal kinds; anything else raises
+    OxenError(OXH_ERR_INVALID) naming the first mismatch. A `Column` does not tell Int32 from Float32: the dtype
+    check beyond the kind stays with the caller's Arrow schema."""
+    frames = _vstack_frames([_as_frame(f) for f in frames])
+    return dict(zip(frames[0], concat([list(f.values()) for f in frames], ctx=ctx)))
+
+
+def vstack_device(frames: Sequence[Mapping], stream=None, ctx: Optional[_capi.Context] = None) -> dict:
+    """`vstack` over frames of device `Column`s, through `concat_device`."""
+    frames = _vstack_frames(frames)
+    return dict(zip(frames[0], concat_device([list(f.values()) for f in frames], stream=stream, ctx=ctx)))
