@@ -985,6 +985,11 @@ int oxh_format_dec(uint64_t lo, uint64_t hi, char* out);
 int oxh_fill_splitmix(void* d_buf, uint64_t nbytes, uint64_t seed, void* stream);
 /* Diagnostic: select the long-path kernel variant (0 = default). Returns the previous value. */
 int oxh_set_kernel_variant(int variant);
+/* Diagnostic: byte in 0..255 = fill every working allocation of a call with it before the call uses it;
+ * -1 (default) = off. Returns the previous value. */
+int oxh_set_scratch_poison(int byte);
+/* Diagnostic: bytes filled so far under a poison (device and pinned together). */
+uint64_t oxh_scratch_poisoned_bytes(void);
 /* Diagnostic counters of a context, out[0..n): [0] device allocations of the large-file piece buffers
  * (files above a staging slot; each one synchronises the device), [1] their current bytes, [2] file
  * requests served on the caller's thread (small requests on an idle context), [3] file-engine runs,

@@ -111,6 +111,8 @@ SIGNATURES = {
     "oxh_format_dec": (_int, [_u64, _u64, ctypes.c_char_p]),
     "oxh_fill_splitmix": (_int, [_vp, _u64, _u64, _vp]),
     "oxh_set_kernel_variant": (_int, [_int]),
+    "oxh_set_scratch_poison": (_int, [_int]),
+    "oxh_scratch_poisoned_bytes": (_u64, []),
     "oxh_xxh3_stream_create": (_int, [_vp, ctypes.POINTER(_vp)]),
     "oxh_xxh3_stream_update": (_int, [_vp, _vp, _u64]),
     "oxh_xxh3_stream_digest": (_int, [_vp, _u64p]),

@@ -9,6 +9,14 @@ namespace oxh::capi {
 
 thread_local std::string g_err;
 std::atomic<int> g_variant{0};
+}  // namespace oxh::capi
+
+namespace oxh {
+std::atomic<int> g_scratch_poison{-1};
+std::atomic<uint64_t> g_scratch_poisoned{0};
+}  // namespace oxh
+
+namespace oxh::capi {
 
 int fail(int code, const std::string& msg) {
     g_err = msg;
@@ -140,6 +148,10 @@ int oxh_device_count(int* count) {
 }
 
 int oxh_set_kernel_variant(int variant) { return g_variant.exchange(variant); }
+
+int oxh_set_scratch_poison(int byte) { return oxh::g_scratch_poison.exchange(byte < 0 || byte > 255 ? -1 : byte); }
+
+uint64_t oxh_scratch_poisoned_bytes(void) { return oxh::g_scratch_poisoned.load(); }
 
 int oxh_xxh3_128_batch_device(const void* d_arena, const uint64_t* d_offsets, const uint64_t* d_lens, uint64_t n,
                               uint64_t* d_out, int mode, void* stream) {

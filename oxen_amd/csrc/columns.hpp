@@ -290,11 +290,15 @@ struct CallBlock {
         if (d) (void)hipFree(d);
         if (h) (void)hipHostFree(h);
     }
-    int make(size_t bytes, const char* what) {
+    // `st`: the stream the call's work on the block is queued on. The pinned half comes back zeroed -- the callers
+    // count on that for the control words they send up -- so of a poison (scratch.hpp) only the device half's stays.
+    int make(size_t bytes, const char* what, hipStream_t st) {
         if (hipMalloc(&d, bytes) != hipSuccess || hipHostMalloc(&h, bytes, hipHostMallocDefault) != hipSuccess) {
             (void)hipGetLastError();
             return fail(OXH_ERR_NOMEM, std::string(what) + ": control block");
         }
+        oxh::poison_device(d, bytes, st);
+        oxh::poison_pinned(h, bytes);
         memset(h, 0, bytes);
         return OXH_OK;
     }

@@ -350,6 +350,7 @@ int oxh_concat_columns_host(oxh_ctx* ctx, uint32_t nparts, uint32_t ncols, const
         if (d_in) (void)hipFree(d_in);
         return fail(OXH_ERR_NOMEM, "concat: " + std::to_string(in.block.total + where.total) + " B for the columns on the device");
     }
+    oxh::poison_device(d_in, in.block.total + 16, st), oxh::poison_device(d_out, where.total + 16, st);
     rc = [&]() -> int {
         for (const oxh::cols::Piece& p : in.block.pieces)
             if (p.bytes) HIP_TRY(hipMemcpyAsync(d_in + p.at, p.src, p.bytes, hipMemcpyHostToDevice, st));

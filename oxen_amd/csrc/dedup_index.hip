@@ -328,6 +328,7 @@ int reserve(DedupIndex* ix, uint64_t n, hipStream_t st, bool& rebuilt, uint64_t*
             return fail(OXH_ERR_NOMEM, "dedup index: table of " + std::to_string(nslots) + " slots");
         }
     }
+    oxh::poison_device(nk, ncap * 16, st), oxh::poison_device(nt, nslots * 8, st);  // (a NULL one is skipped)
     if (nk) {
         if (ix->rows) HIP_TRY(hipMemcpyAsync(nk, ix->d_keys, ix->rows * 16, hipMemcpyDeviceToDevice, st));
         old_keys = ix->d_keys;
@@ -426,6 +427,7 @@ int piece_buffers(DedupIndex* ix) {
         (void)hipHostFree(h);
         return fail(OXH_ERR_NOMEM, "dedup index: device staging");
     }
+    oxh::poison_pinned(h, kPieceRows * 32), oxh::poison_device(d, kPieceRows * 32, ix->ctx->stream);
     ix->h_piece = h;
     ix->d_piece = d;
     return OXH_OK;
@@ -459,7 +461,7 @@ struct Overlap {
     unsigned long long *d_member = nullptr, *d_matrix = nullptr;  // the error word follows the matrix
     uint64_t* h_block = nullptr;  // [matrix 2*nsets^2 | error word | set_first nsets+1]
 
-    int make(oxh_ctx* ctx, const uint64_t* set_first, uint64_t nsets_, bool own_lens) {
+    int make(oxh_ctx* ctx, const uint64_t* set_first, uint64_t nsets_, bool own_lens, hipStream_t st) {
         nsets = nsets_;
         n = set_first[nsets];
         words = (nsets + 63) / 64;
@@ -477,6 +479,7 @@ struct Overlap {
             (void)hipGetLastError();
             return fail(OXH_ERR_NOMEM, "chunk overlap: pinned result");
         }
+        oxh::poison_device(d_block, (n * (1 + (own_lens ? 1 : 0) + words) + tail) * 8, st), oxh::poison_pinned(h_block, tail * 8);
         d_first = d_block;
         d_lens = own_lens ? d_first + n : nullptr;
         d_member = (unsigned long long*)(d_first + n * (own_lens ? 2 : 1));
@@ -563,6 +566,8 @@ int oxh_dedup_index_create(oxh_ctx* ctx, uint64_t capacity_rows, void** out) {
     if (hipMalloc(&ix->d_ctrl, 8 * sizeof(unsigned long long)) != hipSuccess) return cleanup(OXH_ERR_NOMEM, "dedup index: control words");
     if (hipHostMalloc(&ix->h_ctrl, 8 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess)
         return cleanup(OXH_ERR_NOMEM, "dedup index: pinned control words");
+    oxh::poison_device(ix->d_keys, ix->key_cap * 16, ctx->stream), oxh::poison_device(ix->d_table, ix->slots * 8, ctx->stream);
+    oxh::poison_device(ix->d_ctrl, 8 * sizeof(unsigned long long), ctx->stream), oxh::poison_pinned(ix->h_ctrl, 8 * sizeof(unsigned long long));
     if (hipMemsetAsync(ix->d_table, 0xFF, ix->slots * 8, ctx->stream) != hipSuccess ||
         hipStreamSynchronize(ctx->stream) != hipSuccess)
         return cleanup(OXH_ERR_HIP, "dedup index: clearing the table");
@@ -683,7 +688,7 @@ int oxh_chunk_overlap_device(oxh_ctx* ctx, const uint64_t* d_digests, const uint
     if ((rc = overlap_enter(ctx, set_first, nsets, rows_out, bytes_out, done)) || done) return rc;
     hipStream_t st = (hipStream_t)stream;
     Overlap ov;
-    rc = ov.make(ctx, set_first, nsets, false);
+    rc = ov.make(ctx, set_first, nsets, false, st);
     if (rc == OXH_OK) rc = insert_rows(ov.ix, d_digests, hipMemcpyDeviceToDevice, nullptr, ov.n, ov.n, ov.d_first, nullptr, st);
     if (rc == OXH_OK) rc = ov.run(d_lens, rows_out, bytes_out, st);
     ov.release(st, rc != OXH_OK);
@@ -699,7 +704,7 @@ int oxh_chunk_overlap_host(oxh_ctx* ctx, const uint64_t* digests, const uint64_t
     hipStream_t st = ctx->stream;
     const bool with_lens = lens && bytes_out;
     Overlap ov;
-    rc = ov.make(ctx, set_first, nsets, with_lens);
+    rc = ov.make(ctx, set_first, nsets, with_lens, st);
     if (rc == OXH_OK) rc = piece_buffers(ov.ix);
     if (rc == OXH_OK)
         rc = [&]() -> int {

@@ -549,11 +549,12 @@ struct DeviceBlock {
     ~DeviceBlock() {
         if (d) (void)hipFree(d);
     }
-    int make(uint64_t bytes, const char* what) {
+    int make(uint64_t bytes, const char* what, hipStream_t st) {
         if (hipMalloc(&d, bytes + 16) != hipSuccess) {
             (void)hipGetLastError();
             return fail(OXH_ERR_NOMEM, std::string(what) + ": " + std::to_string(bytes) + " B for the named rows on the device");
         }
+        oxh::poison_device(d, bytes + 16, st);
         return OXH_OK;
     }
 };
@@ -588,7 +589,7 @@ int oxh_embedding_mean_host(oxh_ctx* ctx, uint32_t layout, uint64_t nrows, uint3
     const int64_t p_idx = plan.add(idx, nidx * 4);
     plan.add_column(a.col, std::min(lo, hi), hi);
     DeviceBlock block;
-    if ((rc = block.make(plan.total, "embedding mean"))) return rc;
+    if ((rc = block.make(plan.total, "embedding mean", st))) return rc;
     uint64_t stats[4] = {0, 0, 0, 0};
     std::vector<float> mean(dim);
     rc = [&]() -> int {
@@ -646,7 +647,7 @@ int oxh_embedding_similarity_host(oxh_ctx* ctx, uint32_t layout, uint64_t nrows,
     const int64_t p_query = plan.add(query, (uint64_t)dim * 4);
     plan.add_column(a.col, 0, nrows);
     DeviceBlock block;
-    if ((rc = block.make(plan.total, "embedding similarity"))) return rc;
+    if ((rc = block.make(plan.total, "embedding similarity", st))) return rc;
     uint64_t stats[4] = {0, 0, 0, 0};
     std::vector<uint8_t> back(plan.pieces[p_query].at);  // the outputs stand in front of the query
     rc = [&]() -> int {
@@ -700,7 +701,7 @@ int oxh_embedding_take_host(oxh_ctx* ctx, uint32_t layout, uint64_t nrows, uint3
     const int64_t p_idx = plan.add(idx, nout * 4);
     plan.add_column(a.col, std::min(lo, hi), hi);
     DeviceBlock block;
-    if ((rc = block.make(plan.total, "embedding take"))) return rc;
+    if ((rc = block.make(plan.total, "embedding take", st))) return rc;
     uint64_t stats[4] = {0, 0, 0, 0};
     std::vector<uint8_t> back(plan.pieces[p_idx].at);  // the outputs stand in front of the indices
     rc = [&]() -> int {

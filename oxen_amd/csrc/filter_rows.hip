@@ -280,6 +280,7 @@ int oxh_filter_rows_host(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const uin
         (void)hipGetLastError();
         return fail(OXH_ERR_NOMEM, "filter rows: " + std::to_string(plan.staging.total) + " B for the named columns on the device");
     }
+    oxh::poison_device(d_block, plan.staging.total + 16, st);
     uint64_t stats[2] = {0, 0};
     std::vector<uint32_t> out_idx;
     std::vector<uint64_t> out_mask;

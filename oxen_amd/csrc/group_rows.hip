@@ -184,7 +184,7 @@ int group_rows_run(oxh_ctx* ctx, const grouprows::Args& a, const void* const* d_
     int rc = images.measure(true, n, a.nkeys, a.kinds, a.orders, d_values, d_offsets, d_validity, bits, st);
     if (rc) return rc;
     CallBlock ctrl;
-    if ((rc = ctrl.make(kGroupCtrlWords * 8, "group rows"))) return rc;
+    if ((rc = ctrl.make(kGroupCtrlWords * 8, "group rows", st))) return rc;
     unsigned long long* d_ctrl = (unsigned long long*)ctrl.d;
     const unsigned long long* h_ctrl = (const unsigned long long*)ctrl.h;
     void* index = nullptr;
@@ -281,6 +281,7 @@ int oxh_group_rows_host(oxh_ctx* ctx, uint64_t nrows, uint32_t nkeys, const uint
         (void)hipGetLastError();
         return fail(OXH_ERR_NOMEM, "group rows: " + std::to_string(plan.staging.total) + " B for the key columns on the device");
     }
+    oxh::poison_device(d_block, plan.staging.total + 16, st);
     uint64_t stats[4] = {0, 0, 0, 0};
     uint32_t* const wanted[4] = {group, count, first_idx, first_count};
     std::vector<uint32_t> out[4];

@@ -364,7 +364,7 @@ struct KeyedCall {
     uint64_t nl = 0, nr = 0, n = 0, grp_bytes = 0, bucket_bytes = 0;
     oxh::KeyedArgs a{};
 
-    int make(oxh_ctx* ctx, uint64_t nleft, uint64_t nright) {
+    int make(oxh_ctx* ctx, uint64_t nleft, uint64_t nright, hipStream_t st) {
         nl = nleft, nr = nright, n = nleft + nright;
         int rc = oxh_dedup_index_create(ctx, n, &index);
         if (rc) return rc;
@@ -378,6 +378,7 @@ struct KeyedCall {
             (void)hipGetLastError();
             return fail(OXH_ERR_NOMEM, "keyed diff: " + std::to_string(n) + " rows of ids, groups, offsets and buckets");
         }
+        oxh::poison_device(d_block, bucket_at + bucket_bytes + 16, st), oxh::poison_pinned(h_ctrl, oxh::kCtrlWords * 8);
         d_id = (uint64_t*)d_block;
         d_sums = (unsigned long long*)(d_block + sums_at);
         d_ctrl = (unsigned long long*)(d_block + ctrl_at);
@@ -483,7 +484,7 @@ int oxh_keyed_diff_device(oxh_ctx* ctx, const uint64_t* d_left_keys, uint64_t nl
     hipStream_t st = (hipStream_t)stream;
     KeyedCall call;
     uint64_t counts[8] = {};
-    rc = call.make(ctx, nleft, nright);
+    rc = call.make(ctx, nleft, nright, st);
     if (rc == OXH_OK)
         rc = call.classify(d_left_keys, d_right_keys, d_left_targets, d_right_targets, d_left_key0_valid, d_right_key0_valid,
                            bit_offsets2[0], bit_offsets2[1], flags, counts, st);
@@ -529,11 +530,12 @@ int oxh_keyed_diff_host(oxh_ctx* ctx, const uint64_t* left_keys, uint64_t nleft,
     KeyedCall call;
     uint8_t *d_in = nullptr, *d_out = nullptr;
     uint64_t counts[8] = {};
-    rc = call.make(ctx, nleft, nright);
+    rc = call.make(ctx, nleft, nright, st);
     if (rc == OXH_OK && hipMalloc(&d_in, total + 16) != hipSuccess) {
         (void)hipGetLastError();
         rc = fail(OXH_ERR_NOMEM, "keyed diff: " + std::to_string(total) + " B for the tables on the device");
     }
+    oxh::poison_device(d_in, total + 16, st);
     if (rc == OXH_OK)
         rc = [&]() -> int {
             for (int k = 0; k < npieces; ++k)
@@ -547,6 +549,7 @@ int oxh_keyed_diff_host(oxh_ctx* ctx, const uint64_t* left_keys, uint64_t nleft,
                 (void)hipGetLastError();
                 return fail(OXH_ERR_NOMEM, "keyed diff: " + std::to_string(pairs) + " pairs on the device");
             }
+            oxh::poison_device(d_out, status_at + pairs, st);
             if ((r = call.fill(pairs, (uint32_t*)d_out, (uint32_t*)(d_out + right_at), d_out + status_at, st))) return r;
             HIP_TRY(hipMemcpyAsync(left_idx, d_out, pairs * 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipMemcpyAsync(right_idx, d_out + right_at, pairs * 4, hipMemcpyDeviceToHost, st));

@@ -140,6 +140,7 @@ int oversize_item(oxh_ctx* c, const uint8_t* src, uint64_t len, uint64_t* out2, 
         (void)hipGetLastError();
         return fail(OXH_ERR_NOMEM, "oversize hipMalloc failed");
     }
+    oxh::poison_device(d, align_up(len) + 256, c->stream);
     int rc = OXH_OK;
     if (hipMemcpyAsync(d, src, len, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = fail(OXH_ERR_HIP, "oversize H2D failed");
     if (rc == OXH_OK) rc = device_item(c, d, len, out2, cnt2, utf8_1);

@@ -372,6 +372,7 @@ int row_diff_run(oxh_ctx* ctx, const uint64_t* d_base, uint64_t nbase, const uin
         (void)hipGetLastError();
         return release(fail(OXH_ERR_NOMEM, "row diff: " + std::to_string(n) + " rows of ids and last indices"));
     }
+    oxh::poison_device(d_block, (n + 4) * 8 + 2 * n * 4, st), oxh::poison_pinned(h_ctrl, 4 * 8);
     uint64_t* d_first = d_block;
     unsigned long long* d_ctrl = (unsigned long long*)(d_block + n);
     unsigned int* d_last = (unsigned int*)(d_ctrl + 4);
@@ -407,7 +408,7 @@ int RowImageCall::measure(bool keyed_image, uint64_t rows, uint32_t cols, const 
     short_max = gather_all ? 0 : oxh::kRowShortMax;
     ctrl_at = (ncols * sizeof(RowCol) + 63) & ~(size_t)63;
     const size_t bytes = ctrl_at + oxh::kCtrlWords * 8;
-    int rc = block.make(bytes, keyed ? "group rows" : "row hashes");
+    int rc = block.make(bytes, keyed ? "group rows" : "row hashes", st);
     if (rc) return rc;
     RowCol* h_cols = (RowCol*)block.h;
     for (uint32_t c = 0; c < ncols; ++c) {
@@ -535,6 +536,7 @@ int oxh_row_hashes_host(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const uint
         (void)hipGetLastError();
         return fail(OXH_ERR_NOMEM, "row hashes: " + std::to_string(total) + " B for the columns on the device");
     }
+    oxh::poison_device(d_block, total, st);
     rc = [&]() -> int {
         for (const oxh::cols::Piece& p : plan.pieces) HIP_TRY(hipMemcpyAsync(d_block + p.at, p.src, p.bytes, hipMemcpyHostToDevice, st));
         for (uint32_t c = 0; c < ncols; ++c) {
@@ -578,6 +580,7 @@ int oxh_row_diff_host(oxh_ctx* ctx, const uint64_t* base, uint64_t nbase, const 
         (void)hipGetLastError();
         return fail(OXH_ERR_NOMEM, "row diff: " + std::to_string(n) + " rows of digests on the device");
     }
+    oxh::poison_device(d_block, n * 17, st);
     std::vector<uint8_t> flags;
     uint64_t counts[2] = {0, 0};
     rc = [&]() -> int {

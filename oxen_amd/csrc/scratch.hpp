@@ -10,13 +10,37 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdint>
+#include <cstring>
 #include <map>
 #include <mutex>
 
 #include "env.hpp"
 
 namespace oxh {
+
+// oxh_set_scratch_poison (capi_dispatch.hip), a diagnostic: a byte in 0..255 that every working allocation of a
+// call is filled with before the call uses it -- a lease's device bytes and pinned words, a CallBlock
+// (columns.hpp), the blocks an entry allocates for itself -- so that a test sees a result that depends on what
+// such memory held before (tests/test_scratch_contents.py). -1, the default: off, one relaxed load per
+// allocation. The staging slots and the piece buffers of the file engine are not filled.
+extern std::atomic<int> g_scratch_poison;
+extern std::atomic<uint64_t> g_scratch_poisoned;  // oxh_scratch_poisoned_bytes(): bytes filled so far
+
+// Device memory the call has just allocated: filled on `st`, ahead of the call's work on that stream.
+inline void poison_device(void* d, uint64_t bytes, hipStream_t st) {
+    const int byte = g_scratch_poison.load(std::memory_order_relaxed);
+    if (byte < 0 || !d || !bytes) return;
+    if (hipMemsetAsync(d, byte, bytes, st) == hipSuccess) g_scratch_poisoned.fetch_add(bytes, std::memory_order_relaxed);
+}
+// Pinned memory no copy is in flight to or from.
+inline void poison_pinned(void* h, uint64_t bytes) {
+    const int byte = g_scratch_poison.load(std::memory_order_relaxed);
+    if (byte < 0 || !h || !bytes) return;
+    memset(h, byte, bytes);
+    g_scratch_poisoned.fetch_add(bytes, std::memory_order_relaxed);
+}
 
 struct ScratchCache {
     std::mutex mu;
@@ -80,6 +104,13 @@ class ScratchLease {
             const hipError_t e = hipMalloc(&cache_->base, bytes);
             if (e != hipSuccess) return e;
             cache_->size = bytes;
+            filled_ = 0;
+        }
+        // the poison (above) goes over what this lease has not handed out before: a later get() of the same
+        // lease (the concat's write after its measure) keeps what the earlier one may still hold
+        if (bytes > filled_) {
+            poison_device((uint8_t*)cache_->base + filled_, bytes - filled_, st_);
+            filled_ = bytes;
         }
         *out = cache_->base;
         return hipSuccess;
@@ -95,6 +126,11 @@ class ScratchLease {
             const hipError_t e = hipHostMalloc(&cache_->pinned, bytes, hipHostMallocDefault);
             if (e != hipSuccess) return e;
             cache_->pinned_size = bytes;
+            pinned_filled_ = 0;
+        }
+        if (bytes > pinned_filled_) {
+            poison_pinned((uint8_t*)cache_->pinned + pinned_filled_, bytes - pinned_filled_);
+            pinned_filled_ = bytes;
         }
         *out = cache_->pinned;
         return hipSuccess;
@@ -117,6 +153,7 @@ class ScratchLease {
 
    private:
     hipStream_t st_;
+    uint64_t filled_ = 0, pinned_filled_ = 0;  // what get() / pinned() have handed out (and poisoned) so far
     ScratchCache* cache_ = nullptr;
     std::unique_lock<std::mutex> lk_;
 };

@@ -396,7 +396,7 @@ int sort_rows_run(const sortrows::Args& a, const void* const* d_values, const vo
     const uint64_t n = a.nrows, ntiles = radix_tiles(n), ntable = 256 * ntiles;
     const size_t ctrl_at = (a.nkeys * sizeof(SortCol) + 63) & ~(size_t)63, ctrl_bytes = kSortCtrlWords * 8;
     CallBlock block;
-    int rc = block.make(ctrl_at + ctrl_bytes, "sort rows");
+    int rc = block.make(ctrl_at + ctrl_bytes, "sort rows", st);
     if (rc) return rc;
     SortCol* h_cols = (SortCol*)block.h;
     for (uint32_t c = 0; c < a.nkeys; ++c) {
@@ -553,6 +553,7 @@ int oxh_sort_rows_host(oxh_ctx* ctx, uint64_t nrows, uint32_t nkeys, const uint3
         (void)hipGetLastError();
         return fail(OXH_ERR_NOMEM, "sort rows: " + std::to_string(plan.staging.total) + " B for the key columns on the device");
     }
+    oxh::poison_device(d_block, plan.staging.total + 16, st);
     uint64_t stats[3] = {0, 0, 0};
     std::vector<uint32_t> out;
     rc = [&]() -> int {

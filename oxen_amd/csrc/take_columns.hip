@@ -377,7 +377,7 @@ struct TakeCall {
         ctrl_at = (out_at + a.nout * sizeof(oxh::TakeOut) + 63) & ~(size_t)63;
         totals_at = ctrl_at + oxh::kTakeCtrlWords * 8;
         bytes = totals_at + a.nout * 8;
-        int rc = block.make(bytes, "take");
+        int rc = block.make(bytes, "take", st);
         if (rc) return rc;
         oxh::TakeSrc* src = (oxh::TakeSrc*)block.h;
         for (uint32_t c = 0; c < a.nsrc; ++c) {
@@ -482,6 +482,7 @@ struct TakeCall {
                 (void)hipStreamSynchronize(st);
                 return fail(OXH_ERR_NOMEM, "take: the lists of " + std::to_string(npieces) + " pieces of long cells");
             }
+            oxh::poison_device(d_lists, npieces * 12, st);
             k.item_cp = (uint64_t*)d_lists;
             k.item_row = (uint32_t*)(d_lists + npieces * 8);
             k.nitems = npieces;
@@ -581,6 +582,7 @@ int oxh_take_columns_host(oxh_ctx* ctx, uint32_t nsrc, const uint32_t* kinds, co
         (void)hipGetLastError();
         return fail(OXH_ERR_NOMEM, "take: " + std::to_string(plan_in.total) + " B for the columns on the device");
     }
+    oxh::poison_device(d_in, plan_in.total + 16, st);
     std::vector<uint64_t> need;
     bool fits = false;
     rc = [&]() -> int {
@@ -607,6 +609,7 @@ int oxh_take_columns_host(oxh_ctx* ctx, uint32_t nsrc, const uint32_t* kinds, co
             (void)hipGetLastError();
             return fail(OXH_ERR_NOMEM, "take: " + std::to_string(where.total) + " B for the output columns on the device");
         }
+        oxh::poison_device(d_out, where.total + 16, st);
         std::vector<void*> o_values(nout), o_offsets(nout);
         std::vector<uint8_t*> o_validity(nout);
         for (uint32_t o = 0; o < nout; ++o) {

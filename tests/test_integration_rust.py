@@ -104,7 +104,7 @@ def test_rust_block_matches_the_header():
     block = rust_block()
     rs = rust_functions(block)
     test_only = set(re.search(r"//\s*test-only, not bound:\s*([\w, ]+)", block).group(1).replace(" ", "").split(","))
-    assert test_only == {"oxh_fill_splitmix", "oxh_set_kernel_variant"}, test_only
+    assert test_only == {"oxh_fill_splitmix", "oxh_set_kernel_variant", "oxh_set_scratch_poison", "oxh_scratch_poisoned_bytes"}, test_only
     assert not (test_only & set(rs)), test_only & set(rs)
     missing = sorted(set(hdr) - set(rs) - test_only)
     assert not missing, f"header exports not bound in INTEGRATION.md: {missing}"

@@ -213,15 +213,23 @@ def test_short_cell_lengths_at_every_destination_alignment(ctx, form, kind):
     check(ctx, form, [col], rng.permutation(len(cells)).astype(np.uint32))
 
 
+def threshold_cells(rng):
+    """Cells of T - 1, T, T + 1 bytes around the short / long threshold and P - 1, P, P + 1, 2 P + 1 around the
+    piece size, each among short cells (also the frame of tests/test_scratch_contents.py's take)."""
+    body = lambda n: bytes(rng.integers(0, 256, size=n, dtype=np.uint8))  # noqa: E731
+    cells = []
+    for n in (T - 1, T, T + 1, P - 1, P, P + 1, 2 * P + 1):
+        cells += [b"ab", body(n), b"c", b"", body(5)]
+    return cells
+
+
 @pytest.mark.parametrize("form", FORMS)
 def test_cell_lengths_around_the_threshold_and_the_piece_size(ctx, form):
     """T - 1, T, T + 1 around the short / long threshold; P - 1, P, P + 1, 2 P + 1 around the piece size, each
     among short cells, at odd destinations; taken twice, in order and out of order."""
     rng = np.random.default_rng(8)
     body = lambda n: bytes(rng.integers(0, 256, size=n, dtype=np.uint8))  # noqa: E731
-    cells = []
-    for n in (T - 1, T, T + 1, P - 1, P, P + 1, 2 * P + 1):
-        cells += [b"ab", body(n), b"c", b"", body(5)]
+    cells = threshold_cells(rng)
     col = strings(cells, lead=b"q")
     order = np.arange(len(cells), dtype=np.uint32)
     want = check(ctx, form, [col], order)
