@@ -930,6 +930,118 @@ int oxh_embedding_take_host(oxh_ctx* ctx, uint32_t layout, uint64_t nrows, uint3
                             const uint8_t* validity, uint64_t validity_bit, const uint32_t* idx, uint64_t nout, void* out_values,
                             uint8_t* out_validity, uint64_t* stats4);
 
+/* ---------------------------------------------------------------- CSV: record index and typed Arrow columns
+ * `oxen df data.csv ..` and `oxen diff a.csv b.csv` first read the file (core/df/tabular.rs:39-71 read_df_csv,
+ * base_lazy_csv_reader), and the tabular metadata reads it again for width, height and schema
+ * (repositories/metadata/tabular.rs:10-25). oxh_csv_* do that on the device: CSV bytes in HBM to a record index (a
+ * handle), then to columns in this header's own description (OXH_COL_*: values, offsets, validity) that every
+ * tabular entry above takes as they are.
+ *
+ * The rules restate polars' documented reader under the reference's settings (header row, eol_char '\n',
+ * truncate_ragged_lines, ignore_errors, a one-byte separator, an optional one-byte quote). They are NOT pinned by
+ * a run of polars.
+ *   Quotes by parity. With a quote byte configured, EVERY occurrence of it toggles "inside quotes", wherever it
+ *     stands; a doubled quote toggles twice and changes nothing. On well-formed input this is RFC 4180; on
+ *     malformed input (a stray quote in the middle of a field) it is not. With OXH_CSV_NO_QUOTE no byte is special.
+ *   Records. A record ends at '\n' outside quotes. The end of the buffer ends the last record whatever the parity
+ *     (stats8[7] says that the buffer ended inside quotes). One '\r' directly before the ending '\n' (or before the
+ *     end of the buffer) is not part of the record's last field. A record of zero bytes, or of that one '\r', is
+ *     skipped and counted.
+ *   Fields. A record splits at the separators outside quotes.
+ *   Field values. A field whose first and last bytes are both the quote (length >= 2) loses them, and every
+ *     doubled quote inside becomes one (left to right: a run of k quotes keeps k - k / 2). Any other field is its
+ *     bytes as they are.
+ *   Header. With OXH_CSV_HAS_HEADER the first kept record is the header and its field count is ncols. Without it
+ *     ncols is the first kept record's field count and that record is data.
+ *   Ragged records. A short data record has nulls for its missing fields, a long one loses its extra fields (and
+ *     the '\r' rule applies to the record's own last field only). Both are counted.
+ *   Nulls. An empty unquoted field is null in every type. "" (quoted, empty) is an empty string in a string column
+ *     and null in the others (counted with the empty fields).
+ *   Types (grammars over the whole field value; no whitespace trimming):
+ *     OXH_CSV_INT64    [+-]?[0-9]+ , exact; out of range is null, never wrapped;
+ *     OXH_CSV_FLOAT64  [+-]?([0-9]+(\.[0-9]*)?|\.[0-9]+)([eE][+-]?[0-9]+)?  or  [+-]?(inf|infinity|nan), ASCII
+ *                      case-insensitive: the CORRECTLY ROUNDED double, bit for bit what C's strtod gives; NaN is
+ *                      the quiet NaN 0x7FF8000000000000 with the sign as written;
+ *     OXH_CSV_BOOL     true / false, ASCII case-insensitive;
+ *     OXH_CSV_STRING / OXH_CSV_STRING64   the field value, with int32 / int64 offsets (OXH_COL_BYTES32 / 64).
+ *     Text that does not match its grammar is null (ignore_errors), counted apart from the empty-field nulls. A
+ *     null cell's value is 0 / false / no bytes.
+ *   Floats. The device converts a cell itself where one IEEE operation is exact: at most 19 significant digits, a
+ *     mantissa <= 2^53 and a decimal exponent within +-22 (double(m) * 10^e or double(m) / 10^-e, plain * and /),
+ *     and the zeros, infinities and NaNs. Every other matching cell is DEFERRED: compacted on the device, its text
+ *     brought down, converted on the host (std::from_chars; strtod in the "C" locale outside the doubles' range)
+ *     and scattered back inside the same blocking call. stats4[2] counts them.
+ *   Inference. Over the first max_rows data rows, per column the AND of each cell's class bits -- the value is an
+ *     in-range INT64 / matches the FLOAT64 grammar / is a BOOL; an empty value (quoted or not) and a missing field
+ *     have all three. Int64 if every cell is an integer, else Float64, else Boolean, else String; a column with
+ *     every bit after no rows or only empty cells is String (OXH_CSV_STRING; the caller picks STRING64).
+ *   Out of scope: dialect sniffing (qsv_sniffer: the caller passes separator and quote); the LossyUtf8
+ *     replacement of invalid sequences (bytes are copied as they are); comment lines, skip_rows, multi-byte
+ *     separators, dates; buffers of 2^32 bytes and more (OXH_ERR_INVALID: positions are u32); files larger than one
+ *     device buffer (no piece pipeline).
+ *
+ * The handle (a void*, as the dedup index's) holds the index: `ends`, the u32 position of every separator and
+ * record end outside quotes in ascending order (4 B per delimiter); `rec_end`, for every record the place of its
+ * end in `ends` (4 B per record); `row_rec`, the kept records (4 B per record); and the header's names. Field f of
+ * record r is the bytes between ends[first(r) + f - 1] + 1 and ends[first(r) + f], present iff first(r) + f <=
+ * rec_end[r]: a CSR form, not an nrows x ncols table. oxh_csv_open_device reads the caller's d_bytes (any
+ * alignment), which must stay alive and unchanged until oxh_csv_close; oxh_csv_open_host owns a device copy. All
+ * entries block until complete. A handle is used by one thread at a time, on the device of its ctx; the ctx must
+ * outlive it. stream (hipStream_t, NULL = the null stream) orders the device forms' work; the host forms,
+ * oxh_csv_infer and oxh_csv_header use the ctx's stream.
+ *   stats8 = {records, data rows, ncols, delimiters (the entries of `ends`), skipped empty records, short records,
+ *   long records, 1 if the buffer ended inside quotes}.
+ * oxh_csv_open_*: OXH_ERR_INVALID, before OXH_ERR_NODEVICE (there is no CPU path), in this order: a separator above
+ * 255; a quote above OXH_CSV_NO_QUOTE; a separator that is '\n' or '\r'; a quote that is '\n' or '\r'; a quote
+ * equal to the separator; unknown flags; nbytes >= 2^32; NULL bytes with nbytes > 0; NULL out; NULL stats8; then
+ * nbytes == 0 is OXH_OK with zeroed stats and a valid empty handle; then OXH_ERR_NODEVICE; then a NULL ctx. A
+ * failed allocation is OXH_ERR_NOMEM with the outputs untouched.
+ * oxh_csv_close: NULL is OXH_OK.
+ * oxh_csv_header: the header's names one after the other in names (capacity bytes) with ncols + 1 name_offsets;
+ * names_bytes always receives their size, and with names NULL or a capacity below it nothing else is written
+ * (OXH_OK: the caller sizes and calls again). Without OXH_CSV_HAS_HEADER there are no names: 0 bytes, offsets 0.
+ * OXH_ERR_INVALID: a NULL handle, name_offsets or names_bytes.
+ * oxh_csv_infer: types[c] for the ncols columns. OXH_ERR_INVALID: a NULL handle; NULL types with ncols > 0.
+ * max_rows == 0 or no rows: every column is OXH_CSV_STRING.
+ * oxh_csv_columns_*: the nsel columns col_idx[k] (any order, repeats allowed) as types[k]. Outputs, per selection:
+ * values (INT64 / FLOAT64: nrows 8-byte cells; BOOL: ceil(nrows / 8) bytes from bit 0; strings: the bytes),
+ * offsets (strings: nrows + 1 int32 / int64 from 0; else not read), validity (ceil(nrows / 8) bytes, an Arrow
+ * bitmap from bit 0, the bits past nrows zero, ALWAYS written). value_capacity[k] = the bytes values[k] holds.
+ * value_bytes[k] = the bytes of values in use; stats4 (4 per selection) = {nulls from empty or missing fields,
+ * nulls from unparsable text, deferred cells, value bytes}. With the three output tables NULL the call only
+ * measures (value_bytes, stats4), as the take and the concat do, so the caller can size string buffers. In
+ * _device the buffers the tables name are on the device, in _host on the host; the tables themselves,
+ * value_capacity, value_bytes and stats4 are host arrays in both. OXH_ERR_INVALID, in this order: a NULL handle;
+ * with selections NULL col_idx or types; a col_idx[k] >= ncols; an unknown type; NULL value_bytes or stats4; only
+ * some of the three output tables NULL; outputs without value_capacity; with rows, per selection: a NULL
+ * validity[k], a string column without offsets[k], with a capacity and no values[k] or with offsets[k] not aligned
+ * to its 4- / 8-byte entries, another column without values[k], with a capacity below its values or (INT64, FLOAT64)
+ * with values[k] not 8-byte aligned -- the alignments in both forms, as Arrow's buffers have them; then, after the
+ * strings were measured and before anything is
+ * written: an OXH_CSV_STRING column of more than 2^31 - 1 bytes, a string column above its value_capacity. nsel ==
+ * 0 or no rows: OXH_OK, value_bytes and stats4 zeroed, nothing else written. A failed allocation is OXH_ERR_NOMEM
+ * with the outputs untouched. */
+#define OXH_CSV_NO_QUOTE 256
+#define OXH_CSV_HAS_HEADER 1
+#define OXH_CSV_INT64 1
+#define OXH_CSV_FLOAT64 2
+#define OXH_CSV_BOOL 3
+#define OXH_CSV_STRING 4
+#define OXH_CSV_STRING64 5
+int oxh_csv_open_device(oxh_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, uint32_t separator, uint32_t quote, uint32_t flags,
+                        void** out, uint64_t* stats8, void* stream);
+int oxh_csv_open_host(oxh_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, uint32_t separator, uint32_t quote, uint32_t flags,
+                      void** out, uint64_t* stats8);
+int oxh_csv_close(void* csv);
+int oxh_csv_header(void* csv, uint8_t* names, uint64_t capacity, uint64_t* name_offsets, uint64_t* names_bytes);
+int oxh_csv_infer(void* csv, uint64_t max_rows, uint32_t* types);
+int oxh_csv_columns_device(void* csv, uint32_t nsel, const uint32_t* col_idx, const uint32_t* types, const uint64_t* value_capacity,
+                           void* const* d_values, void* const* d_offsets, uint8_t* const* d_validity, uint64_t* value_bytes,
+                           uint64_t* stats4, void* stream);
+int oxh_csv_columns_host(void* csv, uint32_t nsel, const uint32_t* col_idx, const uint32_t* types, const uint64_t* value_capacity,
+                         void* const* values, void* const* offsets, uint8_t* const* validity, uint64_t* value_bytes,
+                         uint64_t* stats4);
+
 /* ---------------------------------------------------------------- K2: merkle parent nodes */
 /* get_combined_hash (hasher.rs:67-80) x n on the device:
  * XXH3-128(content.to_le_bytes() || metadata.to_le_bytes()), inputs as (lo, hi) pairs. */

@@ -43,7 +43,8 @@ _FROM_TABULAR = ("KeyedDiff", "STATUS_NAMES", "keyed_diff_digests", "keyed_diff_
                  "embedding_take", "embedding_take_device", "page_rows", "nearest_neighbors", "nearest_neighbors_device",
                  "sort_by_similarity", "sort_by_similarity_device", "concat", "concat_device", "slice_range", "parse_slice",
                  "slice_rows", "slice_rows_device", "head", "head_device", "tail", "tail_device", "page", "page_device", "vstack",
-                 "vstack_device")
+                 "vstack_device", "CsvStats", "CsvColumnStats", "CsvFile", "CSV_TYPE_NAMES", "read_csv", "read_csv_device", "csv_shape",
+                 "csv_schema")
 
 
 def __getattr__(name):

@@ -63,6 +63,13 @@ OXH_FILTER_MAX_LITERAL_BYTES = 4096   # all byte literals of one call together
 OXH_EMB_FIXED = 0       # the layouts of an embedding column: Arrow FixedSizeList<float32>[dim]
 OXH_EMB_LIST32 = 1      # Arrow List<float32>: int32 offsets in elements
 OXH_EMB_LIST64 = 2      # Arrow LargeList<float32>: int64 offsets in elements
+OXH_CSV_NO_QUOTE = 256  # no byte is a quote
+OXH_CSV_HAS_HEADER = 1  # flags: the first kept record names the columns
+OXH_CSV_INT64 = 1       # the types of a CSV column
+OXH_CSV_FLOAT64 = 2
+OXH_CSV_BOOL = 3
+OXH_CSV_STRING = 4      # OXH_COL_BYTES32
+OXH_CSV_STRING64 = 5    # OXH_COL_BYTES64
 
 _u64 = ctypes.c_uint64
 _u32 = ctypes.c_uint32
@@ -189,6 +196,15 @@ SIGNATURES = {
     "oxh_embedding_similarity_host": (_int, [_vp, _u32, _u64, _u32, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64p]),
     "oxh_embedding_take_device": (_int, [_vp, _u32, _u64, _u32, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64p, _vp]),
     "oxh_embedding_take_host": (_int, [_vp, _u32, _u64, _u32, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64p]),
+    "oxh_csv_open_device": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, ctypes.POINTER(_vp), _u64p, _vp]),
+    "oxh_csv_open_host": (_int, [_vp, _vp, _u64, _u32, _u32, _u32, ctypes.POINTER(_vp), _u64p]),
+    "oxh_csv_close": (_int, [_vp]),
+    "oxh_csv_header": (_int, [_vp, _vp, _u64, _u64p, _u64p]),
+    "oxh_csv_infer": (_int, [_vp, _u64, ctypes.POINTER(_u32)]),
+    "oxh_csv_columns_device": (_int, [_vp, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32), _u64p, ctypes.POINTER(_vp),
+                                      ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u64p, _u64p, _vp]),
+    "oxh_csv_columns_host": (_int, [_vp, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32), _u64p, ctypes.POINTER(_vp),
+                                    ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u64p, _u64p]),
     "oxh_comm_check": (_int, [_int]),
     "oxh_ctx_counters": (_int, [_vp, _u64p, _int]),
     "oxh_comm_unique_id": (_int, [ctypes.c_char_p]),

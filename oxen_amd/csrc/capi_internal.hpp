@@ -37,6 +37,11 @@
 //                      selected rows by per-workgroup partial sums added in a fixed order, the cosine similarity of
 //                      every row with its descending order key, the row sort above for the permutation, the take
 //                      of a page's vectors
+//   csv_read.hip       CSV bytes to a record index and to typed Arrow columns (oxh_csv_*): quote parity by a
+//                      prefix-xor over per-tile quote counts, the delimiters outside quotes by count, scan, emit,
+//                      the kept records' row map, then one lane per row for every column (csv_number.hpp's parsers,
+//                      shared with the host), the floats the device cannot round in one operation converted on the
+//                      host (csv_host.hpp)
 // There is no CPU hashing path: every digest this library returns was computed on the GPU.
 #pragma once
 

@@ -1896,3 +1896,280 @@ def vstack_device(frames: Sequence[Mapping], stream=None, ctx: Optional[_capi.Co
     """`vstack` over frames of device `Column`s, through `concat_device`."""
     frames = _vstack_frames(frames)
     return dict(zip(frames[0], concat_device([list(f.values()) for f in frames], stream=stream, ctx=ctx)))
+
+
+# ---------------------------------------------------------------- CSV: record index and typed columns (oxh_csv_*)
+CSV_TYPE_NAMES = {_capi.OXH_CSV_INT64: "Int64", _capi.OXH_CSV_FLOAT64: "Float64", _capi.OXH_CSV_BOOL: "Boolean",
+                  _capi.OXH_CSV_STRING: "String", _capi.OXH_CSV_STRING64: "LargeString"}   # polars' dtype names
+_CSV_TYPE_OF = {name: code for code, name in CSV_TYPE_NAMES.items()}
+
+
+class CsvStats(NamedTuple):
+    """stats8 of oxh_csv_open_*."""
+    records: int
+    rows: int
+    ncols: int
+    delimiters: int
+    skipped_empty: int
+    short_records: int
+    long_records: int
+    ended_in_quotes: int
+
+
+class CsvColumnStats(NamedTuple):
+    """stats4 of one selected column of oxh_csv_columns_*."""
+    null_empty: int
+    null_unparsable: int
+    deferred: int
+    value_bytes: int
+
+
+def _csv_type(t) -> int:
+    if isinstance(t, str):
+        if t not in _CSV_TYPE_OF:
+            raise _capi.OxenError(f"unknown CSV column type {t!r} (one of {sorted(_CSV_TYPE_OF)})", _capi.OXH_ERR_INVALID)
+        return _CSV_TYPE_OF[t]
+    return int(t)
+
+
+def _csv_byte(ch, what, none=None) -> int:
+    if ch is None and none is not None:
+        return none
+    raw = ch.encode("utf-8") if isinstance(ch, str) else bytes(ch)
+    if len(raw) != 1:
+        raise _capi.OxenError(f"the {what} is one byte, got {ch!r}", _capi.OXH_ERR_INVALID)
+    return raw[0]
+
+
+class CsvFile:
+    """The record index of one CSV buffer (an oxh_csv_open_* handle): `stats`, `names`, `infer`, `measure`,
+    `columns`. data: bytes / a uint8 numpy array (the host form, which owns a device copy), or with device=True a
+    uint8 torch tensor on the device, which the object keeps alive. The rules are include/oxen_hash.h's "CSV": quotes
+    by parity, records at '\\n' outside quotes, ragged records truncated or filled with nulls, unparsable text null.
+    Dialect sniffing is the caller's: delimiter and quote_char are one byte each (quote_char None: no quoting)."""
+
+    def __init__(self, data, delimiter=",", quote_char='"', has_header: bool = True, ctx: Optional[_capi.Context] = None,
+                 device: bool = False, stream=None):
+        self.device = device
+        self.ctx = ctx
+        self.stream = stream
+        self.handle = None
+        sep = _csv_byte(delimiter, "delimiter")
+        quote = _csv_byte(quote_char, "quote", none=_capi.OXH_CSV_NO_QUOTE)
+        flags = _capi.OXH_CSV_HAS_HEADER if has_header else 0
+        out = ctypes.c_void_p()
+        stats = np.zeros(8, dtype=np.uint64)
+        if device:
+            from .device import _require_cuda, _stream
+
+            _require_cuda(data)
+            if data.element_size() != 1 or not data.is_contiguous():
+                raise _capi.OxenError("the CSV bytes are a contiguous uint8 tensor", _capi.OXH_ERR_INVALID)
+            self.data = data
+            _capi.check(_capi.lib().oxh_csv_open_device(_handle(ctx), data.data_ptr() if data.numel() else None, data.numel(), sep, quote,
+                                                        flags, ctypes.byref(out), stats.ctypes.data_as(_capi._u64p), _stream(stream)),
+                        "oxh_csv_open_device")
+        else:
+            self.data = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+            _capi.check(_capi.lib().oxh_csv_open_host(_handle(ctx), self.data.ctypes.data if self.data.size else None, self.data.size, sep,
+                                                      quote, flags, ctypes.byref(out), stats.ctypes.data_as(_capi._u64p)),
+                        "oxh_csv_open_host")
+        self.handle = out
+        self.stats = CsvStats(*(int(x) for x in stats))
+        self.has_header = bool(has_header)
+        self._names = None
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            _capi.lib().oxh_csv_close(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def raw_names(self) -> list:
+        """The header's names as bytes; without a header none."""
+        if self._names is None:
+            n = self.stats.ncols
+            offsets, size = np.zeros(n + 1, dtype=np.uint64), ctypes.c_uint64(0)
+            L = _capi.lib()
+            _capi.check(L.oxh_csv_header(self.handle, None, 0, offsets.ctypes.data_as(_capi._u64p), ctypes.byref(size)), "oxh_csv_header")
+            buf = np.zeros(max(size.value, 1), dtype=np.uint8)
+            _capi.check(L.oxh_csv_header(self.handle, buf.ctypes.data, size.value, offsets.ctypes.data_as(_capi._u64p), ctypes.byref(size)),
+                        "oxh_csv_header")
+            raw = buf.tobytes()
+            self._names = [raw[int(offsets[c]):int(offsets[c + 1])] for c in range(n)] if self.has_header else []
+        return self._names
+
+    @property
+    def names(self) -> list:
+        """The column names: the header's (invalid UTF-8 replaced, a repeated name as `name_duplicated_k`, polars'
+        spelling), or column_1 .. without a header."""
+        if not self.has_header:
+            return [f"column_{c + 1}" for c in range(self.stats.ncols)]
+        seen, out = {}, []
+        for raw in self.raw_names:
+            name = raw.decode("utf-8", errors="replace")
+            k = seen.get(name, 0)
+            seen[name] = k + 1
+            out.append(name if k == 0 else f"{name}_duplicated_{k - 1}")
+        return out
+
+    def infer(self, rows: int = 10000) -> list:
+        """oxh_csv_infer: one OXH_CSV_* per column from the first `rows` data rows."""
+        types = (ctypes.c_uint32 * max(self.stats.ncols, 1))()
+        _capi.check(_capi.lib().oxh_csv_infer(self.handle, int(rows), types), "oxh_csv_infer")
+        return [int(types[c]) for c in range(self.stats.ncols)]
+
+    def _selection(self, cols, types):
+        cols, types = [int(c) for c in cols], [_csv_type(t) for t in types]
+        if len(cols) != len(types):
+            raise _capi.OxenError("one type per selected column", _capi.OXH_ERR_INVALID)
+        n = max(len(cols), 1)
+        return cols, types, (ctypes.c_uint32 * n)(*cols), (ctypes.c_uint32 * n)(*types)
+
+    def _call(self, nsel, col_idx, type_words, capacity, values, offsets, validity):
+        value_bytes, stats = np.zeros(max(nsel, 1), dtype=np.uint64), np.zeros(4 * max(nsel, 1), dtype=np.uint64)
+        L = _capi.lib()
+        args = (self.handle, nsel, col_idx, type_words, None if capacity is None else capacity.ctypes.data_as(_capi._u64p), values, offsets,
+                validity, value_bytes.ctypes.data_as(_capi._u64p), stats.ctypes.data_as(_capi._u64p))
+        if self.device:
+            from .device import _stream
+
+            _capi.check(L.oxh_csv_columns_device(*args, _stream(self.stream)), "oxh_csv_columns_device")
+        else:
+            _capi.check(L.oxh_csv_columns_host(*args), "oxh_csv_columns_host")
+        return ([int(x) for x in value_bytes[:nsel]], [CsvColumnStats(*(int(x) for x in stats[4 * k:4 * k + 4])) for k in range(nsel)])
+
+    def measure(self, cols, types):
+        """(value_bytes, [CsvColumnStats]) of the selected columns without writing them."""
+        cols, types, col_idx, type_words = self._selection(cols, types)
+        return self._call(len(cols), col_idx, type_words, None, None, None, None)
+
+    def columns(self, cols, types, with_stats: bool = False):
+        """The selected columns (indices) as `Column`s of the given OXH_CSV_* types (or polars' dtype names): numpy
+        arrays in the host form, torch tensors on the device in the device form. Validity is always there."""
+        cols, types, col_idx, type_words = self._selection(cols, types)
+        nsel, n = len(cols), self.stats.rows
+        strings = [t in (_capi.OXH_CSV_STRING, _capi.OXH_CSV_STRING64) for t in types]
+        sizes = [0] * nsel   # the bytes of the string columns, and only they are measured
+        which = [k for k in range(nsel) if strings[k]]
+        if which:
+            for k, size in zip(which, self.measure([cols[k] for k in which], [types[k] for k in which])[0]):
+                sizes[k] = size
+        if self.device:
+            import torch
+
+            dev = self.data.device
+            make = lambda count, dtype: torch.empty(count, dtype=dtype, device=dev)   # noqa: E731
+            ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None      # noqa: E731
+            i64, f64, u8, i32 = torch.int64, torch.float64, torch.uint8, torch.int32
+        else:
+            make = lambda count, dtype: np.zeros(count, dtype=dtype)                   # noqa: E731
+            ptr = lambda a: a.ctypes.data if a is not None and a.size else None        # noqa: E731
+            i64, f64, u8, i32 = np.int64, np.float64, np.uint8, np.int32
+        out = []
+        capacity = np.zeros(max(nsel, 1), dtype=np.uint64)
+        for k, t in enumerate(types):
+            validity = make((n + 7) // 8, u8)
+            if strings[k]:
+                values, offsets = make(sizes[k], u8), make(n + 1, i64 if t == _capi.OXH_CSV_STRING64 else i32)
+                if n == 0:
+                    offsets[:] = 0
+                capacity[k] = sizes[k]
+                kind = OXH_COL_BYTES64 if t == _capi.OXH_CSV_STRING64 else OXH_COL_BYTES32
+            elif t == _capi.OXH_CSV_BOOL:
+                values, offsets, kind = make((n + 7) // 8, u8), None, OXH_COL_BOOL
+                capacity[k] = (n + 7) // 8
+            else:
+                values, offsets, kind = make(n, i64 if t == _capi.OXH_CSV_INT64 else f64), None, OXH_COL_FIXED8
+                capacity[k] = 8 * n
+            out.append(Column(kind, n, values, offsets, validity))
+        m = max(nsel, 1)
+        tables = [(ctypes.c_void_p * m)(*[ptr(getattr(c, field)) for c in out]) for field in ("values", "offsets", "validity")]
+        _, stats = self._call(nsel, col_idx, type_words, capacity, *tables)
+        return (out, stats) if with_stats else out
+
+
+def _csv_bytes(path_or_bytes):
+    if isinstance(path_or_bytes, (bytes, bytearray, memoryview, np.ndarray)):
+        return path_or_bytes, None
+    path = str(path_or_bytes)
+    with open(path, "rb") as f:
+        return f.read(), path
+
+
+def _csv_delimiter(delimiter, path):
+    # the reference sniffs the dialect (qsv_sniffer) and falls back to ','; sniffing stays with the caller, and a
+    # .tsv file reads with tabs
+    if delimiter is not None:
+        return delimiter
+    return "\t" if path is not None and path.lower().endswith(".tsv") else ","
+
+
+def _csv_frame(f: CsvFile, schema, columns, infer_rows) -> dict:
+    names = f.names
+    if columns is None:
+        picked = list(range(len(names)))
+    else:
+        picked = []
+        for c in columns:
+            if isinstance(c, str) and c not in names:
+                raise _capi.OxenError(f"no column {c!r} in the CSV header {names}", _capi.OXH_ERR_INVALID)
+            picked.append(names.index(c) if isinstance(c, str) else int(c))
+    inferred = None
+    types = []
+    for c in picked:
+        given = None if schema is None else (schema.get(names[c]) if isinstance(schema, Mapping) else schema[c])
+        if given is None:
+            inferred = inferred if inferred is not None else f.infer(infer_rows)
+            given = inferred[c]
+        types.append(_csv_type(given))
+    return dict(zip([names[c] for c in picked], f.columns(picked, types)))
+
+
+def read_csv(path_or_bytes, delimiter=None, quote_char='"', has_header: bool = True, schema=None, columns=None,
+             infer_rows: int = 10000, ctx: Optional[_capi.Context] = None) -> dict:
+    """`read_df_csv` (core/df/tabular.rs:39-71) on the device: a CSV file (a path) or its bytes to an ordered
+    {name: Column} in host memory that every function of this module takes. delimiter: one byte; None reads a
+    `.tsv` path with tabs and anything else with commas (the reference's sniffing stays with the caller).
+    quote_char None: no quoting. schema: {name: type} or a sequence by column index, a type being an OXH_CSV_* code
+    or polars' dtype name ("Int64", "Float64", "Boolean", "String", "LargeString"); columns without one are inferred
+    from the first infer_rows rows (the reference's infer_schema_length). columns: the names or indices to read."""
+    data, path = _csv_bytes(path_or_bytes)
+    with CsvFile(data, _csv_delimiter(delimiter, path), quote_char, has_header, ctx=ctx) as f:
+        return _csv_frame(f, schema, columns, infer_rows)
+
+
+def read_csv_device(d_bytes, delimiter=",", quote_char='"', has_header: bool = True, schema=None, columns=None,
+                    infer_rows: int = 10000, ctx: Optional[_capi.Context] = None, stream=None) -> dict:
+    """`read_csv` over the file's bytes already on the device (a uint8 torch tensor, say after the add hashed
+    them): device `Column`s that every `_device` function of this module accepts unchanged. Blocks."""
+    with CsvFile(d_bytes, delimiter, quote_char, has_header, ctx=ctx, device=True, stream=stream) as f:
+        return _csv_frame(f, schema, columns, infer_rows)
+
+
+def csv_shape(path_or_bytes, delimiter=None, quote_char='"', has_header: bool = True, ctx: Optional[_capi.Context] = None) -> tuple:
+    """(width, height) of the tabular metadata (repositories/metadata/tabular.rs:10-25): the columns and the data
+    rows, by the index alone -- a newline inside a quoted field ends no record."""
+    data, path = _csv_bytes(path_or_bytes)
+    with CsvFile(data, _csv_delimiter(delimiter, path), quote_char, has_header, ctx=ctx) as f:
+        return f.stats.ncols, f.stats.rows
+
+
+def csv_schema(path_or_bytes, delimiter=None, quote_char='"', has_header: bool = True, infer_rows: int = 10000,
+               ctx: Optional[_capi.Context] = None) -> list:
+    """[(name, dtype name)] of the tabular metadata: the header's names and the inferred types."""
+    data, path = _csv_bytes(path_or_bytes)
+    with CsvFile(data, _csv_delimiter(delimiter, path), quote_char, has_header, ctx=ctx) as f:
+        return list(zip(f.names, [CSV_TYPE_NAMES[t] for t in f.infer(infer_rows)]))
