@@ -1042,6 +1042,79 @@ int oxh_csv_columns_host(void* csv, uint32_t nsel, const uint32_t* col_idx, cons
                          void* const* values, void* const* offsets, uint8_t* const* validity, uint64_t* value_bytes,
                          uint64_t* stats4);
 
+/* ---------------------------------------------------------------- CSV text: typed Arrow columns to the file's bytes
+ * Every path of the reference that produces a frame ends in `write_df` (core/df/tabular.rs:1492-1547): `oxen df
+ * --output` / `--write` (command/df.rs:20,25,52), the diff's output (cmd/diff.rs:343, repositories/diffs.rs:1378), the
+ * tabular merge, restore and checkout results (repositories/merge.rs:872, restore.rs:496, checkout.rs:182), the
+ * workspace commit (repositories/workspaces/data_frames.rs:223) and oxen-py's df_utils.rs:19. oxh_write_csv_* do its
+ * `csv` and `tsv` arms on the device: the columns of this header's own description (what oxh_csv_columns_* and every
+ * tabular entry above produce) to the bytes of the file. (The oxh_csv_* names are the reader's seven entries over
+ * its handle; the writer has no handle and is named by what it does.)
+ *
+ * The rules restate polars 0.49.1's CsvWriter as the reference configures it (include_header(true),
+ * with_separator(delimiter), everything else default). They are NOT pinned by a run of polars.
+ *   Records. The header record, when OXH_CSV_HAS_HEADER is set, holds the column names written by the string rule;
+ *     one record per row follows; fields are joined by the one-byte separator; every record, the last one included,
+ *     ends with '\n'. There is no BOM and no '\r'.
+ *   Null cell (any type): no bytes.
+ *   OXH_CSV_INT64    decimal digits, '-' in front of a negative, never '+'; INT64_MIN is -9223372036854775808.
+ *   OXH_CSV_BOOL     true / false.
+ *   OXH_CSV_FLOAT64  ryu's Buffer::format. A finite value: the shortest digits that read back as the value, nearest
+ *     to it; with d those digits (L of them, no trailing zero), the value d x 10^k and kk = L + k:
+ *       0 <= k and kk <= 16   digits, k zeros, ".0"         12.0 -> 12.0, 1e15 -> 1000000000000000.0
+ *       0 < kk <= 16          the point after kk digits     12.5 -> 12.5
+ *       -5 < kk <= 0          "0.", -kk zeros, digits       1e-5 -> 0.00001, 0.1 -> 0.1
+ *       L == 1                d "e" (kk - 1)                1e16 -> 1e16, 1e-6 -> 1e-6
+ *       otherwise             d0 "." rest "e" (kk - 1)      1.5e16 -> 1.5e16, 1.25e-7 -> 1.25e-7
+ *     with no '+' and no zero padding in the exponent. The zeros are 0.0 and -0.0. Every NaN is NaN (no sign, no
+ *     payload); the infinities are inf / -inf.
+ *   OXH_CSV_STRING / OXH_CSV_STRING64 (the column is OXH_COL_BYTES32 / OXH_COL_BYTES64): quote style "necessary". A
+ *     cell is quoted iff it is empty, or contains the separator, the quote byte, '\n' or '\r'; inside the quotes every
+ *     quote byte is doubled; all other bytes are copied as they are (no UTF-8 check). An empty string is "" (two
+ *     quote bytes): that keeps it apart from a null, and the reader's "Nulls" rule reads it back as an empty string.
+ *   Floats on the device. The device writes a double itself where one IEEE division proves its shortest digits: a
+ *     normal |v| < 1e15 whose digits are an integer m < 1e15 with |v| == double(m) / 10^j for a j in 0 .. 22, and the
+ *     zeros, infinities and NaNs. Every other finite value is DEFERRED -- subnormals, |v| >= 1e15, doubles with 16 or
+ *     17 shortest digits (the output of most arithmetic), digits further than 22 places behind the point: compacted
+ *     in (row, column) order on the device, the bits brought down, formatted on the host (std::to_chars, then the
+ *     same digits-to-text function) and copied into place inside the same blocking call. stats4[2] counts them; a
+ *     column of such doubles pays a host conversion per cell.
+ *   One column and a null. A one-column frame writes a null row as an empty record, which oxh_csv_open_* skips (its
+ *     "Records" rule): reading the file back loses exactly those rows. Frames of two and more columns round-trip.
+ *   Stated and not built: narrower integers and floats, dates, float_precision, other quote styles, a null_value.
+ *
+ * Inputs: nrows rows of ncols columns; types[c] (OXH_CSV_*) says how column c is written and kinds[c] (OXH_COL_*)
+ * what its arrays are; values / offsets / validity / bit_offsets as oxh_row_hashes_* takes them; the column names
+ * as bytes one after the other in names with ncols + 1 name_offsets (read only with OXH_CSV_HAS_HEADER; host memory
+ * in both forms). Outputs: the file's bytes in out (capacity bytes; device memory in _device, host memory in _host);
+ * out_bytes = the file's size; stats4 = {bytes, quoted cells (the header's included), deferred float cells, null
+ * cells}. With out NULL the call only measures (out_bytes, stats4), as the take, the concat and oxh_csv_columns_* do.
+ * With a capacity below the need nothing is written to out, out_bytes and stats4 are set and the call returns
+ * OXH_ERR_INVALID. nrows == 0 writes the header alone. Both forms block until complete; stream (hipStream_t, NULL =
+ * the null stream) orders the device form's work, the host form stages its columns through one device block and
+ * uses the ctx's stream. A pair of offsets that is negative or decreases is never read through.
+ * OXH_ERR_INVALID, before OXH_ERR_NODEVICE (there is no CPU path), in this order: NULL types, kinds, values, offsets,
+ * validity or bit_offsets; ncols == 0; a separator above 255; a quote of OXH_CSV_NO_QUOTE (the writer always has a
+ * quote byte) or above 255; a separator that is '\n' or '\r'; a quote that is '\n' or '\r'; a quote equal to the
+ * separator; a separator, then a quote, that can occur in the text of a number or boolean (0-9, '+', '-', '.', the
+ * ASCII letters); unknown flags; an unknown type; a column whose kind does not fit its type (INT64 / FLOAT64 need
+ * OXH_COL_FIXED8, BOOL needs OXH_COL_BOOL, STRING needs OXH_COL_BYTES32, STRING64 needs OXH_COL_BYTES64); with
+ * OXH_CSV_HAS_HEADER: NULL name_offsets, name_offsets that decrease, NULL names with name bytes; NULL out_bytes or
+ * stats4; more than 2^40 rows; with rows, per column: a byte column without offsets, another column without values,
+ * and in the host form offsets that are negative or decrease, bytes without values; then OXH_ERR_NODEVICE; then a
+ * NULL ctx; then, after the lengths were measured and before anything is written: a pair of offsets that is negative
+ * or decreases, a byte column with bytes and no values, a single row whose text is 2^32 bytes or more; then a
+ * capacity below the need. A failed allocation is OXH_ERR_NOMEM with the outputs untouched. */
+int oxh_write_csv_device(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const uint32_t* types, const uint32_t* kinds,
+                         const void* const* d_values, const void* const* d_offsets, const uint8_t* const* d_validity,
+                         const uint64_t* bit_offsets, const uint8_t* names, const uint64_t* name_offsets, uint32_t separator,
+                         uint32_t quote, uint32_t flags, uint8_t* d_out, uint64_t capacity, uint64_t* out_bytes, uint64_t* stats4,
+                         void* stream);
+int oxh_write_csv_host(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const uint32_t* types, const uint32_t* kinds,
+                       const void* const* values, const void* const* offsets, const uint8_t* const* validity,
+                       const uint64_t* bit_offsets, const uint8_t* names, const uint64_t* name_offsets, uint32_t separator,
+                       uint32_t quote, uint32_t flags, uint8_t* out, uint64_t capacity, uint64_t* out_bytes, uint64_t* stats4);
+
 /* ---------------------------------------------------------------- K2: merkle parent nodes */
 /* get_combined_hash (hasher.rs:67-80) x n on the device:
  * XXH3-128(content.to_le_bytes() || metadata.to_le_bytes()), inputs as (lo, hi) pairs. */

@@ -18,7 +18,9 @@ Modules:
                rows grouped by equality on key columns (group_rows, unique, unique_count, is_duplicated,
                n_duped_rows), and the rows a `--filter` selects (parse_filter, filter_terms, filter_rows, filter_df),
                and the embedding query: mean of the selected vectors, cosine similarity of every row, the ranked
-               page (embedding_mean, cosine_similarity, embedding_take, nearest_neighbors, sort_by_similarity)
+               page (embedding_mean, cosine_similarity, embedding_take, nearest_neighbors, sort_by_similarity),
+               and the CSV file itself: read on the device (read_csv, read_csv_device) and written there (write_csv,
+               write_csv_device, write_df)
   procpool  -- file hashing sharded over reader processes (the open/close floor is per process)
   shard     -- multi-GPU sharding and the RCCL digest gather
   device    -- device-resident (HBM) batch entry points over torch buffers
@@ -44,7 +46,7 @@ _FROM_TABULAR = ("KeyedDiff", "STATUS_NAMES", "keyed_diff_digests", "keyed_diff_
                  "sort_by_similarity", "sort_by_similarity_device", "concat", "concat_device", "slice_range", "parse_slice",
                  "slice_rows", "slice_rows_device", "head", "head_device", "tail", "tail_device", "page", "page_device", "vstack",
                  "vstack_device", "CsvStats", "CsvColumnStats", "CsvFile", "CSV_TYPE_NAMES", "read_csv", "read_csv_device", "csv_shape",
-                 "csv_schema")
+                 "csv_schema", "CsvWriteStats", "write_csv", "write_csv_device", "write_df")
 
 
 def __getattr__(name):

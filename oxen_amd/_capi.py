@@ -205,6 +205,12 @@ SIGNATURES = {
                                       ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u64p, _u64p, _vp]),
     "oxh_csv_columns_host": (_int, [_vp, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32), _u64p, ctypes.POINTER(_vp),
                                     ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u64p, _u64p]),
+    "oxh_write_csv_device": (_int, [_vp, _u64, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_vp),
+                                    ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u64p, _vp, _u64p, _u32, _u32, _u32, _vp, _u64,
+                                    _u64p, _u64p, _vp]),
+    "oxh_write_csv_host": (_int, [_vp, _u64, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_vp),
+                                  ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u64p, _vp, _u64p, _u32, _u32, _u32, _vp, _u64,
+                                  _u64p, _u64p]),
     "oxh_comm_check": (_int, [_int]),
     "oxh_ctx_counters": (_int, [_vp, _u64p, _int]),
     "oxh_comm_unique_id": (_int, [ctypes.c_char_p]),

@@ -42,6 +42,10 @@
 //                      the kept records' row map, then one lane per row for every column (csv_number.hpp's parsers,
 //                      shared with the host), the floats the device cannot round in one operation converted on the
 //                      host (csv_host.hpp)
+//   csv_write.hip      typed Arrow columns to the bytes of a CSV file (oxh_write_csv_*): one lane per row over all its
+//                      columns for the row's text length, the scan, then a wave's 64 rows assembled in LDS and stored
+//                      on the destination's 16-byte grid (csv_text.hpp's text functions, shared with the host), the
+//                      doubles the device cannot prove with one division formatted on the host
 // There is no CPU hashing path: every digest this library returns was computed on the GPU.
 #pragma once
 

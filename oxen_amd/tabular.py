@@ -38,6 +38,10 @@ every row with it, the rows ranked from the most similar on and one page of them
 or more frames written one after the other, as copies -- `concat`, `concat_device`, `slice_range`, `parse_slice`,
 `slice_rows`, `head`, `tail`, `page`, `vstack`, each frame function with a `_device` twin.
 
+`oxh_csv_*` reads a CSV file into such columns on the device (`read_csv`, `read_csv_device`, `CsvFile`) and
+`oxh_write_csv_*` writes them back as the file's bytes, which is how every path of the reference ends (`write_df`,
+core/df/tabular.rs:1492-1547) -- `write_csv`, `write_csv_device`, `write_df`.
+
 A frame is an ordered mapping from column name to `Column`. A row's bytes are, over the columns in the
 frame's order: nothing for a null, the raw little-endian bytes of Int8 / Int32 / Float32 / Int64 /
 Float64 / Datetime(ms), one byte 0 or 1 for a boolean, the UTF-8 bytes of a string. Every other dtype
@@ -2173,3 +2177,134 @@ def csv_schema(path_or_bytes, delimiter=None, quote_char='"', has_header: bool =
     data, path = _csv_bytes(path_or_bytes)
     with CsvFile(data, _csv_delimiter(delimiter, path), quote_char, has_header, ctx=ctx) as f:
         return list(zip(f.names, [CSV_TYPE_NAMES[t] for t in f.infer(infer_rows)]))
+
+
+# ---------------------------------------------------------------- CSV text: typed columns to the file's bytes (oxh_write_csv_*)
+class CsvWriteStats(NamedTuple):
+    """stats4 of oxh_write_csv_*."""
+    bytes: int
+    quoted_cells: int
+    deferred: int
+    nulls: int
+
+
+_WRITE_TYPE_OF_KIND = {OXH_COL_BOOL: _capi.OXH_CSV_BOOL, OXH_COL_BYTES32: _capi.OXH_CSV_STRING, OXH_COL_BYTES64: _capi.OXH_CSV_STRING64}
+_WRITE_TYPE_OF_DTYPE = {"int64": _capi.OXH_CSV_INT64, "torch.int64": _capi.OXH_CSV_INT64,
+                        "float64": _capi.OXH_CSV_FLOAT64, "torch.float64": _capi.OXH_CSV_FLOAT64}
+
+
+def _write_types(names, cols, types) -> list:
+    """One OXH_CSV_* per column: what `types` gives ({name: type} or a sequence by column), else what the Column's
+    kind says, a FIXED8 column by its dtype."""
+    out = []
+    for k, (name, c) in enumerate(zip(names, cols)):
+        given = None if types is None else (types.get(name) if isinstance(types, Mapping) else types[k])
+        if given is not None:
+            out.append(_csv_type(given))
+        elif c.kind in _WRITE_TYPE_OF_KIND:
+            out.append(_WRITE_TYPE_OF_KIND[c.kind])
+        elif c.kind == OXH_COL_FIXED8 and str(getattr(c.values, "dtype", None)) in _WRITE_TYPE_OF_DTYPE:
+            out.append(_WRITE_TYPE_OF_DTYPE[str(c.values.dtype)])
+        else:
+            raise _capi.OxenError(f"column {name!r} (kind {c.kind}, dtype {getattr(c.values, 'dtype', None)}) has no CSV text here: the "
+                                  "writer takes Int64, Float64, Boolean and strings -- cast the column, or name its type in types=",
+                                  _capi.OXH_ERR_INVALID)
+    return out
+
+
+def _write_head(frame: Mapping, delimiter, quote_char, include_header, types):
+    """What both forms pass in front of the column tables and behind them."""
+    names = list(frame.keys())
+    cols = list(frame.values())
+    if cols and any(c.nrows != cols[0].nrows for c in cols):
+        raise _capi.OxenError("the columns of a frame have one row count", _capi.OXH_ERR_INVALID)
+    n = max(len(cols), 1)
+    type_words = (ctypes.c_uint32 * n)(*_write_types(names, cols, types))
+    raw = [name.encode("utf-8") if isinstance(name, str) else bytes(name) for name in names]
+    name_offsets = np.zeros(len(raw) + 1, dtype=np.uint64)
+    np.cumsum([len(b) for b in raw], out=name_offsets[1:])
+    name_bytes = np.frombuffer(b"".join(raw) + b"\0", dtype=np.uint8)
+    tail = (_csv_byte(delimiter, "delimiter"), _csv_byte(quote_char, "quote", none=_capi.OXH_CSV_NO_QUOTE),
+            _capi.OXH_CSV_HAS_HEADER if include_header else 0)
+    return cols, type_words, name_bytes, name_offsets, tail
+
+
+def _write_call(fn, what, ctx, cols, type_words, tables, name_bytes, name_offsets, tail, out, capacity, *stream):
+    size, stats = ctypes.c_uint64(0), np.zeros(4, dtype=np.uint64)
+    nrows = cols[0].nrows if cols else 0
+    _capi.check(fn(_handle(ctx), nrows, len(cols), type_words, *tables, name_bytes.ctypes.data, name_offsets.ctypes.data_as(_capi._u64p),
+                   *tail, out, capacity, ctypes.byref(size), stats.ctypes.data_as(_capi._u64p), *stream), what)
+    return int(size.value), CsvWriteStats(*(int(x) for x in stats))
+
+
+def write_csv(frame: Mapping, path=None, delimiter=",", quote_char='"', include_header: bool = True, types=None,
+              ctx: Optional[_capi.Context] = None, with_stats: bool = False):
+    """oxh_write_csv_host: the frame (an ordered {name: Column}, or what `column` takes, in host memory) as the bytes
+    of a CSV file, by the rules of include/oxen_hash.h "CSV text" -- polars' CsvWriter as `write_df` configures it
+    (core/df/tabular.rs:1492-1547). With a path the bytes are also written there, through `AtomicFile` as the
+    reference does. types: {name: type} or a sequence by column for what the Column's kind does not say (a FIXED8
+    column is typed by its int64 / float64 dtype). The mapping's key order is the column order; `str` keys go out as
+    UTF-8."""
+    frame = _as_frame(frame)
+    cols, type_words, name_bytes, name_offsets, tail = _write_head(frame, delimiter, quote_char, include_header, types)
+    keep = []
+
+    def ptr(a):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a)
+        keep.append(a)
+        return a.ctypes.data if a.size else None
+
+    tables = _tables(cols, ptr)
+    fn = _capi.lib().oxh_write_csv_host
+    need, _ = _write_call(fn, "oxh_write_csv_host", ctx, cols, type_words, tables, name_bytes, name_offsets, tail, None, 0)
+    out = np.zeros(max(need, 1), dtype=np.uint8)
+    need, stats = _write_call(fn, "oxh_write_csv_host", ctx, cols, type_words, tables, name_bytes, name_offsets, tail, out.ctypes.data, need)
+    data = out[:need].tobytes()
+    if path is not None:
+        from .version_store import AtomicFile
+
+        AtomicFile(path, ctx).write(data)
+    return (data, stats) if with_stats else data
+
+
+def write_csv_device(frame: Mapping, delimiter=",", quote_char='"', include_header: bool = True, types=None,
+                     ctx: Optional[_capi.Context] = None, capacity: Optional[int] = None, stream=None, with_stats: bool = False):
+    """oxh_write_csv_device: the same over device `Column`s (what `read_csv_device`, `take_device`, `concat_device`
+    return); the file's bytes as a uint8 torch tensor on the device. It measures, allocates, then writes; a caller's
+    `capacity` (bytes) skips the measure, and a capacity below the need is the library's error. Blocks."""
+    import torch
+
+    from .device import _require_cuda, _stream
+
+    cols, type_words, name_bytes, name_offsets, tail = _write_head(frame, delimiter, quote_char, include_header, types)
+    tensors = [t for c in cols for t in (c.values, c.offsets, c.validity) if t is not None]
+    _require_cuda(*tensors)
+    if any(not t.is_contiguous() for t in tensors):
+        raise _capi.OxenError("column tensors must be contiguous", _capi.OXH_ERR_INVALID)
+    device = tensors[0].device if tensors else "cuda"
+    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()  # noqa: E731
+    tables = _tables(cols, ptr)
+    fn = _capi.lib().oxh_write_csv_device
+    head = (fn, "oxh_write_csv_device", ctx, cols, type_words, tables, name_bytes, name_offsets, tail)
+    if capacity is None:
+        capacity, _ = _write_call(*head, None, 0, _stream(stream))
+    out = torch.empty(max(int(capacity), 1), dtype=torch.uint8, device=device)
+    need, stats = _write_call(*head, out.data_ptr(), int(capacity), _stream(stream))
+    return (out[:need], stats) if with_stats else out[:need]
+
+
+def write_df(frame: Mapping, path, ctx: Optional[_capi.Context] = None) -> bytes:
+    """`write_df` (core/df/tabular.rs:1529-1547) for the two text formats this module reads: `.csv` with ',' and `.tsv`
+    with '\\t'. Any other extension raises the reference's "Unknown file type" error."""
+    import os
+
+    path = str(path)
+    ext = os.path.splitext(path)[1][1:] or None
+    if ext == "csv":
+        return write_csv(frame, path, ",", ctx=ctx)
+    if ext == "tsv":
+        return write_csv(frame, path, "\t", ctx=ctx)
+    shown = "None" if ext is None else f'Some("{ext}")'
+    raise _capi.OxenError(f'Unknown file type write_df "{path}" {shown}', _capi.OXH_ERR_INVALID)
