@@ -77,6 +77,8 @@ CSV_TEST_SRC = os.path.join(ROOT, "tests", "native", "csv_host_test.cpp")
 CSV_TEST = os.path.join(ROOT, "tests", "native", "csv_host_test")  # tests only: the CSV reader's parsers and host pieces
 CSV_WRITE_TEST_SRC = os.path.join(ROOT, "tests", "native", "csv_write_host_test.cpp")
 CSV_WRITE_TEST = os.path.join(ROOT, "tests", "native", "csv_write_host_test")  # tests only: the CSV writer's text functions
+CSV_FLOAT_CASES_SRC = os.path.join(ROOT, "tests", "native", "csv_float_cases.cpp")
+CSV_FLOAT_CASES = os.path.join(ROOT, "tests", "native", "csv_float_cases")  # tests only: both CSV float conversions over a test's cells
 FAKE_RCCL_SRC = os.path.join(ROOT, "tests", "native", "fake_rccl.cpp")
 # tests only: an "RCCL" for N processes on one GPU (OXH_RCCL_LIB), with and without ncclGather
 FAKE_RCCL = os.path.join(ROOT, "tests", "native", "libfake_rccl.so")
@@ -98,7 +100,8 @@ def build_host(force: bool = False, verbose: bool = False) -> str:
     (tests/native/group_rows_host_test.cpp), of the filter's terms and host pieces
     (tests/native/filter_rows_host_test.cpp), of the embedding query's host pieces and order key
     (tests/native/embedding_host_test.cpp), of the CSV reader's parsers and host pieces
-    (tests/native/csv_host_test.cpp) and of the CSV writer's text functions (tests/native/csv_write_host_test.cpp)."""
+    (tests/native/csv_host_test.cpp), of the CSV writer's text functions (tests/native/csv_write_host_test.cpp) and of
+    both CSV float conversions over cells a test sends in (tests/native/csv_float_cases.cpp)."""
     hdr = os.path.join(ROOT, "include", "oxen_hash.h")
     steps = [
         (HELPER, [HELPER_SRC, os.path.join(CSRC, "reader_pool.hpp"), hdr, LIB],
@@ -141,6 +144,9 @@ def build_host(force: bool = False, verbose: bool = False) -> str:
          ["g++", "-std=c++17", "-O2", "-Wall", "-o", CSV_TEST + ".tmp", CSV_TEST_SRC]),
         (CSV_WRITE_TEST, [CSV_WRITE_TEST_SRC, os.path.join(CSRC, "csv_text.hpp")],
          ["g++", "-std=c++17", "-O2", "-Wall", "-o", CSV_WRITE_TEST + ".tmp", CSV_WRITE_TEST_SRC]),
+        (CSV_FLOAT_CASES, [CSV_FLOAT_CASES_SRC, os.path.join(CSRC, "csv_host.hpp"), os.path.join(CSRC, "csv_number.hpp"),
+                           os.path.join(CSRC, "csv_text.hpp"), hdr],
+         ["g++", "-std=c++17", "-O2", "-Wall", "-o", CSV_FLOAT_CASES + ".tmp", CSV_FLOAT_CASES_SRC]),
     ]
     for target, extra in ((FAKE_RCCL, []), (FAKE_RCCL_NOGATHER, ["-DFAKE_NO_GATHER"])):
         steps.append((target, [FAKE_RCCL_SRC],
