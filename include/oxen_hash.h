@@ -1115,6 +1115,62 @@ int oxh_write_csv_host(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const uint3
                        const uint64_t* bit_offsets, const uint8_t* names, const uint64_t* name_offsets, uint32_t separator,
                        uint32_t quote, uint32_t flags, uint8_t* out, uint64_t capacity, uint64_t* out_bytes, uint64_t* stats4);
 
+/* ---------------------------------------------------------------- JSON text: typed Arrow columns to the file's bytes
+ * The reference turns a frame into JSON at two places: `write_df`'s `jsonl`, `ndjson` and `json` arms
+ * (core/df/tabular.rs:1469-1490, 1536-1538; JsonWriter with JsonFormat::JsonLines / JsonFormat::Json), and every
+ * data-frame view the server returns (JsonDataFrameView::json_from_df, view/json_data_frame_view.rs:268-285, and
+ * view/json_data_frame.rs:129: JsonWriter with JsonFormat::Json over the page). oxh_write_json_* do both on the
+ * device, over the same columns as oxh_write_csv_*.
+ *
+ * The rules restate polars 0.49.1's JsonWriter (polars-json's serializers). They are NOT pinned by a run of polars.
+ *   File shape. OXH_JSON_LINES (flags 0): one object per row, each followed by '\n', the last one too; zero rows
+ *     give zero bytes. OXH_JSON_ARRAY (flag 1): '[', the rows' objects joined by ',', ']', with no newline anywhere;
+ *     zero rows give []. A row is {"name":value,"name":value}: the columns in order, no spaces. A name is written by
+ *     the string rule; the names are not checked for duplicates.
+ *   Null cell (any type): null.
+ *   OXH_CSV_INT64    the CSV rule: decimal digits, '-' in front of a negative.
+ *   OXH_CSV_BOOL     true / false.
+ *   OXH_CSV_FLOAT64  a finite value is ryu's Buffer::format, exactly the CSV rule's five forms, with 0.0 and -0.0;
+ *     every NaN and both infinities are null.
+ *   OXH_CSV_STRING / OXH_CSV_STRING64: '"', the bytes, '"'; an empty string is "". '"' becomes \" and '\' becomes
+ *     \\; 0x08, 0x0C, 0x0A, 0x0D, 0x09 become \b, \f, \n, \r, \t; every other byte below 0x20 becomes \u00XX with
+ *     lowercase hex; everything else is copied as it is -- 0x7F, '/' and every byte at or above 0x80. There is no
+ *     UTF-8 check.
+ *   The type codes are the OXH_CSV_* above: they are this header's only column-type enum, not the CSV format's own.
+ *   Floats on the device: as in "CSV text". The doubles that one IEEE division does not prove are DEFERRED to the
+ *     host inside the same blocking call, through the same 32-byte slots and the same conversion; stats4[2] counts
+ *     them.
+ *   Stated and not built: lists and embeddings (polars writes a float32 by its own shortest digits), structs, dates,
+ *     narrower numbers, pretty printing.
+ *
+ * Inputs: as oxh_write_csv_* without separator and quote; names and name_offsets are always read (host memory in
+ * both forms); flags is OXH_JSON_LINES or OXH_JSON_ARRAY. Outputs: the file's bytes in out (capacity bytes; device
+ * memory in _device, host memory in _host); out_bytes = the file's size; stats4 = {bytes, string cells in which at
+ * least one byte was escaped (a name that needs escaping counts once when the frame has rows), deferred float cells,
+ * cells written as null (null cells and non-finite floats together)}. With out NULL the call only measures. With a
+ * capacity below the need nothing is written to out, out_bytes and stats4 are set and the call returns
+ * OXH_ERR_INVALID. Both forms block until complete; stream orders the device form's work, the host form stages its
+ * columns through one device block and uses the ctx's stream. A pair of offsets that is negative or decreases is
+ * never read through.
+ * OXH_ERR_INVALID, every message starting with "json write:", before OXH_ERR_NODEVICE (there is no CPU path), in this
+ * order: NULL types, kinds, values, offsets, validity or bit_offsets; ncols == 0; unknown flags; an unknown type; a
+ * column whose kind does not fit its type; NULL name_offsets, name_offsets that decrease, NULL names with name bytes;
+ * NULL out_bytes or stats4; more than 2^40 rows; with rows, per column: a byte column without offsets, another
+ * column without values, and in the host form offsets that are negative or decrease, bytes without values; then
+ * OXH_ERR_NODEVICE; then a NULL ctx; then, after the lengths were measured and before anything is written: a pair of
+ * offsets that is negative or decreases, a byte column with bytes and no values, a single row whose text is 2^32
+ * bytes or more; then a capacity below the need. A failed allocation is OXH_ERR_NOMEM with the outputs untouched. */
+#define OXH_JSON_LINES 0
+#define OXH_JSON_ARRAY 1
+int oxh_write_json_device(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const uint32_t* types, const uint32_t* kinds,
+                          const void* const* d_values, const void* const* d_offsets, const uint8_t* const* d_validity,
+                          const uint64_t* bit_offsets, const uint8_t* names, const uint64_t* name_offsets, uint32_t flags,
+                          uint8_t* d_out, uint64_t capacity, uint64_t* out_bytes, uint64_t* stats4, void* stream);
+int oxh_write_json_host(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const uint32_t* types, const uint32_t* kinds,
+                        const void* const* values, const void* const* offsets, const uint8_t* const* validity,
+                        const uint64_t* bit_offsets, const uint8_t* names, const uint64_t* name_offsets, uint32_t flags,
+                        uint8_t* out, uint64_t capacity, uint64_t* out_bytes, uint64_t* stats4);
+
 /* ---------------------------------------------------------------- K2: merkle parent nodes */
 /* get_combined_hash (hasher.rs:67-80) x n on the device:
  * XXH3-128(content.to_le_bytes() || metadata.to_le_bytes()), inputs as (lo, hi) pairs. */

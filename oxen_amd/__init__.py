@@ -20,7 +20,8 @@ Modules:
                and the embedding query: mean of the selected vectors, cosine similarity of every row, the ranked
                page (embedding_mean, cosine_similarity, embedding_take, nearest_neighbors, sort_by_similarity),
                and the CSV file itself: read on the device (read_csv, read_csv_device) and written there (write_csv,
-               write_csv_device, write_df)
+               write_csv_device, write_df), and the same columns as JSON Lines or one JSON array (write_jsonl, write_json and their
+               _device forms)
   procpool  -- file hashing sharded over reader processes (the open/close floor is per process)
   shard     -- multi-GPU sharding and the RCCL digest gather
   device    -- device-resident (HBM) batch entry points over torch buffers
@@ -46,7 +47,8 @@ _FROM_TABULAR = ("KeyedDiff", "STATUS_NAMES", "keyed_diff_digests", "keyed_diff_
                  "sort_by_similarity", "sort_by_similarity_device", "concat", "concat_device", "slice_range", "parse_slice",
                  "slice_rows", "slice_rows_device", "head", "head_device", "tail", "tail_device", "page", "page_device", "vstack",
                  "vstack_device", "CsvStats", "CsvColumnStats", "CsvFile", "CSV_TYPE_NAMES", "read_csv", "read_csv_device", "csv_shape",
-                 "csv_schema", "CsvWriteStats", "write_csv", "write_csv_device", "write_df")
+                 "csv_schema", "CsvWriteStats", "write_csv", "write_csv_device", "write_df", "JsonWriteStats", "write_jsonl",
+                 "write_jsonl_device", "write_json", "write_json_device")
 
 
 def __getattr__(name):

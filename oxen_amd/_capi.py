@@ -70,6 +70,8 @@ OXH_CSV_FLOAT64 = 2
 OXH_CSV_BOOL = 3
 OXH_CSV_STRING = 4      # OXH_COL_BYTES32
 OXH_CSV_STRING64 = 5    # OXH_COL_BYTES64
+OXH_JSON_LINES = 0      # flags of oxh_write_json_*: one object per row and line
+OXH_JSON_ARRAY = 1      # one array of the rows' objects
 
 _u64 = ctypes.c_uint64
 _u32 = ctypes.c_uint32
@@ -211,6 +213,11 @@ SIGNATURES = {
     "oxh_write_csv_host": (_int, [_vp, _u64, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_vp),
                                   ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u64p, _vp, _u64p, _u32, _u32, _u32, _vp, _u64,
                                   _u64p, _u64p]),
+    "oxh_write_json_device": (_int, [_vp, _u64, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_vp),
+                                     ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u64p, _vp, _u64p, _u32, _vp, _u64, _u64p, _u64p,
+                                     _vp]),
+    "oxh_write_json_host": (_int, [_vp, _u64, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_vp),
+                                   ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u64p, _vp, _u64p, _u32, _vp, _u64, _u64p, _u64p]),
     "oxh_comm_check": (_int, [_int]),
     "oxh_ctx_counters": (_int, [_vp, _u64p, _int]),
     "oxh_comm_unique_id": (_int, [ctypes.c_char_p]),

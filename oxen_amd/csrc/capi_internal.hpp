@@ -46,6 +46,11 @@
 //                      columns for the row's text length, the scan, then a wave's 64 rows assembled in LDS and stored
 //                      on the destination's 16-byte grid (csv_text.hpp's text functions, shared with the host), the
 //                      doubles the device cannot prove with one division formatted on the host
+//   json_write.hip     the same columns to the bytes of a JSON Lines or JSON file (oxh_write_json_*): the CSV writer's
+//                      passes with every row carrying its keys (built on the host, copied by the lanes), nulls and
+//                      non-finite floats as null, and every string quoted with its bytes 1, 2 or 6 wide
+//                      (json_text.hpp); a long cell that widens is escaped by the whole wave, a lane's place a wave
+//                      prefix sum of the widths, staged in LDS and stored in aligned 16-byte blocks
 // There is no CPU hashing path: every digest this library returns was computed on the GPU.
 #pragma once
 

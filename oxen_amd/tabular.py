@@ -40,7 +40,9 @@ or more frames written one after the other, as copies -- `concat`, `concat_devic
 
 `oxh_csv_*` reads a CSV file into such columns on the device (`read_csv`, `read_csv_device`, `CsvFile`) and
 `oxh_write_csv_*` writes them back as the file's bytes, which is how every path of the reference ends (`write_df`,
-core/df/tabular.rs:1492-1547) -- `write_csv`, `write_csv_device`, `write_df`.
+core/df/tabular.rs:1492-1547) -- `write_csv`, `write_csv_device`, `write_df`; `oxh_write_json_*` as JSON Lines or one
+JSON array (`write_df`'s jsonl / ndjson / json arms, and the text of a data-frame view) -- `write_jsonl`, `write_json` and
+their `_device` forms.
 
 A frame is an ordered mapping from column name to `Column`. A row's bytes are, over the columns in the
 frame's order: nothing for a null, the raw little-endian bytes of Int8 / Int32 / Float32 / Int64 /
@@ -2295,9 +2297,103 @@ def write_csv_device(frame: Mapping, delimiter=",", quote_char='"', include_head
     return (out[:need], stats) if with_stats else out[:need]
 
 
+# ---------------------------------------------------------------- JSON text: typed columns to the file's bytes (oxh_write_json_*)
+class JsonWriteStats(NamedTuple):
+    """stats4 of oxh_write_json_*."""
+    bytes: int
+    escaped_cells: int
+    deferred: int
+    nulls: int
+
+
+def _json_head(frame: Mapping, types, flags):
+    cols, type_words, name_bytes, name_offsets, _ = _write_head(frame, ",", '"', True, types)
+    return cols, type_words, name_bytes, name_offsets, (flags,)
+
+
+def _json_call(*args):
+    need, stats = _write_call(*args)
+    return need, JsonWriteStats(*stats)
+
+
+def _write_json_host(frame, path, flags, types, ctx, with_stats):
+    frame = _as_frame(frame)
+    cols, type_words, name_bytes, name_offsets, tail = _json_head(frame, types, flags)
+    keep = []
+
+    def ptr(a):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a)
+        keep.append(a)
+        return a.ctypes.data if a.size else None
+
+    tables = _tables(cols, ptr)
+    head = (_capi.lib().oxh_write_json_host, "oxh_write_json_host", ctx, cols, type_words, tables, name_bytes, name_offsets, tail)
+    need, _ = _json_call(*head, None, 0)
+    out = np.zeros(max(need, 1), dtype=np.uint8)
+    need, stats = _json_call(*head, out.ctypes.data, need)
+    data = out[:need].tobytes()
+    if path is not None:
+        from .version_store import AtomicFile
+
+        AtomicFile(path, ctx).write(data)
+    return (data, stats) if with_stats else data
+
+
+def _write_json_device(frame, flags, types, ctx, capacity, stream, with_stats):
+    import torch
+
+    from .device import _require_cuda, _stream
+
+    cols, type_words, name_bytes, name_offsets, tail = _json_head(frame, types, flags)
+    tensors = [t for c in cols for t in (c.values, c.offsets, c.validity) if t is not None]
+    _require_cuda(*tensors)
+    if any(not t.is_contiguous() for t in tensors):
+        raise _capi.OxenError("column tensors must be contiguous", _capi.OXH_ERR_INVALID)
+    device = tensors[0].device if tensors else "cuda"
+    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()  # noqa: E731
+    tables = _tables(cols, ptr)
+    head = (_capi.lib().oxh_write_json_device, "oxh_write_json_device", ctx, cols, type_words, tables, name_bytes, name_offsets, tail)
+    if capacity is None:
+        capacity, _ = _json_call(*head, None, 0, _stream(stream))
+    out = torch.empty(max(int(capacity), 1), dtype=torch.uint8, device=device)
+    need, stats = _json_call(*head, out.data_ptr(), int(capacity), _stream(stream))
+    return (out[:need], stats) if with_stats else out[:need]
+
+
+def write_jsonl(frame: Mapping, path=None, types=None, ctx: Optional[_capi.Context] = None, with_stats: bool = False):
+    """oxh_write_json_host with OXH_JSON_LINES: the frame (an ordered {name: Column}, or what `column` takes, in host
+    memory) as the bytes of a JSON Lines file, by the rules of include/oxen_hash.h "JSON text" -- polars' JsonWriter
+    with JsonFormat::JsonLines, `write_df`'s jsonl / ndjson arm (core/df/tabular.rs:1469-1490). path, types and the
+    key order are `write_csv`'s."""
+    return _write_json_host(frame, path, _capi.OXH_JSON_LINES, types, ctx, with_stats)
+
+
+def write_json(frame: Mapping, path=None, types=None, ctx: Optional[_capi.Context] = None, with_stats: bool = False):
+    """oxh_write_json_host with OXH_JSON_ARRAY: one array of the rows' objects -- JsonFormat::Json, `write_df`'s json
+    arm and the text of a data-frame view (view/json_data_frame_view.rs:268-285)."""
+    return _write_json_host(frame, path, _capi.OXH_JSON_ARRAY, types, ctx, with_stats)
+
+
+def write_jsonl_device(frame: Mapping, types=None, ctx: Optional[_capi.Context] = None, capacity: Optional[int] = None, stream=None,
+                       with_stats: bool = False):
+    """oxh_write_json_device with OXH_JSON_LINES over device `Column`s; the file's bytes as a uint8 torch tensor on the
+    device. It measures, allocates, then writes; a caller's `capacity` (bytes) skips the measure, and a capacity
+    below the need is the library's error. Blocks."""
+    return _write_json_device(frame, _capi.OXH_JSON_LINES, types, ctx, capacity, stream, with_stats)
+
+
+def write_json_device(frame: Mapping, types=None, ctx: Optional[_capi.Context] = None, capacity: Optional[int] = None, stream=None,
+                      with_stats: bool = False):
+    """oxh_write_json_device with OXH_JSON_ARRAY: what `json_from_df` makes of a page built on the device."""
+    return _write_json_device(frame, _capi.OXH_JSON_ARRAY, types, ctx, capacity, stream, with_stats)
+
+
 def write_df(frame: Mapping, path, ctx: Optional[_capi.Context] = None) -> bytes:
-    """`write_df` (core/df/tabular.rs:1529-1547) for the two text formats this module reads: `.csv` with ',' and `.tsv`
-    with '\\t'. Any other extension raises the reference's "Unknown file type" error."""
+    """`write_df` (core/df/tabular.rs:1529-1547) for the text formats this module writes: `.csv` with ',', `.tsv` with
+    '\\t', `.jsonl` / `.ndjson` as JSON Lines and `.json` as one array. Any other extension raises the reference's
+    "Unknown file type" error."""
     import os
 
     path = str(path)
@@ -2306,5 +2402,9 @@ def write_df(frame: Mapping, path, ctx: Optional[_capi.Context] = None) -> bytes
         return write_csv(frame, path, ",", ctx=ctx)
     if ext == "tsv":
         return write_csv(frame, path, "\t", ctx=ctx)
+    if ext in ("jsonl", "ndjson"):
+        return write_jsonl(frame, path, ctx=ctx)
+    if ext == "json":
+        return write_json(frame, path, ctx=ctx)
     shown = "None" if ext is None else f'Some("{ext}")'
     raise _capi.OxenError(f'Unknown file type write_df "{path}" {shown}', _capi.OXH_ERR_INVALID)
