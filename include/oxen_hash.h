@@ -1171,6 +1171,105 @@ int oxh_write_json_host(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const uint
                         const uint64_t* bit_offsets, const uint8_t* names, const uint64_t* name_offsets, uint32_t flags,
                         uint8_t* out, uint64_t capacity, uint64_t* out_bytes, uint64_t* stats4);
 
+/* ---------------------------------------------------------------- JSON Lines: record index and typed Arrow columns
+ * The reference has a JSON Lines arm in every reader: read_df_jsonl (core/df/tabular.rs:73-82), scan_df_jsonl
+ * (:150-160) and the "ndjson" | "jsonl" arm of _read_lazy_df_with_extension (:1077-1079). oxh_jsonl_* do it on the
+ * device: JSON Lines bytes in HBM to a record index (a handle), then to the same typed columns oxh_csv_columns_*
+ * produce, which every tabular entry above takes as they are and oxh_write_json_* writes back.
+ *
+ * The rules restate polars' LazyJsonLineReader under the reference's settings (infer_schema_length 10 000). They
+ * are NOT pinned by a run of polars; where this library chooses differently from polars, the rule says so.
+ *   Records. The buffer splits at EVERY '\n', whatever the string state (a raw newline inside a string is not
+ *     JSON). The end of the buffer ends the last record. JSON whitespace inside a record is 0x20, 0x09 and 0x0D, so
+ *     a '\r' before the '\n' is just whitespace. A line of zero bytes or of whitespace only is skipped and counted.
+ *     Every other line is a record and a row, well formed or not. A UTF-8 BOM is not skipped: it makes the first
+ *     record malformed (out of scope).
+ *   Lexing, from the start of each line (no state crosses a '\n'). A byte is ESCAPED iff the maximal run of '\'
+ *     directly before it, inside the same line, has odd length. A '"' that is not escaped toggles "inside a
+ *     string"; the line starts outside. Outside strings '{' and '[' add 1 to the depth, '}' and ']' subtract 1; the
+ *     line starts at depth 0. A stray quote or bracket damages its own line only.
+ *   Well-formed record. The first non-whitespace byte is '{' and the last is '}'; the depth is at least 1
+ *     everywhere between them and returns to 0 exactly at that last byte; the line does not end inside a string;
+ *     the structural bytes at depth 1 outside strings are "{ }" with only whitespace between, or "{ : , : , ... : }"
+ *     in strict alternation that starts and ends with ':'; every key slot (from '{' or ',' to ':') is exactly one
+ *     string token with whitespace around it; every value slot (from ':' to ',' or '}') is non-empty after trimming
+ *     whitespace. The interior of a nested value is checked for depth and string state only: bracket kinds are NOT
+ *     matched ("[}" passes). Every cell of a malformed record is null in every column; malformed records are counted.
+ *   Value kinds, per cell, on the trimmed slot. First byte '"': a string token -- its last byte is an unescaped '"'
+ *     and there is no other unescaped '"' inside; every '\' escape is one of \" \\ \/ \b \f \n \r \t \uXXXX (four
+ *     hex digits, either case); no raw byte below 0x20; a high surrogate \uD800-\uDBFF is directly followed by a low
+ *     one \uDC00-\uDFFF, and a lone surrogate of either kind is invalid; bytes at or above 0x80 are copied as they
+ *     are, with no UTF-8 check, as the CSV reader does. First byte '{' or '[': a nested value, which ends with '}' or
+ *     ']' respectively. true, false, null: exact, lower case. First byte '-' or a digit: the whole slot matches
+ *     -?(0|[1-9][0-9]*)(\.[0-9]+)?([eE][+-]?[0-9]+)? . Anything else, or a token that breaks its own rule, is
+ *     UNPARSABLE.
+ *   Names (the schema). The keys in order of first appearance over the well-formed records among the first
+ *     infer_rows rows. Keys are compared and reported UNESCAPED: "a\u0062" and "ab" are one column. A record is
+ *     CANONICAL iff its keys are exactly the first k names, in order, for some k <= ncols. In a record with a
+ *     repeated key the FIRST occurrence wins (this library's choice; simd-json's answer depends on the object's
+ *     size). A field whose key is not a name is ignored and counted; it can only come after the window. At most
+ *     65 535 names.
+ *   Types (the OXH_CSV_* codes above, this header's only column-type enum). A missing key, null, or any cell of a
+ *     malformed record is null in every type (stats4[0]).
+ *     OXH_CSV_INT64    a number token without fraction or exponent, in the int64 range (-0 is 0). Every other token
+ *                      is null and counted as unparsable (stats4[1]) -- 1.0 and 1e3 too: this library's choice.
+ *     OXH_CSV_FLOAT64  any number token: the CORRECTLY ROUNDED double, bit for bit what C's strtod gives. -0 is
+ *                      -0.0; a value out of range rounds to +-inf as strtod does; there are no inf / nan spellings.
+ *                      The device converts where one IEEE operation is exact and defers the rest to the host inside
+ *                      the same call, exactly as "CSV" above says; stats4[2] counts the deferred cells.
+ *     OXH_CSV_BOOL     true / false.
+ *     OXH_CSV_STRING / OXH_CSV_STRING64  a string token gives its unescaped bytes (each \uXXXX 1-3 bytes of UTF-8, a
+ *                      surrogate pair 4; \u0000 is the byte 0x00). A number, true or false gives its text as written
+ *                      (polars would re-print the number). A nested value gives its trimmed raw text, so a list of
+ *                      floats or a metadata object survives as JSON text (polars makes a List / Struct). Unparsable
+ *                      is null. The unescaped text is never longer than the raw text.
+ *   Inference (oxh_jsonl_infer, over the same window). As the CSV rule: the AND of class bits, a null or missing
+ *     cell having all three. Int64 if every cell is an integer in range, else Float64 if every cell is a number, else
+ *     Boolean if every cell is a bool, else String; a column with no cell but nulls is String.
+ *   Stated and not built: the `.json` array form (read_df_json: its records end by depth, not by line); lists and
+ *     structs as typed columns, dates, narrower numbers; buffers of 2^32 bytes and more; files larger than one
+ *     device buffer.
+ *
+ * The handle (a void*, as the CSV reader's) holds the index: `ends`, the u32 positions in ascending order of every
+ * '\n' and of the bytes outside strings that open depth 1, close it, or are a ':' or ',' at depth 1 (4 B each);
+ * `rec_end`, for every line the place of its end in `ends`; `row_rec`, the lines that are records; a bit per row for
+ * "well formed" and for "canonical"; and the names. A well-formed record of k fields owns 2 k + 1 entries of `ends`
+ * (2 for "{}"). A canonical row reads field c directly, any other row searches its keys from the front. Lifetime,
+ * threading and streams are the CSV handle's: oxh_jsonl_open_device reads the caller's d_bytes (any alignment),
+ * which must stay alive and unchanged until oxh_jsonl_close; oxh_jsonl_open_host owns a device copy; all entries
+ * block until complete; a handle is used by one thread at a time; stream orders the device forms' work, the host
+ * forms, oxh_jsonl_infer and oxh_jsonl_names use the ctx's stream. A line of whitespace only, and the whitespace
+ * around a record, is walked by one lane. A string cell of 512 bytes and more without an escape is read and copied
+ * by a whole wave; one with an escape is unescaped by one lane (exact, slower than the CSV reader's long cells).
+ *   stats8 = {records, rows (= records), ncols, malformed records, skipped blank lines, well-formed rows that are
+ *   not canonical, ignored fields, nested values at depth 1 (of well-formed records)}.
+ * oxh_jsonl_open_*: infer_rows is the window (UINT64_MAX: every row; the reference passes 10 000). OXH_ERR_INVALID,
+ * every message starting with "jsonl open:", before OXH_ERR_NODEVICE (there is no CPU path), in this order:
+ * infer_rows == 0; unknown flags (none are defined); nbytes >= 2^32; NULL bytes with nbytes > 0; NULL out; NULL
+ * stats8; then nbytes == 0 is OXH_OK with zeroed stats and a valid empty handle; then OXH_ERR_NODEVICE; then a NULL
+ * ctx; after the index, more than 65 535 names is OXH_ERR_INVALID with nothing written. A failed allocation is
+ * OXH_ERR_NOMEM with the outputs untouched.
+ * oxh_jsonl_close: NULL is OXH_OK.
+ * oxh_jsonl_names: the unescaped names, by the size-then-fill contract of oxh_csv_header.
+ * oxh_jsonl_infer: types[c] for the ncols columns. OXH_ERR_INVALID: a NULL handle; NULL types with ncols > 0. No
+ * rows: every column is OXH_CSV_STRING.
+ * oxh_jsonl_columns_*: the parameters, outputs, measure-only mode, checks (in the same order) and stats4 of
+ * oxh_csv_columns_*, word for word; stats4 = {nulls from null, a missing key or a malformed record, nulls from
+ * unparsable cells, deferred cells, value bytes}. Messages start with "jsonl columns:". */
+int oxh_jsonl_open_device(oxh_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, uint64_t infer_rows, uint32_t flags, void** out,
+                          uint64_t* stats8, void* stream);
+int oxh_jsonl_open_host(oxh_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, uint64_t infer_rows, uint32_t flags, void** out,
+                        uint64_t* stats8);
+int oxh_jsonl_close(void* jsonl);
+int oxh_jsonl_names(void* jsonl, uint8_t* names, uint64_t capacity, uint64_t* name_offsets, uint64_t* names_bytes);
+int oxh_jsonl_infer(void* jsonl, uint32_t* types);
+int oxh_jsonl_columns_device(void* jsonl, uint32_t nsel, const uint32_t* col_idx, const uint32_t* types, const uint64_t* value_capacity,
+                             void* const* d_values, void* const* d_offsets, uint8_t* const* d_validity, uint64_t* value_bytes,
+                             uint64_t* stats4, void* stream);
+int oxh_jsonl_columns_host(void* jsonl, uint32_t nsel, const uint32_t* col_idx, const uint32_t* types, const uint64_t* value_capacity,
+                           void* const* values, void* const* offsets, uint8_t* const* validity, uint64_t* value_bytes,
+                           uint64_t* stats4);
+
 /* ---------------------------------------------------------------- K2: merkle parent nodes */
 /* get_combined_hash (hasher.rs:67-80) x n on the device:
  * XXH3-128(content.to_le_bytes() || metadata.to_le_bytes()), inputs as (lo, hi) pairs. */

@@ -21,7 +21,7 @@ Modules:
                page (embedding_mean, cosine_similarity, embedding_take, nearest_neighbors, sort_by_similarity),
                and the CSV file itself: read on the device (read_csv, read_csv_device) and written there (write_csv,
                write_csv_device, write_df), and the same columns as JSON Lines or one JSON array (write_jsonl, write_json and their
-               _device forms)
+               _device forms), and JSON Lines read on the device (read_jsonl, read_jsonl_device, read_df)
   procpool  -- file hashing sharded over reader processes (the open/close floor is per process)
   shard     -- multi-GPU sharding and the RCCL digest gather
   device    -- device-resident (HBM) batch entry points over torch buffers
@@ -48,7 +48,8 @@ _FROM_TABULAR = ("KeyedDiff", "STATUS_NAMES", "keyed_diff_digests", "keyed_diff_
                  "slice_rows", "slice_rows_device", "head", "head_device", "tail", "tail_device", "page", "page_device", "vstack",
                  "vstack_device", "CsvStats", "CsvColumnStats", "CsvFile", "CSV_TYPE_NAMES", "read_csv", "read_csv_device", "csv_shape",
                  "csv_schema", "CsvWriteStats", "write_csv", "write_csv_device", "write_df", "JsonWriteStats", "write_jsonl",
-                 "write_jsonl_device", "write_json", "write_json_device")
+                 "write_jsonl_device", "write_json", "write_json_device", "JsonlStats", "JsonlFile", "read_jsonl", "read_jsonl_device",
+                 "jsonl_shape", "jsonl_schema", "read_df")
 
 
 def __getattr__(name):

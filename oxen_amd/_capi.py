@@ -218,6 +218,15 @@ SIGNATURES = {
                                      _vp]),
     "oxh_write_json_host": (_int, [_vp, _u64, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_vp),
                                    ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u64p, _vp, _u64p, _u32, _vp, _u64, _u64p, _u64p]),
+    "oxh_jsonl_open_device": (_int, [_vp, _vp, _u64, _u64, _u32, ctypes.POINTER(_vp), _u64p, _vp]),
+    "oxh_jsonl_open_host": (_int, [_vp, _vp, _u64, _u64, _u32, ctypes.POINTER(_vp), _u64p]),
+    "oxh_jsonl_close": (_int, [_vp]),
+    "oxh_jsonl_names": (_int, [_vp, _vp, _u64, _u64p, _u64p]),
+    "oxh_jsonl_infer": (_int, [_vp, ctypes.POINTER(_u32)]),
+    "oxh_jsonl_columns_device": (_int, [_vp, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32), _u64p, ctypes.POINTER(_vp),
+                                        ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u64p, _u64p, _vp]),
+    "oxh_jsonl_columns_host": (_int, [_vp, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32), _u64p, ctypes.POINTER(_vp),
+                                      ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u64p, _u64p]),
     "oxh_comm_check": (_int, [_int]),
     "oxh_ctx_counters": (_int, [_vp, _u64p, _int]),
     "oxh_comm_unique_id": (_int, [ctypes.c_char_p]),

@@ -18,13 +18,14 @@ SOURCES = [os.path.join(CSRC, f) for f in (
     "xxh3_kernels.hip", "capi_dispatch.hip", "capi_context.hip", "staging.hip", "large_items.hip", "xxh3_stream.hip",
     "engine.hip", "modified.hip", "publish.hip", "fastcdc.hip", "fastcdc_scan.hip", "fastcdc_walk.hip", "dedup_index.hip",
     "row_hash.hip", "keyed_diff.hip", "take_columns.hip", "concat_columns.hip", "sort_rows.hip", "group_rows.hip", "filter_rows.hip",
-    "embedding.hip", "csv_read.hip", "csv_write.hip", "json_write.hip", "reader_pool.cpp", "comm.cpp", "fastcdc_host.cpp")]
+    "embedding.hip", "csv_read.hip", "csv_write.hip", "json_write.hip", "jsonl_read.hip", "reader_pool.cpp", "comm.cpp", "fastcdc_host.cpp")]
 DEPS = SOURCES + [os.path.join(CSRC, h) for h in ("capi_internal.hpp", "xxh3_device.hpp", "fastcdc_gear.h", "fastcdc_plan.hpp",
                                                  "fastcdc_device.hpp", "pool.hpp", "scratch.hpp", "reader_pool.hpp",
                                                  "env.hpp", "keyed_diff_host.hpp", "columns.hpp",
                                                  "take_columns_host.hpp", "concat_columns_host.hpp", "sort_rows_host.hpp", "sort_keys.hpp",
                                                  "group_rows_host.hpp", "filter_rows_host.hpp", "filter_terms.hpp",
-                                                 "embedding_host.hpp", "csv_host.hpp", "csv_number.hpp", "csv_text.hpp", "json_text.hpp")] + [os.path.join(ROOT, "include", "oxen_hash.h")]
+                                                 "embedding_host.hpp", "csv_host.hpp", "csv_number.hpp", "csv_text.hpp", "json_text.hpp", "jsonl_host.hpp",
+                                                 "jsonl_text.hpp")] + [os.path.join(ROOT, "include", "oxen_hash.h")]
 HELPER_SRC = os.path.join(CSRC, "hash_helper.cpp")
 HELPER = os.path.join(HERE, "oxh_hash_helper")  # the reader-pool helper process (oxh_pool_*)
 ARCH = "gfx950"
@@ -81,6 +82,8 @@ CSV_FLOAT_CASES_SRC = os.path.join(ROOT, "tests", "native", "csv_float_cases.cpp
 CSV_FLOAT_CASES = os.path.join(ROOT, "tests", "native", "csv_float_cases")  # tests only: both CSV float conversions over a test's cells
 JSON_WRITE_TEST_SRC = os.path.join(ROOT, "tests", "native", "json_write_host_test.cpp")
 JSON_WRITE_TEST = os.path.join(ROOT, "tests", "native", "json_write_host_test")  # tests only: the JSON writer's text functions
+JSONL_TEST_SRC = os.path.join(ROOT, "tests", "native", "jsonl_host_test.cpp")
+JSONL_TEST = os.path.join(ROOT, "tests", "native", "jsonl_host_test")  # tests only: the JSON Lines reader's grammar, carries and host pieces
 FAKE_RCCL_SRC = os.path.join(ROOT, "tests", "native", "fake_rccl.cpp")
 # tests only: an "RCCL" for N processes on one GPU (OXH_RCCL_LIB), with and without ncclGather
 FAKE_RCCL = os.path.join(ROOT, "tests", "native", "libfake_rccl.so")
@@ -103,8 +106,9 @@ def build_host(force: bool = False, verbose: bool = False) -> str:
     (tests/native/filter_rows_host_test.cpp), of the embedding query's host pieces and order key
     (tests/native/embedding_host_test.cpp), of the CSV reader's parsers and host pieces
     (tests/native/csv_host_test.cpp), of the CSV writer's text functions (tests/native/csv_write_host_test.cpp), of
-    both CSV float conversions over cells a test sends in (tests/native/csv_float_cases.cpp) and of the JSON writer's
-    text functions (tests/native/json_write_host_test.cpp)."""
+    both CSV float conversions over cells a test sends in (tests/native/csv_float_cases.cpp), of the JSON writer's
+    text functions (tests/native/json_write_host_test.cpp) and of the JSON Lines reader's grammar, carries and host
+    pieces (tests/native/jsonl_host_test.cpp)."""
     hdr = os.path.join(ROOT, "include", "oxen_hash.h")
     steps = [
         (HELPER, [HELPER_SRC, os.path.join(CSRC, "reader_pool.hpp"), hdr, LIB],
@@ -152,6 +156,9 @@ def build_host(force: bool = False, verbose: bool = False) -> str:
          ["g++", "-std=c++17", "-O2", "-Wall", "-o", CSV_FLOAT_CASES + ".tmp", CSV_FLOAT_CASES_SRC]),
         (JSON_WRITE_TEST, [JSON_WRITE_TEST_SRC, os.path.join(CSRC, "json_text.hpp"), os.path.join(CSRC, "csv_text.hpp")],
          ["g++", "-std=c++17", "-O2", "-Wall", "-o", JSON_WRITE_TEST + ".tmp", JSON_WRITE_TEST_SRC]),
+        (JSONL_TEST, [JSONL_TEST_SRC, os.path.join(CSRC, "jsonl_host.hpp"), os.path.join(CSRC, "jsonl_text.hpp"),
+                      os.path.join(CSRC, "csv_host.hpp"), os.path.join(CSRC, "csv_number.hpp"), hdr],
+         ["g++", "-std=c++17", "-O2", "-Wall", "-o", JSONL_TEST + ".tmp", JSONL_TEST_SRC]),
     ]
     for target, extra in ((FAKE_RCCL, []), (FAKE_RCCL_NOGATHER, ["-DFAKE_NO_GATHER"])):
         steps.append((target, [FAKE_RCCL_SRC],

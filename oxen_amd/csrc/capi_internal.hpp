@@ -51,6 +51,11 @@
 //                      non-finite floats as null, and every string quoted with its bytes 1, 2 or 6 wide
 //                      (json_text.hpp); a long cell that widens is escaped by the whole wave, a lane's place a wave
 //                      prefix sum of the widths, staged in LDS and stored in aligned 16-byte blocks
+//   jsonl_read.hip     JSON Lines bytes to a record index and to the same typed columns (oxh_jsonl_*): the backslash
+//                      run, the string parity and the depth -- all three restart at every newline -- as associative
+//                      carries folded over lanes, waves, tiles and, by one workgroup, the tiles in order
+//                      (jsonl_text.hpp, shared with the host); then the CSV reader's count, scan, emit, row map and
+//                      one lane per row, a canonical row reading field c and any other searching its keys
 // There is no CPU hashing path: every digest this library returns was computed on the GPU.
 #pragma once
 

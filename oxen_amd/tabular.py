@@ -2408,3 +2408,193 @@ def write_df(frame: Mapping, path, ctx: Optional[_capi.Context] = None) -> bytes
         return write_json(frame, path, ctx=ctx)
     shown = "None" if ext is None else f'Some("{ext}")'
     raise _capi.OxenError(f'Unknown file type write_df "{path}" {shown}', _capi.OXH_ERR_INVALID)
+
+
+# ---------------------------------------------------------------- JSON Lines: record index and typed columns (oxh_jsonl_*)
+_READ_ERROR = "Could not read tabular data from path"   # the reference's OxenError::basic_str of a failed read
+
+
+class JsonlStats(NamedTuple):
+    """stats8 of oxh_jsonl_open_*."""
+    records: int
+    rows: int
+    ncols: int
+    malformed: int
+    skipped_blank: int
+    non_canonical: int
+    ignored_fields: int
+    nested_values: int
+
+
+class JsonlFile:
+    """The record index of one JSON Lines buffer (an oxh_jsonl_open_* handle), the twin of `CsvFile`: `stats`,
+    `names`, `infer`, `measure`, `columns`. data: bytes / a uint8 numpy array (the host form, which owns a device
+    copy), or with device=True a uint8 torch tensor on the device, which the object keeps alive. The rules are
+    include/oxen_hash.h's "JSON Lines": a record per line, the names in order of first appearance over the first
+    infer_rows rows, a malformed record or an unparsable cell null."""
+
+    def __init__(self, data, infer_rows: int = 10000, ctx: Optional[_capi.Context] = None, device: bool = False, stream=None):
+        self.device = device
+        self.ctx = ctx
+        self.stream = stream
+        self.handle = None
+        window = (1 << 64) - 1 if infer_rows is None else int(infer_rows)
+        out = ctypes.c_void_p()
+        stats = np.zeros(8, dtype=np.uint64)
+        if device:
+            from .device import _require_cuda, _stream
+
+            _require_cuda(data)
+            if data.element_size() != 1 or not data.is_contiguous():
+                raise _capi.OxenError("the JSON Lines bytes are a contiguous uint8 tensor", _capi.OXH_ERR_INVALID)
+            self.data = data
+            _capi.check(_capi.lib().oxh_jsonl_open_device(_handle(ctx), data.data_ptr() if data.numel() else None, data.numel(), window, 0,
+                                                          ctypes.byref(out), stats.ctypes.data_as(_capi._u64p), _stream(stream)),
+                        "oxh_jsonl_open_device")
+        else:
+            self.data = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+            _capi.check(_capi.lib().oxh_jsonl_open_host(_handle(ctx), self.data.ctypes.data if self.data.size else None, self.data.size, window,
+                                                        0, ctypes.byref(out), stats.ctypes.data_as(_capi._u64p)),
+                        "oxh_jsonl_open_host")
+        self.handle = out
+        self.stats = JsonlStats(*(int(x) for x in stats))
+        self._names = None
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            _capi.lib().oxh_jsonl_close(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def raw_names(self) -> list:
+        """The unescaped names as bytes."""
+        if self._names is None:
+            n = self.stats.ncols
+            offsets, size = np.zeros(n + 1, dtype=np.uint64), ctypes.c_uint64(0)
+            L = _capi.lib()
+            _capi.check(L.oxh_jsonl_names(self.handle, None, 0, offsets.ctypes.data_as(_capi._u64p), ctypes.byref(size)), "oxh_jsonl_names")
+            buf = np.zeros(max(size.value, 1), dtype=np.uint8)
+            _capi.check(L.oxh_jsonl_names(self.handle, buf.ctypes.data, size.value, offsets.ctypes.data_as(_capi._u64p), ctypes.byref(size)),
+                        "oxh_jsonl_names")
+            raw = buf.tobytes()
+            self._names = [raw[int(offsets[c]):int(offsets[c + 1])] for c in range(n)]
+        return self._names
+
+    @property
+    def names(self) -> list:
+        """The column names (invalid UTF-8 replaced; the names of one file are distinct as bytes)."""
+        return [raw.decode("utf-8", errors="replace") for raw in self.raw_names]
+
+    def infer(self) -> list:
+        """oxh_jsonl_infer: one OXH_CSV_* per column from the window given at open."""
+        types = (ctypes.c_uint32 * max(self.stats.ncols, 1))()
+        _capi.check(_capi.lib().oxh_jsonl_infer(self.handle, types), "oxh_jsonl_infer")
+        return [int(types[c]) for c in range(self.stats.ncols)]
+
+    _selection = CsvFile._selection
+
+    def _call(self, nsel, col_idx, type_words, capacity, values, offsets, validity):
+        value_bytes, stats = np.zeros(max(nsel, 1), dtype=np.uint64), np.zeros(4 * max(nsel, 1), dtype=np.uint64)
+        L = _capi.lib()
+        args = (self.handle, nsel, col_idx, type_words, None if capacity is None else capacity.ctypes.data_as(_capi._u64p), values, offsets,
+                validity, value_bytes.ctypes.data_as(_capi._u64p), stats.ctypes.data_as(_capi._u64p))
+        if self.device:
+            from .device import _stream
+
+            _capi.check(L.oxh_jsonl_columns_device(*args, _stream(self.stream)), "oxh_jsonl_columns_device")
+        else:
+            _capi.check(L.oxh_jsonl_columns_host(*args), "oxh_jsonl_columns_host")
+        return ([int(x) for x in value_bytes[:nsel]], [CsvColumnStats(*(int(x) for x in stats[4 * k:4 * k + 4])) for k in range(nsel)])
+
+    measure = CsvFile.measure
+    columns = CsvFile.columns
+
+
+def _jsonl_frame(f: JsonlFile, schema, columns, ignore_errors: bool) -> dict:
+    names = f.names
+    if columns is None:
+        picked = list(range(len(names)))
+    else:
+        picked = []
+        for c in columns:
+            if isinstance(c, str) and c not in names:
+                raise _capi.OxenError(f"no column {c!r} among the JSON Lines names {names}", _capi.OXH_ERR_INVALID)
+            picked.append(names.index(c) if isinstance(c, str) else int(c))
+    inferred = None
+    types = []
+    for c in picked:
+        given = None if schema is None else (schema.get(names[c]) if isinstance(schema, Mapping) else schema[c])
+        if given is None:
+            inferred = inferred if inferred is not None else f.infer()
+            given = inferred[c]
+        types.append(_csv_type(given))
+    cols, stats = f.columns(picked, types, with_stats=True)
+    if not ignore_errors and (f.stats.malformed or any(s.null_unparsable for s in stats)):
+        raise _capi.OxenError(_READ_ERROR, _capi.OXH_ERR_INVALID)
+    return dict(zip([names[c] for c in picked], cols))
+
+
+def read_jsonl(path_or_bytes, schema=None, columns=None, infer_rows: int = 10000, ignore_errors: bool = False,
+               ctx: Optional[_capi.Context] = None) -> dict:
+    """`read_df_jsonl` (core/df/tabular.rs:73-82) on the device: a JSON Lines file (a path) or its bytes to the
+    ordered {name: Column} in host memory that every function of this module takes. schema and columns as
+    `read_csv`'s; columns without a type are inferred from the first infer_rows rows, which are also the rows whose
+    keys name the columns. A malformed record, or an unparsable cell in a selected column, raises the reference's
+    "Could not read tabular data from path"; with ignore_errors=True those cells are null."""
+    data, _ = _csv_bytes(path_or_bytes)
+    with JsonlFile(data, infer_rows, ctx=ctx) as f:
+        return _jsonl_frame(f, schema, columns, ignore_errors)
+
+
+def read_jsonl_device(d_bytes, schema=None, columns=None, infer_rows: int = 10000, ignore_errors: bool = False,
+                      ctx: Optional[_capi.Context] = None, stream=None) -> dict:
+    """`read_jsonl` over the file's bytes already on the device (a uint8 torch tensor): device `Column`s that every
+    `_device` function of this module accepts unchanged. Blocks."""
+    with JsonlFile(d_bytes, infer_rows, ctx=ctx, device=True, stream=stream) as f:
+        return _jsonl_frame(f, schema, columns, ignore_errors)
+
+
+def jsonl_shape(path_or_bytes, infer_rows: int = 10000, ctx: Optional[_capi.Context] = None) -> tuple:
+    """(width, height) of the tabular metadata: the names and the records, by the index alone."""
+    data, _ = _csv_bytes(path_or_bytes)
+    with JsonlFile(data, infer_rows, ctx=ctx) as f:
+        return f.stats.ncols, f.stats.rows
+
+
+def jsonl_schema(path_or_bytes, infer_rows: int = 10000, ctx: Optional[_capi.Context] = None) -> list:
+    """[(name, dtype name)] of the tabular metadata: the names and the inferred types."""
+    data, _ = _csv_bytes(path_or_bytes)
+    with JsonlFile(data, infer_rows, ctx=ctx) as f:
+        return list(zip(f.names, [CSV_TYPE_NAMES[t] for t in f.infer()]))
+
+
+def read_df(path, ctx: Optional[_capi.Context] = None) -> dict:
+    """`read_df` (core/df/tabular.rs:1032-1048 and the arms of :1077-1103) for the text formats this module reads, the
+    twin of `write_df`: `.csv`, `.data` and `.tsv` through `read_csv`, `.jsonl` and `.ndjson` through `read_jsonl`.
+    `.json`, `.parquet` and `.arrow` are forms this module does not read. Any other extension raises the text of the
+    `_` arm (:1097-1101); a path without an extension that of the earlier branch (:1044-1045), which prints the
+    Option as `None`."""
+    import os
+
+    path = str(path)
+    ext = os.path.splitext(path)[1][1:]
+    if ext in ("csv", "data", "tsv"):
+        return read_csv(path, ctx=ctx)
+    if ext in ("jsonl", "ndjson"):
+        return read_jsonl(path, ctx=ctx)
+    if ext in ("json", "parquet", "arrow"):
+        raise _capi.OxenError(f'reading the "{ext}" form is not built: {path}', _capi.OXH_ERR_INVALID)
+    # Rust's {path:?} quotes the path; a path without an extension prints its Option as None
+    raise _capi.OxenError(f'Could not load data frame with path: "{path}" and extension: {ext or "None"}', _capi.OXH_ERR_INVALID)
