@@ -1171,6 +1171,67 @@ int oxh_write_json_host(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const uint
                         const uint64_t* bit_offsets, const uint8_t* names, const uint64_t* name_offsets, uint32_t flags,
                         uint8_t* out, uint64_t capacity, uint64_t* out_bytes, uint64_t* stats4);
 
+/* ---------------------------------------------------------------- Parquet: typed Arrow columns to the file's bytes
+ * `write_df`'s parquet arm (core/df/tabular.rs:1508-1517: polars' ParquetWriter) is where `oxen df --output x.parquet`,
+ * the diff's output, the tabular merge and restore results and the workspace commit end when the target is a
+ * `.parquet` file. oxh_write_parquet_* write such a file on the device, over the same columns as oxh_write_csv_*.
+ * A writer chooses its encodings; this one's are fixed, so that a plain reader can check every byte:
+ *   Envelope. "PAR1", the row groups, the footer, the footer's 4-byte little-endian length, "PAR1". The footer is a
+ *     FileMetaData in Thrift compact protocol: version 1; the schema, a REQUIRED root group `schema` and one
+ *     OPTIONAL column per input column (OXH_CSV_INT64 -> INT64, OXH_CSV_FLOAT64 -> DOUBLE, OXH_CSV_BOOL -> BOOLEAN,
+ *     OXH_CSV_STRING / OXH_CSV_STRING64 -> BYTE_ARRAY with converted type UTF8 and logical type STRING); num_rows; the
+ *     row groups; a created_by string that names this project; column_orders, TYPE_ORDER for every column. Every
+ *     column chunk: codec UNCOMPRESSED, encodings [PLAIN, RLE], num_values, total_uncompressed_size ==
+ *     total_compressed_size == the bytes of its pages with their headers, data_page_offset == where its first page
+ *     header starts, file_offset 0. A row group: total_byte_size == total_compressed_size == the sum over its
+ *     chunks, num_rows, file_offset == its first page, ordinal.
+ *   Row groups and pages. Rows are cut at multiples of 1 024 (a tile). A row group holds rows_per_group rows (0: the
+ *     default, 1 048 576; else a positive multiple of 1 024), its column chunks one after the other in column order,
+ *     each a run of DataPage V1 pages. A page is a whole number of tiles: tiles are added until its levels plus
+ *     values reach page_bytes (0: the default, 1 MiB); a page always takes at least one tile, so one huge cell makes
+ *     one big page. A page whose levels plus values exceed INT32_MAX is refused before anything is written.
+ *   Definition levels (max level 1): a 4-byte length, then the RLE / bit-packed hybrid at width 1. A page without a
+ *     null is one RLE run, varint(n << 1) then the byte 1. A page with a null is one bit-packed run,
+ *     varint((ceil(n / 8) << 1) | 1), then the validity bits LSB first -- the Arrow bitmap's bytes at bit offset 0 --
+ *     with the pad bits of the last byte 0. A NULL validity pointer means no nulls.
+ *   Values: PLAIN, the cells that are not null in row order. INT64 and DOUBLE: the 8 bytes. BOOLEAN: one bit a
+ *     cell, LSB first, pad bits 0. BYTE_ARRAY: a little-endian u32 length, then the bytes; invalid UTF-8 is copied as
+ *     it is; a cell of 2^32 bytes or more is refused.
+ *   Statistics, per column chunk: null_count for every column; min_value and max_value for INT64 (signed) and for
+ *     DOUBLE by the format's rule (NaNs left out; neither written when every cell is NaN or null; a zero min is -0.0,
+ *     a zero max is +0.0). Booleans and strings get null_count only. There are no page statistics or indexes.
+ *   Stated and not built: reading Parquet; compression; dictionary encoding; nested and narrower types; the `arrow`
+ *     arm of `write_df`.
+ *
+ * Inputs: as oxh_write_json_* (names and name_offsets are always read; host memory in both forms), then
+ * rows_per_group, page_bytes and flags (none defined). Outputs: the file's bytes in out (capacity bytes; device
+ * memory in _device, host memory in _host); out_bytes = the file's size; stats4 = {bytes, row groups, pages, null
+ * cells}. With out NULL the call only measures. With a capacity below the need nothing is written to out, out_bytes
+ * and stats4 are set and the call returns OXH_ERR_INVALID. nrows == 0 gives a valid file with the schema and no row
+ * group. Both forms block until complete; stream orders the device form's work, the host form stages its columns
+ * through one device block and uses the ctx's stream. Every byte of the file is written by the call: the result
+ * does not depend on what out held. A pair of offsets that is negative or decreases is never read through.
+ * OXH_ERR_INVALID, every message starting with "parquet write:", before OXH_ERR_NODEVICE (there is no CPU path), in
+ * this order: NULL types, kinds, values, offsets, validity or bit_offsets; ncols == 0; non-zero flags; a
+ * rows_per_group that is no multiple of 1 024; an unknown type; a column whose kind does not fit its type; NULL
+ * name_offsets, name_offsets that decrease, NULL names with name bytes; NULL out_bytes or stats4; more than 2^40 rows;
+ * with rows, per column: a byte column without offsets, another column without values, and in the host form offsets
+ * that are negative or decrease, bytes without values; then OXH_ERR_NODEVICE; then a NULL ctx; then, after the
+ * measure and before anything is written: a pair of offsets that is negative or decreases, a byte column with bytes
+ * and no values, a string cell of 2^32 bytes or more, a page above INT32_MAX bytes, more than 32 767 row groups (a RowGroup's
+ * ordinal is an int16); then a capacity below the need.
+ * A failed allocation is OXH_ERR_NOMEM with the outputs untouched. */
+int oxh_write_parquet_device(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const uint32_t* types, const uint32_t* kinds,
+                             const void* const* d_values, const void* const* d_offsets, const uint8_t* const* d_validity,
+                             const uint64_t* bit_offsets, const uint8_t* names, const uint64_t* name_offsets,
+                             uint64_t rows_per_group, uint64_t page_bytes, uint32_t flags, uint8_t* d_out, uint64_t capacity,
+                             uint64_t* out_bytes, uint64_t* stats4, void* stream);
+int oxh_write_parquet_host(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const uint32_t* types, const uint32_t* kinds,
+                           const void* const* values, const void* const* offsets, const uint8_t* const* validity,
+                           const uint64_t* bit_offsets, const uint8_t* names, const uint64_t* name_offsets,
+                           uint64_t rows_per_group, uint64_t page_bytes, uint32_t flags, uint8_t* out, uint64_t capacity,
+                           uint64_t* out_bytes, uint64_t* stats4);
+
 /* ---------------------------------------------------------------- JSON Lines: record index and typed Arrow columns
  * The reference has a JSON Lines arm in every reader: read_df_jsonl (core/df/tabular.rs:73-82), scan_df_jsonl
  * (:150-160) and the "ndjson" | "jsonl" arm of _read_lazy_df_with_extension (:1077-1079). oxh_jsonl_* do it on the

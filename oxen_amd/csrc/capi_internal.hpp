@@ -56,6 +56,11 @@
 //                      carries folded over lanes, waves, tiles and, by one workgroup, the tiles in order
 //                      (jsonl_text.hpp, shared with the host); then the CSV reader's count, scan, emit, row map and
 //                      one lane per row, a canonical row reading field c and any other searching its keys
+//   parquet_write.hip  the same columns to the bytes of a Parquet file (oxh_write_parquet_*): per 1 024-row tile and
+//                      column the valid rows, value bytes and min / max by wave reductions; the host plans pages, row
+//                      groups, Thrift headers and the footer from that table (parquet_host.hpp); then a wave per tile
+//                      and column compacts the valid cells to their ranks through LDS -- mbcnt over validity ballots
+//                      -- and stores them in aligned 16-byte blocks behind the page's header and levels
 // There is no CPU hashing path: every digest this library returns was computed on the GPU.
 #pragma once
 

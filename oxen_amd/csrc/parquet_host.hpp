@@ -1,0 +1,368 @@
+// oxen_amd/csrc/parquet_host.hpp -- the host-only pieces of oxh_write_parquet_* (parquet_write.hip): the argument
+// checks that need no device, in the header's order; the Thrift compact encoder; the planner that turns the measure
+// kernel's tile table into pages, row groups, every PageHeader's bytes, every page's place in the file and the
+// footer; and the folding of the tiles' min / max partials into a column chunk's statistics. The format is stated in
+// include/oxen_hash.h "Parquet". Plain C++ with no HIP in it, so that a stand-alone program can call it
+// (tests/native/parquet_host_test.cpp, which is also what a sanitizer build runs).
+#pragma once
+
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "columns.hpp"
+
+namespace oxh::parquet {
+
+constexpr uint64_t kTileRows = 1024;                 // rows are cut at its multiples
+constexpr uint64_t kDefaultGroupRows = 1048576;
+constexpr uint64_t kDefaultPageBytes = 1048576;
+constexpr uint64_t kMaxRows = 1ull << 40;
+constexpr uint64_t kMaxCell = 1ull << 32;            // a BYTE_ARRAY's length is a u32
+constexpr uint64_t kMaxPage = 0x7FFFFFFFull;         // PageHeader's sizes are i32
+constexpr const char* kCreatedBy = "oxen_amd parquet writer (gfx950)";
+
+// What the measure kernel leaves per (tile, column), entry tile * ncols + column.
+struct Tile {
+    uint64_t value_bytes;  // 8 * valid; strings: the sum of 4 + length over the valid rows; booleans: valid
+    uint64_t min, max;     // INT64: signed; DOUBLE: the bits, over the cells that are not NaN; BOOLEAN: min = bool_tail
+                           // of the tile, the values of its last 7 valid rows
+    uint32_t valid;        // the rows that are not null
+    uint32_t has_minmax;   // min and max hold a value
+};
+
+// What the emit kernel reads per page and per (tile, column).
+struct Page {
+    uint64_t file_at;       // where the page's header starts in the file
+    uint64_t head_src;      // its head in the plan's byte blob: PageHeader, the levels' length and run header
+    uint64_t values_bytes;
+    uint64_t row0;          // the page's first row
+    uint32_t rows, nvalid;
+    uint32_t head_len;
+    uint32_t level_bytes;   // the bit-packed validity behind the head; 0 for a page without a null
+    uint32_t tile0;         // its first tile
+    uint32_t col;
+};
+
+struct Place {
+    uint32_t page;
+    uint32_t rank_base;     // the valid rows of the page in front of the tile
+    uint64_t byte_base;     // strings: their value bytes; booleans: the rank_base & 7 value bits of the page's earlier
+                            // rows that share the tile's first byte, in the byte's order
+};
+
+#if defined(__HIPCC__)
+#define OXH_PQ_BOTH __host__ __device__
+#else
+#define OXH_PQ_BOTH
+#endif
+// The values of the last 7 valid rows so far, the last one in bit 0, after 64 more rows (mask: not null, vals: the
+// value bits of those). The measure kernel folds it over a tile's steps, the planner over a page's tiles.
+OXH_PQ_BOTH inline uint32_t bool_tail(uint32_t tail, uint64_t mask, uint64_t vals) {
+    uint32_t t = 0, cnt = 0;
+    while (mask && cnt < 7) {
+        const int j = 63 - __builtin_clzll(mask);
+        mask &= ~(1ull << j);
+        t |= (uint32_t)((vals >> j) & 1) << cnt;
+        ++cnt;
+    }
+    return (t | (tail << cnt)) & 0x7F;
+}
+
+// ---------------------------------------------------------------- Thrift compact protocol
+enum : uint8_t { kTBoolTrue = 1, kTBoolFalse = 2, kTI16 = 4, kTI32 = 5, kTI64 = 6, kTBinary = 8, kTList = 9, kTStruct = 12 };
+
+struct Thrift {
+    std::vector<uint8_t> out;
+    std::vector<int16_t> last{0};  // the last field id of every open struct
+
+    void varint(uint64_t v) {
+        while (v >= 0x80) out.push_back((uint8_t)(v | 0x80)), v >>= 7;
+        out.push_back((uint8_t)v);
+    }
+    static uint64_t zigzag(int64_t v) { return ((uint64_t)v << 1) ^ (uint64_t)(v >> 63); }
+    void field(int16_t id, uint8_t type) {
+        const int delta = id - last.back();
+        if (delta > 0 && delta <= 15) {
+            out.push_back((uint8_t)((delta << 4) | type));
+        } else {
+            out.push_back(type);
+            varint(zigzag(id));
+        }
+        last.back() = id;
+    }
+    void i16(int16_t id, int16_t v) { field(id, kTI16), varint(zigzag(v)); }
+    void i32(int16_t id, int32_t v) { field(id, kTI32), varint(zigzag(v)); }
+    void i64(int16_t id, int64_t v) { field(id, kTI64), varint(zigzag(v)); }
+    void raw_binary(const void* p, uint64_t n) {
+        varint(n);
+        out.insert(out.end(), (const uint8_t*)p, (const uint8_t*)p + n);
+    }
+    void binary(int16_t id, const void* p, uint64_t n) { field(id, kTBinary), raw_binary(p, n); }
+    void list(int16_t id, uint8_t elem, uint64_t n) {
+        field(id, kTList);
+        if (n < 15) {
+            out.push_back((uint8_t)((n << 4) | elem));
+        } else {
+            out.push_back((uint8_t)(0xF0 | elem));
+            varint(n);
+        }
+    }
+    void begin() { last.push_back(0); }                       // a struct that is a list element
+    void begin(int16_t id) { field(id, kTStruct), begin(); }  // a struct that is a field
+    void end() { out.push_back(0), last.pop_back(); }
+};
+
+inline uint32_t varint_len(uint64_t v) {
+    uint32_t n = 1;
+    while (v >= 0x80) v >>= 7, ++n;
+    return n;
+}
+
+// ---------------------------------------------------------------- arguments
+struct Args {
+    uint64_t nrows;
+    uint32_t ncols;
+    const uint32_t* types;
+    const uint32_t* kinds;
+    const void* const* values;
+    const void* const* offsets;
+    const uint8_t* const* validity;
+    const uint64_t* bit_offsets;
+    const uint8_t* names;
+    const uint64_t* name_offsets;
+    uint64_t rows_per_group, page_bytes;
+    uint32_t flags;
+    uint8_t* out;
+    uint64_t capacity;
+    uint64_t* out_bytes;
+    uint64_t* stats4;
+};
+
+inline bool known_type(uint32_t t) { return t >= OXH_CSV_INT64 && t <= OXH_CSV_STRING64; }
+inline bool is_string(uint32_t t) { return t == OXH_CSV_STRING || t == OXH_CSV_STRING64; }
+inline uint32_t kind_of(uint32_t type) {
+    return type == OXH_CSV_BOOL ? OXH_COL_BOOL : type == OXH_CSV_STRING ? OXH_COL_BYTES32 : type == OXH_CSV_STRING64 ? OXH_COL_BYTES64 : OXH_COL_FIXED8;
+}
+inline uint64_t group_rows_of(uint64_t rows_per_group) { return rows_per_group ? rows_per_group : kDefaultGroupRows; }
+inline uint64_t page_bytes_of(uint64_t page_bytes) { return page_bytes ? page_bytes : kDefaultPageBytes; }
+
+// "" when the arguments are well formed, else what is wrong with them, in the header's order.
+inline std::string write_error(const Args& a, bool host) {
+    if (!a.types || !a.kinds || !a.values || !a.offsets || !a.validity || !a.bit_offsets)
+        return "types, kinds, values, offsets, validity or bit_offsets is NULL";
+    if (a.ncols == 0) return "ncols is 0";
+    if (a.flags) return "unknown flags";
+    if (a.rows_per_group % kTileRows) return "rows_per_group is not a multiple of 1024";
+    for (uint32_t c = 0; c < a.ncols; ++c)
+        if (!known_type(a.types[c])) return "column " + std::to_string(c) + " has unknown type " + std::to_string(a.types[c]);
+    for (uint32_t c = 0; c < a.ncols; ++c)
+        if (a.kinds[c] != kind_of(a.types[c]))
+            return "column " + std::to_string(c) + " of type " + std::to_string(a.types[c]) + " has kind " + std::to_string(a.kinds[c]) +
+                   ", not " + std::to_string(kind_of(a.types[c]));
+    if (!a.name_offsets) return "name_offsets is NULL";
+    for (uint32_t c = 0; c < a.ncols; ++c)
+        if (a.name_offsets[c + 1] < a.name_offsets[c]) return "name_offsets decrease at column " + std::to_string(c);
+    if (!a.names && a.name_offsets[a.ncols] > a.name_offsets[0]) return "names is NULL";
+    if (!a.out_bytes || !a.stats4) return "out_bytes or stats4 is NULL";
+    if (a.nrows > kMaxRows) return "more than 2^40 rows";
+    for (uint32_t c = 0; c < a.ncols && a.nrows; ++c) {
+        const std::string what = oxh::cols::column_error("column " + std::to_string(c), a.kinds[c], a.values[c], a.offsets[c], a.nrows, host);
+        if (!what.empty()) return what;
+    }
+    return "";
+}
+
+// ---------------------------------------------------------------- statistics
+// A column chunk's min / max from its tiles' partials. DOUBLE follows the format's rule: the NaNs were left out by
+// the kernel, no value at all gives no min / max, a min of zero is -0.0 and a max of zero is +0.0.
+struct MinMax {
+    bool has = false;
+    uint64_t min = 0, max = 0;
+    static double as_double(uint64_t bits) {
+        double d;
+        memcpy(&d, &bits, 8);
+        return d;
+    }
+    void fold(const Tile& t, uint32_t type) {
+        if (!t.has_minmax) return;
+        if (!has) {
+            has = true, min = t.min, max = t.max;
+        } else if (type == OXH_CSV_INT64) {
+            if ((int64_t)t.min < (int64_t)min) min = t.min;
+            if ((int64_t)t.max > (int64_t)max) max = t.max;
+        } else {
+            if (as_double(t.min) < as_double(min)) min = t.min;
+            if (as_double(t.max) > as_double(max)) max = t.max;
+        }
+    }
+    void finish(uint32_t type) {
+        if (!has || type != OXH_CSV_FLOAT64) return;
+        if (as_double(min) == 0.0) min = 0x8000000000000000ull;
+        if (as_double(max) == 0.0) max = 0;
+    }
+};
+
+// ---------------------------------------------------------------- the plan
+struct Plan {
+    std::vector<Page> pages;
+    std::vector<Place> places;     // ntiles * ncols
+    std::vector<uint8_t> blob;     // the pages' heads, one after the other
+    std::vector<uint8_t> footer;   // FileMetaData, its u32 length, "PAR1"
+    uint64_t out_bytes = 0, row_groups = 0, null_cells = 0;
+    std::string error;             // not empty: the file is refused
+};
+
+// Bytes of a page of `rows` rows: its levels (with their u32 length) and its values.
+inline uint64_t level_run_len(uint64_t rows, bool nulls) {
+    return nulls ? varint_len((((rows + 7) / 8) << 1) | 1) + (rows + 7) / 8 : varint_len(rows << 1) + 1;
+}
+inline uint64_t values_len(uint32_t type, uint64_t valid, uint64_t bytes) { return type == OXH_CSV_BOOL ? (valid + 7) / 8 : bytes; }
+
+inline void put_u32(std::vector<uint8_t>& out, uint32_t v) {
+    for (int k = 0; k < 4; ++k) out.push_back((uint8_t)(v >> (8 * k)));
+}
+
+struct ChunkMeta {
+    uint64_t first_page_at = 0, bytes = 0, rows = 0, nulls = 0;
+    MinMax mm;
+};
+
+inline int32_t parquet_type(uint32_t t) { return t == OXH_CSV_INT64 ? 2 : t == OXH_CSV_FLOAT64 ? 5 : t == OXH_CSV_BOOL ? 0 : 6; }
+
+// tiles: ceil(nrows / 1024) * ncols entries. The names are read as write_error() left them.
+inline Plan make_plan(uint64_t nrows, uint32_t ncols, const uint32_t* types, const uint8_t* names, const uint64_t* name_offsets,
+                      uint64_t rows_per_group, uint64_t page_bytes, const Tile* tiles) {
+    Plan p;
+    const uint64_t group_rows = group_rows_of(rows_per_group), budget = page_bytes_of(page_bytes);
+    const uint64_t ntiles = (nrows + kTileRows - 1) / kTileRows, group_tiles = group_rows / kTileRows;
+    p.places.resize(ntiles * ncols);
+    uint64_t at = 4;  // behind "PAR1"
+    struct Group {
+        uint64_t rows, at, bytes;
+        std::vector<ChunkMeta> chunks;
+    };
+    std::vector<Group> groups;
+    for (uint64_t t0 = 0; t0 < ntiles; t0 += group_tiles) {
+        const uint64_t t1 = std::min(ntiles, t0 + group_tiles);
+        Group g{std::min(nrows, t1 * kTileRows) - t0 * kTileRows, at, 0, std::vector<ChunkMeta>(ncols)};
+        for (uint32_t c = 0; c < ncols; ++c) {
+            ChunkMeta& m = g.chunks[c];
+            m.first_page_at = at;
+            for (uint64_t t = t0; t < t1;) {
+                // one page: whole tiles until the levels and the values reach the budget
+                Page pg{};
+                pg.file_at = at, pg.row0 = t * kTileRows, pg.tile0 = (uint32_t)t, pg.col = c;
+                uint64_t rows = 0, valid = 0, bytes = 0;
+                uint32_t carry = 0;  // booleans: bool_tail of the page so far
+                do {
+                    const Tile& tl = tiles[t * ncols + c];
+                    const uint64_t tile_rows = std::min(nrows - t * kTileRows, kTileRows);
+                    if (tl.valid > tile_rows) return p.error = "a tile counts more valid rows than it has", p;
+                    uint64_t lead = 0;  // the carry's newest valid & 7 bits, the oldest of them in bit 0
+                    for (uint32_t k = 0; k < (valid & 7); ++k) lead |= (uint64_t)((carry >> ((valid & 7) - 1 - k)) & 1) << k;
+                    p.places[t * ncols + c] = Place{(uint32_t)p.pages.size(), (uint32_t)valid, types[c] == OXH_CSV_BOOL ? lead : bytes};
+                    if (types[c] == OXH_CSV_BOOL) {
+                        const uint32_t cnt = std::min<uint32_t>(tl.valid, 7);
+                        carry = (((uint32_t)tl.min & ((1u << cnt) - 1)) | (carry << cnt)) & 0x7F;
+                    }
+                    rows += tile_rows, valid += tl.valid, bytes += tl.value_bytes;
+                    m.mm.fold(tl, types[c]);
+                    ++t;
+                } while (t < t1 && 4 + level_run_len(rows, valid < rows) + values_len(types[c], valid, bytes) < budget);
+                const bool nulls = valid < rows;
+                const uint64_t run = level_run_len(rows, nulls), vbytes = values_len(types[c], valid, bytes);
+                const uint64_t body = 4 + run + vbytes;
+                if (body > kMaxPage || rows > kMaxPage)
+                    return p.error = "a page of column " + std::to_string(c) + " has " + std::to_string(body) + " B: more than a PageHeader's int32", p;
+                Thrift th;
+                th.i32(1, 0);  // DATA_PAGE
+                th.i32(2, (int32_t)body), th.i32(3, (int32_t)body);
+                th.begin(5);
+                th.i32(1, (int32_t)rows), th.i32(2, 0), th.i32(3, 3), th.i32(4, 3);  // PLAIN, RLE, RLE
+                th.end();
+                th.out.push_back(0);
+                put_u32(th.out, (uint32_t)run);
+                if (nulls) {
+                    th.varint((((rows + 7) / 8) << 1) | 1);
+                } else {
+                    th.varint(rows << 1);
+                    th.out.push_back(1);
+                }
+                pg.head_src = p.blob.size(), pg.head_len = (uint32_t)th.out.size();
+                pg.level_bytes = nulls ? (uint32_t)((rows + 7) / 8) : 0;
+                pg.values_bytes = vbytes, pg.rows = (uint32_t)rows, pg.nvalid = (uint32_t)valid;
+                p.blob.insert(p.blob.end(), th.out.begin(), th.out.end());
+                const uint64_t whole = pg.head_len + pg.level_bytes + vbytes;  // == the header's bytes + body
+                at += whole, m.bytes += whole, m.rows += rows, m.nulls += rows - valid;
+                p.pages.push_back(pg);
+            }
+            m.mm.finish(types[c]);
+            g.bytes += m.bytes, p.null_cells += m.nulls;
+        }
+        groups.push_back(std::move(g));
+    }
+    if (groups.size() > 32767) return p.error = std::to_string(groups.size()) + " row groups: more than a RowGroup's int16 ordinal", p;
+    // the footer
+    Thrift f;
+    f.i32(1, 1);
+    f.list(2, kTStruct, ncols + 1);
+    f.begin();
+    f.i32(3, 0), f.binary(4, "schema", 6), f.i32(5, (int32_t)ncols);
+    f.end();
+    for (uint32_t c = 0; c < ncols; ++c) {
+        f.begin();
+        f.i32(1, parquet_type(types[c])), f.i32(3, 1);  // OPTIONAL
+        f.binary(4, names + name_offsets[c], name_offsets[c + 1] - name_offsets[c]);
+        if (is_string(types[c])) {
+            f.i32(6, 0);  // UTF8
+            f.begin(10), f.begin(1), f.end(), f.end();  // LogicalType.STRING
+        }
+        f.end();
+    }
+    f.i64(3, (int64_t)nrows);
+    f.list(4, kTStruct, groups.size());
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+        const Group& g = groups[gi];
+        f.begin();
+        f.list(1, kTStruct, ncols);
+        for (uint32_t c = 0; c < ncols; ++c) {
+            const ChunkMeta& m = g.chunks[c];
+            f.begin();
+            f.i64(2, 0);  // file_offset: unused since the metadata sits in the footer
+            f.begin(3);
+            f.i32(1, parquet_type(types[c]));
+            f.list(2, kTI32, 2), f.varint(Thrift::zigzag(0)), f.varint(Thrift::zigzag(3));  // PLAIN, RLE
+            f.list(3, kTBinary, 1), f.raw_binary(names + name_offsets[c], name_offsets[c + 1] - name_offsets[c]);
+            f.i32(4, 0);  // UNCOMPRESSED
+            f.i64(5, (int64_t)m.rows), f.i64(6, (int64_t)m.bytes), f.i64(7, (int64_t)m.bytes);
+            f.i64(9, (int64_t)m.first_page_at);
+            f.begin(12);
+            f.i64(3, (int64_t)m.nulls);
+            if (m.mm.has) f.binary(5, &m.mm.max, 8), f.binary(6, &m.mm.min, 8);
+            f.end();
+            f.end();
+            f.end();
+        }
+        f.i64(2, (int64_t)g.bytes), f.i64(3, (int64_t)g.rows), f.i64(5, (int64_t)g.at), f.i64(6, (int64_t)g.bytes);
+        f.i16(7, (int16_t)gi);
+        f.end();
+    }
+    f.binary(6, kCreatedBy, strlen(kCreatedBy));
+    f.list(7, kTStruct, ncols);
+    for (uint32_t c = 0; c < ncols; ++c) f.begin(), f.begin(1), f.end(), f.end();  // ColumnOrder.TYPE_ORDER
+    f.out.push_back(0);
+    p.footer = std::move(f.out);
+    const uint64_t meta = p.footer.size();
+    if (meta > 0xFFFFFFFFull) return p.error = "the footer has " + std::to_string(meta) + " B: more than its u32 length", p;
+    put_u32(p.footer, (uint32_t)meta);
+    p.footer.insert(p.footer.end(), {'P', 'A', 'R', '1'});
+    p.row_groups = groups.size();
+    p.out_bytes = at + p.footer.size();
+    return p;
+}
+
+}  // namespace oxh::parquet

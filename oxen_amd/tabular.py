@@ -42,7 +42,8 @@ or more frames written one after the other, as copies -- `concat`, `concat_devic
 `oxh_write_csv_*` writes them back as the file's bytes, which is how every path of the reference ends (`write_df`,
 core/df/tabular.rs:1492-1547) -- `write_csv`, `write_csv_device`, `write_df`; `oxh_write_json_*` as JSON Lines or one
 JSON array (`write_df`'s jsonl / ndjson / json arms, and the text of a data-frame view) -- `write_jsonl`, `write_json` and
-their `_device` forms.
+their `_device` forms; `oxh_write_parquet_*` as an uncompressed Parquet file (what `write_df`'s parquet arm is for) --
+`write_parquet`, `write_parquet_device`.
 
 A frame is an ordered mapping from column name to `Column`. A row's bytes are, over the columns in the
 frame's order: nothing for a null, the raw little-endian bytes of Int8 / Int32 / Float32 / Int64 /
@@ -2388,6 +2389,82 @@ def write_json_device(frame: Mapping, types=None, ctx: Optional[_capi.Context] =
                       with_stats: bool = False):
     """oxh_write_json_device with OXH_JSON_ARRAY: what `json_from_df` makes of a page built on the device."""
     return _write_json_device(frame, _capi.OXH_JSON_ARRAY, types, ctx, capacity, stream, with_stats)
+
+
+# ---------------------------------------------------------------- Parquet: typed columns to the file's bytes (oxh_write_parquet_*)
+class ParquetWriteStats(NamedTuple):
+    """stats4 of oxh_write_parquet_*."""
+    bytes: int
+    row_groups: int
+    pages: int
+    nulls: int
+
+
+def _parquet_head(frame: Mapping, rows_per_group, page_bytes, types):
+    # the columns, types and names as the CSV writer's call takes them; its own tail (separator, quote, header) is not used
+    cols, type_words, name_bytes, name_offsets, _ = _write_head(frame, ",", '"', True, types)
+    return cols, type_words, name_bytes, name_offsets, (int(rows_per_group or 0), int(page_bytes or 0), 0)
+
+
+def _parquet_call(*args):
+    need, stats = _write_call(*args)
+    return need, ParquetWriteStats(*stats)
+
+
+def write_parquet(frame: Mapping, path=None, rows_per_group=None, page_bytes=None, types=None, ctx: Optional[_capi.Context] = None,
+                  with_stats: bool = False):
+    """oxh_write_parquet_host: the frame (an ordered {name: Column}, or what `column` takes, in host memory) as the bytes
+    of a Parquet file by the rules of include/oxen_hash.h "Parquet" -- uncompressed, PLAIN values, DataPage V1, what
+    `write_df`'s parquet arm (core/df/tabular.rs:1508-1517) is for; polars, pyarrow and DuckDB read it. rows_per_group
+    (None: 1 048 576; a multiple of 1 024) and page_bytes (None: 1 MiB) cut the row groups and pages. path, types and
+    the key order are `write_csv`'s. `write_df` itself still refuses `.parquet`: this is the entry."""
+    frame = _as_frame(frame)
+    cols, type_words, name_bytes, name_offsets, tail = _parquet_head(frame, rows_per_group, page_bytes, types)
+    keep = []
+
+    def ptr(a):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a)
+        keep.append(a)
+        return a.ctypes.data if a.size else None
+
+    tables = _tables(cols, ptr)
+    head = (_capi.lib().oxh_write_parquet_host, "oxh_write_parquet_host", ctx, cols, type_words, tables, name_bytes, name_offsets, tail)
+    need, _ = _parquet_call(*head, None, 0)
+    out = np.zeros(max(need, 1), dtype=np.uint8)
+    need, stats = _parquet_call(*head, out.ctypes.data, need)
+    data = out[:need].tobytes()
+    if path is not None:
+        from .version_store import AtomicFile
+
+        AtomicFile(path, ctx).write(data)
+    return (data, stats) if with_stats else data
+
+
+def write_parquet_device(frame: Mapping, rows_per_group=None, page_bytes=None, types=None, ctx: Optional[_capi.Context] = None,
+                         capacity: Optional[int] = None, stream=None, with_stats: bool = False):
+    """oxh_write_parquet_device over device `Column`s; the file's bytes as a uint8 torch tensor on the device. It
+    measures, allocates, then writes; a caller's `capacity` (bytes) skips the measure, and a capacity below the need is
+    the library's error. Blocks."""
+    import torch
+
+    from .device import _require_cuda, _stream
+
+    cols, type_words, name_bytes, name_offsets, tail = _parquet_head(frame, rows_per_group, page_bytes, types)
+    tensors = [t for c in cols for t in (c.values, c.offsets, c.validity) if t is not None]
+    _require_cuda(*tensors)
+    if any(not t.is_contiguous() for t in tensors):
+        raise _capi.OxenError("column tensors must be contiguous", _capi.OXH_ERR_INVALID)
+    device = tensors[0].device if tensors else "cuda"
+    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()  # noqa: E731
+    tables = _tables(cols, ptr)
+    head = (_capi.lib().oxh_write_parquet_device, "oxh_write_parquet_device", ctx, cols, type_words, tables, name_bytes, name_offsets, tail)
+    if capacity is None:
+        capacity, _ = _parquet_call(*head, None, 0, _stream(stream))
+    out = torch.empty(max(int(capacity), 1), dtype=torch.uint8, device=device)
+    need, stats = _parquet_call(*head, out.data_ptr(), int(capacity), _stream(stream))
+    return (out[:need], stats) if with_stats else out[:need]
 
 
 def write_df(frame: Mapping, path, ctx: Optional[_capi.Context] = None) -> bytes:
