@@ -1200,7 +1200,7 @@ int oxh_write_json_host(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const uint
  *   Statistics, per column chunk: null_count for every column; min_value and max_value for INT64 (signed) and for
  *     DOUBLE by the format's rule (NaNs left out; neither written when every cell is NaN or null; a zero min is -0.0,
  *     a zero max is +0.0). Booleans and strings get null_count only. There are no page statistics or indexes.
- *   Stated and not built: reading Parquet; compression; dictionary encoding; nested and narrower types; the `arrow`
+ *   Stated and not built: compression; dictionary encoding; nested and narrower types; the `arrow`
  *     arm of `write_df`.
  *
  * Inputs: as oxh_write_json_* (names and name_offsets are always read; host memory in both forms), then
@@ -1330,6 +1330,80 @@ int oxh_jsonl_columns_device(void* jsonl, uint32_t nsel, const uint32_t* col_idx
 int oxh_jsonl_columns_host(void* jsonl, uint32_t nsel, const uint32_t* col_idx, const uint32_t* types, const uint64_t* value_capacity,
                            void* const* values, void* const* offsets, uint8_t* const* validity, uint64_t* value_bytes,
                            uint64_t* stats4);
+
+/* ---------------------------------------------------------------- Parquet: the file's bytes to typed Arrow columns
+ * The reference reads Parquet in read_df_parquet / scan_parquet (core/df/tabular.rs:111, :172), which feed every
+ * `oxen df`, diff and workspace path once a file is committed as `.parquet`, and takes the height from the metadata
+ * (ParquetReader::num_rows, :1445). oxh_parquet_* do it on the device: the bytes of an UNCOMPRESSED Parquet file
+ * with a FLAT schema in HBM to a page index (a handle), then to the typed columns oxh_csv_columns_* produce, which
+ * every tabular entry above takes as they are and oxh_write_parquet_* writes back.
+ *   Read. Leaf columns directly under the root, REQUIRED or OPTIONAL (max definition level 0 or 1). Physical types:
+ *     BOOLEAN -> OXH_COL_BOOL; INT32, FLOAT -> OXH_COL_FIXED4; INT64, DOUBLE -> OXH_COL_FIXED8; BYTE_ARRAY ->
+ *     OXH_COL_BYTES32 or OXH_COL_BYTES64, the caller's choice. Logical and converted types are NOT interpreted: the
+ *     physical bits are delivered (a DATE is its int32 days, a TIMESTAMP its int64, a DECIMAL its unscaled integer, a
+ *     BYTE_ARRAY its bytes with no UTF-8 check). Pages: DataPage V1 and V2, DICTIONARY_PAGE, and a chunk that starts
+ *     dictionary-coded and falls back to PLAIN pages. Encodings: PLAIN; PLAIN_DICTIONARY / RLE_DICTIONARY at index
+ *     widths 0 to 32; RLE for definition levels with any mix of RLE and bit-packed runs; RLE for BOOLEAN values. A null
+ *     cell's value is 0 / false / no bytes.
+ *   Type words. A column is read as the type word the caller names: its native one (oxh_parquet_types), or
+ *     OXH_CSV_INT64 on an INT32 column (sign-extended), OXH_CSV_FLOAT64 on a FLOAT column (widened exactly), or
+ *     OXH_CSV_STRING64 on a BYTE_ARRAY column. OXH_CSV_INT32 and OXH_CSV_FLOAT32 give the narrow kinds as they are
+ *     (4-byte cells, values 4-byte aligned); only these entries know the two words, every writer refuses them.
+ *   Refused at open, the message naming the column and the cause: a codec other than UNCOMPRESSED (the codec's number
+ *     is named, so that a caller can route the file to the CPU; a V2 page's is_compressed flag means nothing without a
+ *     codec and is ignored), nested fields, repeated fields, encrypted files. Refused at oxh_parquet_columns_* when the
+ *     column is selected: INT96 and FIXED_LEN_BYTE_ARRAY (known from the footer: oxh_parquet_types says so), and what
+ *     only the pages show -- DELTA_* and BYTE_STREAM_SPLIT or any other value encoding, repetition levels, level
+ *     encodings other than RLE, index pages. An unselected column of these does not stop the others.
+ *   Stated and not built: decompression (snappy, zstd: polars' default writer compresses, so this reader reads this
+ *     library's files and any written with compression off); row-range and row-group selection; page and column
+ *     indexes; statistics pushdown; the `.arrow` form.
+ *
+ * The handle holds the footer's plan and the page table: one record per page (where its body starts, its kind, its
+ * num_values, its value encoding, where its levels and values start), found by chasing every chunk's PageHeaders on
+ * the device at open, one lane per chunk. Offsets are 64-bit and a file may pass 4 GiB; a page may not pass
+ * INT32_MAX bytes; rows are at most 2^40. Lifetime, threading and streams are the JSON Lines handle's:
+ * oxh_parquet_open_device reads the caller's d_bytes (any alignment), which must stay alive and unchanged until
+ * oxh_parquet_close; oxh_parquet_open_host owns a device copy; all entries block until complete; a handle is used by
+ * one thread at a time; stream orders the device forms' work, the host forms use the ctx's stream. No result depends
+ * on what working memory or the outputs held, and every load is bounded by the page or run it belongs to: a
+ * malformed page (a run or a length chain that leaves its page, a dictionary index beyond its dictionary -- read as
+ * index 0 --, a PLAIN page shorter than its values) makes oxh_parquet_columns_* return OXH_ERR_INVALID.
+ *   stats8 = {rows, ncols, row groups, data pages, dictionary pages, footer bytes, columns this reader cannot read, 0}.
+ * oxh_parquet_open_*: flags must be 0. OXH_ERR_INVALID, every message starting with "parquet open:", in this order:
+ * unknown flags; NULL bytes with nbytes > 0; NULL out; NULL stats8; then the footer's refusals -- fewer than 12
+ * bytes; the magic PARE (encrypted); a tail, then a head, that is not PAR1; a footer length larger than the file; a
+ * footer that is no FileMetaData; an encrypted footer; a schema without a root; a nested field; a repeated field;
+ * more than 2^40 rows; per row group, in order: a chunk count that is not the schema's, a chunk without plain
+ * metadata, a codec other than UNCOMPRESSED, a chunk that is not inside the file in front of the footer, a
+ * num_values that is not the group's rows; group rows that do not sum to num_rows. Chunks are NOT checked against
+ * their neighbours: chunks that overlap are read as they stand (every load stays inside its own chunk). In the host form the footer is in
+ * host memory and its refusals come BEFORE OXH_ERR_NODEVICE; in the device form it has to come down first, so
+ * OXH_ERR_NODEVICE and a NULL ctx come before them. Then the page walk: a page header that runs past its chunk,
+ * negative sizes, or pages whose values do not sum to the chunk's num_values are OXH_ERR_INVALID. A failed
+ * allocation is OXH_ERR_NOMEM with the outputs untouched.
+ * oxh_parquet_close: NULL is OXH_OK.
+ * oxh_parquet_names: the names, by the size-then-fill contract of oxh_csv_header.
+ * oxh_parquet_types: per column, types4[4 c ..] = {the type word it is read as natively (0: none), its physical
+ * type (the format's number), 1 if REQUIRED, 1 if this reader can read it}. OXH_ERR_INVALID: a NULL handle; NULL
+ * types4 with columns.
+ * oxh_parquet_columns_*: the parameters, outputs, measure-only mode, size-then-fill contract and checks (in the same
+ * order) of oxh_csv_columns_*, with OXH_CSV_INT32 and OXH_CSV_FLOAT32 known; then, per selection in order: a column
+ * this reader cannot read (its cause named), a type word that does not fit the column's physical type. stats4 =
+ * {nulls, dictionary-coded values, pages (data and dictionary), value bytes}. Messages start with "parquet columns:". */
+#define OXH_CSV_INT32 6   /* oxh_parquet_columns_* only */
+#define OXH_CSV_FLOAT32 7 /* oxh_parquet_columns_* only */
+int oxh_parquet_open_device(oxh_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, uint32_t flags, void** out, uint64_t* stats8, void* stream);
+int oxh_parquet_open_host(oxh_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, uint32_t flags, void** out, uint64_t* stats8);
+int oxh_parquet_close(void* parquet);
+int oxh_parquet_names(void* parquet, uint8_t* names, uint64_t capacity, uint64_t* name_offsets, uint64_t* names_bytes);
+int oxh_parquet_types(void* parquet, uint32_t* types4);
+int oxh_parquet_columns_device(void* parquet, uint32_t nsel, const uint32_t* col_idx, const uint32_t* types, const uint64_t* value_capacity,
+                               void* const* d_values, void* const* d_offsets, uint8_t* const* d_validity, uint64_t* value_bytes,
+                               uint64_t* stats4, void* stream);
+int oxh_parquet_columns_host(void* parquet, uint32_t nsel, const uint32_t* col_idx, const uint32_t* types, const uint64_t* value_capacity,
+                             void* const* values, void* const* offsets, uint8_t* const* validity, uint64_t* value_bytes,
+                             uint64_t* stats4);
 
 /* ---------------------------------------------------------------- K2: merkle parent nodes */
 /* get_combined_hash (hasher.rs:67-80) x n on the device:

@@ -22,7 +22,8 @@ Modules:
                and the CSV file itself: read on the device (read_csv, read_csv_device) and written there (write_csv,
                write_csv_device, write_df), and the same columns as JSON Lines or one JSON array (write_jsonl, write_json and their
                _device forms), and as a Parquet file (write_parquet, write_parquet_device),
-               and JSON Lines read on the device (read_jsonl, read_jsonl_device, read_df)
+               and JSON Lines read on the device (read_jsonl, read_jsonl_device, read_df), and uncompressed Parquet
+               read on the device (read_parquet, read_parquet_device, ParquetFile)
   procpool  -- file hashing sharded over reader processes (the open/close floor is per process)
   shard     -- multi-GPU sharding and the RCCL digest gather
   device    -- device-resident (HBM) batch entry points over torch buffers
@@ -51,7 +52,8 @@ _FROM_TABULAR = ("KeyedDiff", "STATUS_NAMES", "keyed_diff_digests", "keyed_diff_
                  "csv_schema", "CsvWriteStats", "write_csv", "write_csv_device", "write_df", "JsonWriteStats", "write_jsonl",
                  "write_jsonl_device", "write_json", "write_json_device", "ParquetWriteStats",
                  "write_parquet", "write_parquet_device", "JsonlStats", "JsonlFile", "read_jsonl", "read_jsonl_device",
-                 "jsonl_shape", "jsonl_schema", "read_df")
+                 "jsonl_shape", "jsonl_schema", "read_df", "ParquetStats", "ParquetColumnStats", "ParquetColumnType", "ParquetFile",
+                 "read_parquet", "read_parquet_device", "parquet_shape", "parquet_schema")
 
 
 def __getattr__(name):

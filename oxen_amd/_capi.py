@@ -70,6 +70,8 @@ OXH_CSV_FLOAT64 = 2
 OXH_CSV_BOOL = 3
 OXH_CSV_STRING = 4      # OXH_COL_BYTES32
 OXH_CSV_STRING64 = 5    # OXH_COL_BYTES64
+OXH_CSV_INT32 = 6       # OXH_COL_FIXED4; oxh_parquet_columns_* only
+OXH_CSV_FLOAT32 = 7     # OXH_COL_FIXED4; oxh_parquet_columns_* only
 OXH_JSON_LINES = 0      # flags of oxh_write_json_*: one object per row and line
 OXH_JSON_ARRAY = 1      # one array of the rows' objects
 
@@ -233,6 +235,15 @@ SIGNATURES = {
                                         ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u64p, _u64p, _vp]),
     "oxh_jsonl_columns_host": (_int, [_vp, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32), _u64p, ctypes.POINTER(_vp),
                                       ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u64p, _u64p]),
+    "oxh_parquet_open_device": (_int, [_vp, _vp, _u64, _u32, ctypes.POINTER(_vp), _u64p, _vp]),
+    "oxh_parquet_open_host": (_int, [_vp, _vp, _u64, _u32, ctypes.POINTER(_vp), _u64p]),
+    "oxh_parquet_close": (_int, [_vp]),
+    "oxh_parquet_names": (_int, [_vp, _vp, _u64, _u64p, _u64p]),
+    "oxh_parquet_types": (_int, [_vp, ctypes.POINTER(_u32)]),
+    "oxh_parquet_columns_device": (_int, [_vp, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32), _u64p, ctypes.POINTER(_vp),
+                                          ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u64p, _u64p, _vp]),
+    "oxh_parquet_columns_host": (_int, [_vp, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32), _u64p, ctypes.POINTER(_vp),
+                                        ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u64p, _u64p]),
     "oxh_comm_check": (_int, [_int]),
     "oxh_ctx_counters": (_int, [_vp, _u64p, _int]),
     "oxh_comm_unique_id": (_int, [ctypes.c_char_p]),

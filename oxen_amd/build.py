@@ -18,14 +18,14 @@ SOURCES = [os.path.join(CSRC, f) for f in (
     "xxh3_kernels.hip", "capi_dispatch.hip", "capi_context.hip", "staging.hip", "large_items.hip", "xxh3_stream.hip",
     "engine.hip", "modified.hip", "publish.hip", "fastcdc.hip", "fastcdc_scan.hip", "fastcdc_walk.hip", "dedup_index.hip",
     "row_hash.hip", "keyed_diff.hip", "take_columns.hip", "concat_columns.hip", "sort_rows.hip", "group_rows.hip", "filter_rows.hip",
-    "embedding.hip", "csv_read.hip", "csv_write.hip", "json_write.hip", "jsonl_read.hip", "parquet_write.hip", "reader_pool.cpp", "comm.cpp", "fastcdc_host.cpp")]
+    "embedding.hip", "csv_read.hip", "csv_write.hip", "json_write.hip", "jsonl_read.hip", "parquet_write.hip", "parquet_read.hip", "reader_pool.cpp", "comm.cpp", "fastcdc_host.cpp")]
 DEPS = SOURCES + [os.path.join(CSRC, h) for h in ("capi_internal.hpp", "xxh3_device.hpp", "fastcdc_gear.h", "fastcdc_plan.hpp",
                                                  "fastcdc_device.hpp", "pool.hpp", "scratch.hpp", "reader_pool.hpp",
                                                  "env.hpp", "keyed_diff_host.hpp", "columns.hpp",
                                                  "take_columns_host.hpp", "concat_columns_host.hpp", "sort_rows_host.hpp", "sort_keys.hpp",
                                                  "group_rows_host.hpp", "filter_rows_host.hpp", "filter_terms.hpp",
                                                  "embedding_host.hpp", "csv_host.hpp", "csv_number.hpp", "csv_text.hpp", "json_text.hpp", "jsonl_host.hpp",
-                                                 "jsonl_text.hpp", "parquet_host.hpp")] + [os.path.join(ROOT, "include", "oxen_hash.h")]
+                                                 "jsonl_text.hpp", "parquet_host.hpp", "parquet_read_host.hpp", "parquet_bits.hpp")] + [os.path.join(ROOT, "include", "oxen_hash.h")]
 HELPER_SRC = os.path.join(CSRC, "hash_helper.cpp")
 HELPER = os.path.join(HERE, "oxh_hash_helper")  # the reader-pool helper process (oxh_pool_*)
 ARCH = "gfx950"
@@ -86,6 +86,8 @@ JSONL_TEST_SRC = os.path.join(ROOT, "tests", "native", "jsonl_host_test.cpp")
 JSONL_TEST = os.path.join(ROOT, "tests", "native", "jsonl_host_test")  # tests only: the JSON Lines reader's grammar, carries and host pieces
 PARQUET_TEST_SRC = os.path.join(ROOT, "tests", "native", "parquet_host_test.cpp")
 PARQUET_TEST = os.path.join(ROOT, "tests", "native", "parquet_host_test")  # tests only: the Parquet writer's Thrift encoder, planner and statistics
+PARQUET_READ_TEST_SRC = os.path.join(ROOT, "tests", "native", "parquet_read_host_test.cpp")
+PARQUET_READ_TEST = os.path.join(ROOT, "tests", "native", "parquet_read_host_test")  # tests only: the Parquet reader's Thrift decoder, hybrid runs and footer planner
 FAKE_RCCL_SRC = os.path.join(ROOT, "tests", "native", "fake_rccl.cpp")
 # tests only: an "RCCL" for N processes on one GPU (OXH_RCCL_LIB), with and without ncclGather
 FAKE_RCCL = os.path.join(ROOT, "tests", "native", "libfake_rccl.so")
@@ -110,8 +112,9 @@ def build_host(force: bool = False, verbose: bool = False) -> str:
     (tests/native/csv_host_test.cpp), of the CSV writer's text functions (tests/native/csv_write_host_test.cpp), of
     both CSV float conversions over cells a test sends in (tests/native/csv_float_cases.cpp), of the JSON writer's
     text functions (tests/native/json_write_host_test.cpp), of the JSON Lines reader's grammar, carries and host
-    pieces (tests/native/jsonl_host_test.cpp) and of the Parquet writer's Thrift encoder, planner and statistics
-    (tests/native/parquet_host_test.cpp)."""
+    pieces (tests/native/jsonl_host_test.cpp), of the Parquet writer's Thrift encoder, planner and statistics
+    (tests/native/parquet_host_test.cpp) and of the Parquet reader's Thrift decoder, hybrid runs and footer planner
+    (tests/native/parquet_read_host_test.cpp)."""
     hdr = os.path.join(ROOT, "include", "oxen_hash.h")
     steps = [
         (HELPER, [HELPER_SRC, os.path.join(CSRC, "reader_pool.hpp"), hdr, LIB],
@@ -164,6 +167,9 @@ def build_host(force: bool = False, verbose: bool = False) -> str:
          ["g++", "-std=c++17", "-O2", "-Wall", "-o", JSONL_TEST + ".tmp", JSONL_TEST_SRC]),
         (PARQUET_TEST, [PARQUET_TEST_SRC, os.path.join(CSRC, "parquet_host.hpp"), os.path.join(CSRC, "columns.hpp"), hdr],
          ["g++", "-std=c++17", "-O2", "-Wall", "-o", PARQUET_TEST + ".tmp", PARQUET_TEST_SRC]),
+        (PARQUET_READ_TEST, [PARQUET_READ_TEST_SRC, os.path.join(CSRC, "parquet_read_host.hpp"), os.path.join(CSRC, "parquet_bits.hpp"),
+                             os.path.join(CSRC, "parquet_host.hpp"), os.path.join(CSRC, "csv_host.hpp"), os.path.join(CSRC, "columns.hpp"), hdr],
+         ["g++", "-std=c++17", "-O2", "-Wall", "-o", PARQUET_READ_TEST + ".tmp", PARQUET_READ_TEST_SRC]),
     ]
     for target, extra in ((FAKE_RCCL, []), (FAKE_RCCL_NOGATHER, ["-DFAKE_NO_GATHER"])):
         steps.append((target, [FAKE_RCCL_SRC],

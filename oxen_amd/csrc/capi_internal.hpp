@@ -61,6 +61,10 @@
 //                      groups, Thrift headers and the footer from that table (parquet_host.hpp); then a wave per tile
 //                      and column compacts the valid cells to their ranks through LDS -- mbcnt over validity ballots
 //                      -- and stores them in aligned 16-byte blocks behind the page's header and levels
+//   parquet_read.hip   an uncompressed, flat Parquet file to the same typed columns (oxh_parquet_*): the footer's plan on
+//                      the host (parquet_read_host.hpp, parquet_bits.hpp), a lane per chunk chasing page headers, a wave
+//                      per page for the levels' and indices' hybrid runs, a lane per output row for the gather, the
+//                      strings' length chain through LDS windows
 // There is no CPU hashing path: every digest this library returns was computed on the GPU.
 #pragma once
 

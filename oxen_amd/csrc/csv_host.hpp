@@ -36,7 +36,8 @@ inline uint64_t tiles_of(uint64_t misalign, uint64_t nbytes) { return (misalign 
 inline bool known_type(uint32_t t) { return t >= OXH_CSV_INT64 && t <= OXH_CSV_STRING64; }
 inline bool is_string(uint32_t t) { return t == OXH_CSV_STRING || t == OXH_CSV_STRING64; }
 // bytes of the values buffer of a column of nrows rows that is not a string column
-inline uint64_t fixed_value_bytes(uint32_t type, uint64_t nrows) { return type == OXH_CSV_BOOL ? (nrows + 7) / 8 : nrows * 8; }
+inline bool is_narrow(uint32_t t) { return t == OXH_CSV_INT32 || t == OXH_CSV_FLOAT32; }  // 4-byte cells: the Parquet reader's only
+inline uint64_t fixed_value_bytes(uint32_t type, uint64_t nrows) { return type == OXH_CSV_BOOL ? (nrows + 7) / 8 : nrows * (is_narrow(type) ? 4 : 8); }
 
 // "" when oxh_csv_open_*'s arguments are well formed, else what is wrong with them, in the header's order.
 inline std::string open_error(const uint8_t* bytes, uint64_t nbytes, uint32_t separator, uint32_t quote, uint32_t flags,
@@ -68,13 +69,13 @@ struct ColumnsArgs {
 };
 
 // The same for oxh_csv_columns_* (after the handle itself was checked). All three output tables NULL: the call
-// only measures.
-inline std::string columns_error(const ColumnsArgs& a) {
+// only measures. last_type: the last type word the entry knows (the Parquet reader's entries know the narrow ones).
+inline std::string columns_error(const ColumnsArgs& a, uint32_t last_type = OXH_CSV_STRING64) {
     if (a.nsel && (!a.col_idx || !a.types)) return "col_idx or types is NULL";
     for (uint32_t k = 0; k < a.nsel; ++k)
         if (a.col_idx[k] >= a.ncols) return "selection " + std::to_string(k) + " names column " + std::to_string(a.col_idx[k]) + " of " + std::to_string(a.ncols);
     for (uint32_t k = 0; k < a.nsel; ++k)
-        if (!known_type(a.types[k])) return "selection " + std::to_string(k) + " has unknown type " + std::to_string(a.types[k]);
+        if (a.types[k] < OXH_CSV_INT64 || a.types[k] > last_type) return "selection " + std::to_string(k) + " has unknown type " + std::to_string(a.types[k]);
     if (a.nsel && (!a.value_bytes || !a.stats4)) return "value_bytes or stats4 is NULL";
     const bool measure = !a.values && !a.offsets && !a.validity;
     if (measure || !a.nsel) return "";
@@ -92,7 +93,8 @@ inline std::string columns_error(const ColumnsArgs& a) {
             if (!a.values[k]) return col + " has no values buffer";
             if (a.value_capacity[k] < fixed_value_bytes(a.types[k], a.nrows))
                 return col + ": value_capacity is below the " + std::to_string(fixed_value_bytes(a.types[k], a.nrows)) + " bytes of its values";
-            if (a.types[k] != OXH_CSV_BOOL && ((uintptr_t)a.values[k] & 7)) return col + ": values is not 8-byte aligned";
+            if (is_narrow(a.types[k]) && ((uintptr_t)a.values[k] & 3)) return col + ": values is not 4-byte aligned";
+            if (a.types[k] != OXH_CSV_BOOL && !is_narrow(a.types[k]) && ((uintptr_t)a.values[k] & 7)) return col + ": values is not 8-byte aligned";
         }
     }
     return "";

@@ -43,7 +43,8 @@ or more frames written one after the other, as copies -- `concat`, `concat_devic
 core/df/tabular.rs:1492-1547) -- `write_csv`, `write_csv_device`, `write_df`; `oxh_write_json_*` as JSON Lines or one
 JSON array (`write_df`'s jsonl / ndjson / json arms, and the text of a data-frame view) -- `write_jsonl`, `write_json` and
 their `_device` forms; `oxh_write_parquet_*` as an uncompressed Parquet file (what `write_df`'s parquet arm is for) --
-`write_parquet`, `write_parquet_device`.
+`write_parquet`, `write_parquet_device`; and `oxh_parquet_*` read such a file back (`ParquetFile`, `read_parquet`,
+`read_parquet_device`, `parquet_shape`, `parquet_schema`).
 
 A frame is an ordered mapping from column name to `Column`. A row's bytes are, over the columns in the
 frame's order: nothing for a null, the raw little-endian bytes of Int8 / Int32 / Float32 / Int64 /
@@ -2655,6 +2656,236 @@ def jsonl_schema(path_or_bytes, infer_rows: int = 10000, ctx: Optional[_capi.Con
     data, _ = _csv_bytes(path_or_bytes)
     with JsonlFile(data, infer_rows, ctx=ctx) as f:
         return list(zip(f.names, [CSV_TYPE_NAMES[t] for t in f.infer()]))
+
+
+# ---------------------------------------------------------------- Parquet: page index and typed columns (oxh_parquet_*)
+PARQUET_TYPE_NAMES = {**CSV_TYPE_NAMES, _capi.OXH_CSV_INT32: "Int32", _capi.OXH_CSV_FLOAT32: "Float32"}   # polars' dtype names
+_PARQUET_TYPE_OF = {name: code for code, name in PARQUET_TYPE_NAMES.items()}
+_PARQUET_PHYSICAL = ("BOOLEAN", "INT32", "INT64", "INT96", "FLOAT", "DOUBLE", "BYTE_ARRAY", "FIXED_LEN_BYTE_ARRAY")
+
+
+class ParquetStats(NamedTuple):
+    """stats8 of oxh_parquet_open_* (without its last, unused word)."""
+    rows: int
+    ncols: int
+    row_groups: int
+    data_pages: int
+    dict_pages: int
+    footer_bytes: int
+    unreadable_columns: int
+
+
+class ParquetColumnStats(NamedTuple):
+    """stats4 of one selected column of oxh_parquet_columns_*."""
+    nulls: int
+    dict_values: int
+    pages: int
+    value_bytes: int
+
+
+class ParquetColumnType(NamedTuple):
+    """One column of oxh_parquet_types: the OXH_CSV_* word it is read as natively (0: none), its physical type's
+    name, whether it is REQUIRED, whether this reader can read it."""
+    type: int
+    physical: str
+    required: bool
+    readable: bool
+
+
+def _parquet_type(t) -> int:
+    if isinstance(t, str):
+        if t not in _PARQUET_TYPE_OF:
+            raise _capi.OxenError(f"unknown Parquet column type {t!r} (one of {sorted(_PARQUET_TYPE_OF)})", _capi.OXH_ERR_INVALID)
+        return _PARQUET_TYPE_OF[t]
+    return int(t)
+
+
+class ParquetFile:
+    """The page index of one Parquet buffer (an oxh_parquet_open_* handle), the twin of `JsonlFile`: `stats`,
+    `names`, `types`, `measure`, `columns`. data: bytes / a uint8 numpy array (the host form, which owns a device
+    copy), or with device=True a uint8 torch tensor on the device, which the object keeps alive. The rules are
+    include/oxen_hash.h's "Parquet: the file's bytes": uncompressed files with a flat schema, the physical bits."""
+
+    def __init__(self, data, ctx: Optional[_capi.Context] = None, device: bool = False, stream=None):
+        self.device = device
+        self.ctx = ctx
+        self.stream = stream
+        self.handle = None
+        out = ctypes.c_void_p()
+        stats = np.zeros(8, dtype=np.uint64)
+        if device:
+            from .device import _require_cuda, _stream
+
+            _require_cuda(data)
+            if data.element_size() != 1 or not data.is_contiguous():
+                raise _capi.OxenError("the Parquet bytes are a contiguous uint8 tensor", _capi.OXH_ERR_INVALID)
+            self.data = data
+            _capi.check(_capi.lib().oxh_parquet_open_device(_handle(ctx), data.data_ptr() if data.numel() else None, data.numel(), 0,
+                                                            ctypes.byref(out), stats.ctypes.data_as(_capi._u64p), _stream(stream)),
+                        "oxh_parquet_open_device")
+        else:
+            self.data = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+            _capi.check(_capi.lib().oxh_parquet_open_host(_handle(ctx), self.data.ctypes.data if self.data.size else None, self.data.size, 0,
+                                                          ctypes.byref(out), stats.ctypes.data_as(_capi._u64p)),
+                        "oxh_parquet_open_host")
+        self.handle = out
+        self.stats = ParquetStats(*(int(x) for x in stats[:7]))
+        self._names = None
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            _capi.lib().oxh_parquet_close(self.handle)
+            self.handle = None
+
+    __enter__ = JsonlFile.__enter__
+    __exit__ = JsonlFile.__exit__
+    __del__ = JsonlFile.__del__
+
+    @property
+    def raw_names(self) -> list:
+        """The names as bytes."""
+        if self._names is None:
+            n = self.stats.ncols
+            offsets, size = np.zeros(n + 1, dtype=np.uint64), ctypes.c_uint64(0)
+            L = _capi.lib()
+            _capi.check(L.oxh_parquet_names(self.handle, None, 0, offsets.ctypes.data_as(_capi._u64p), ctypes.byref(size)), "oxh_parquet_names")
+            buf = np.zeros(max(size.value, 1), dtype=np.uint8)
+            _capi.check(L.oxh_parquet_names(self.handle, buf.ctypes.data, size.value, offsets.ctypes.data_as(_capi._u64p), ctypes.byref(size)),
+                        "oxh_parquet_names")
+            raw = buf.tobytes()
+            self._names = [raw[int(offsets[c]):int(offsets[c + 1])] for c in range(n)]
+        return self._names
+
+    names = JsonlFile.names
+
+    def types(self) -> list:
+        """oxh_parquet_types: one `ParquetColumnType` per column, by the footer and the page table."""
+        n = self.stats.ncols
+        words = (ctypes.c_uint32 * max(4 * n, 1))()
+        _capi.check(_capi.lib().oxh_parquet_types(self.handle, words), "oxh_parquet_types")
+        return [ParquetColumnType(int(words[4 * c]), _PARQUET_PHYSICAL[words[4 * c + 1]] if words[4 * c + 1] < 8 else str(words[4 * c + 1]),
+                                  bool(words[4 * c + 2]), bool(words[4 * c + 3])) for c in range(n)]
+
+    def _selection(self, cols, types):
+        cols, types = [int(c) for c in cols], [_parquet_type(t) for t in types]
+        if len(cols) != len(types):
+            raise _capi.OxenError("one type per selected column", _capi.OXH_ERR_INVALID)
+        n = max(len(cols), 1)
+        return cols, types, (ctypes.c_uint32 * n)(*cols), (ctypes.c_uint32 * n)(*types)
+
+    def _call(self, nsel, col_idx, type_words, capacity, values, offsets, validity):
+        value_bytes, stats = np.zeros(max(nsel, 1), dtype=np.uint64), np.zeros(4 * max(nsel, 1), dtype=np.uint64)
+        L = _capi.lib()
+        args = (self.handle, nsel, col_idx, type_words, None if capacity is None else capacity.ctypes.data_as(_capi._u64p), values, offsets,
+                validity, value_bytes.ctypes.data_as(_capi._u64p), stats.ctypes.data_as(_capi._u64p))
+        if self.device:
+            from .device import _stream
+
+            _capi.check(L.oxh_parquet_columns_device(*args, _stream(self.stream)), "oxh_parquet_columns_device")
+        else:
+            _capi.check(L.oxh_parquet_columns_host(*args), "oxh_parquet_columns_host")
+        return ([int(x) for x in value_bytes[:nsel]], [ParquetColumnStats(*(int(x) for x in stats[4 * k:4 * k + 4])) for k in range(nsel)])
+
+    measure = CsvFile.measure
+
+    def columns(self, cols, types, with_stats: bool = False):
+        """The selected columns (indices) as `Column`s of the given type words (or polars' dtype names): numpy arrays
+        in the host form, torch tensors on the device in the device form. Validity is always there."""
+        cols, types, col_idx, type_words = self._selection(cols, types)
+        nsel, n = len(cols), self.stats.rows
+        strings = [t in (_capi.OXH_CSV_STRING, _capi.OXH_CSV_STRING64) for t in types]
+        sizes = [0] * nsel   # the bytes of the string columns, and only they are measured
+        which = [k for k in range(nsel) if strings[k]]
+        if which:
+            for k, size in zip(which, self.measure([cols[k] for k in which], [types[k] for k in which])[0]):
+                sizes[k] = size
+        if self.device:
+            import torch
+
+            dev = self.data.device
+            make = lambda count, dtype: torch.empty(count, dtype=getattr(torch, dtype), device=dev)   # noqa: E731
+            ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None                    # noqa: E731
+        else:
+            make = lambda count, dtype: np.zeros(count, dtype=dtype)                                 # noqa: E731
+            ptr = lambda a: a.ctypes.data if a is not None and a.size else None                      # noqa: E731
+        fixed = {_capi.OXH_CSV_INT64: ("int64", 8), _capi.OXH_CSV_FLOAT64: ("float64", 8), _capi.OXH_CSV_INT32: ("int32", 4),
+                 _capi.OXH_CSV_FLOAT32: ("float32", 4)}
+        out = []
+        capacity = np.zeros(max(nsel, 1), dtype=np.uint64)
+        for k, t in enumerate(types):
+            validity = make((n + 7) // 8, "uint8")
+            if strings[k]:
+                values, offsets = make(sizes[k], "uint8"), make(n + 1, "int64" if t == _capi.OXH_CSV_STRING64 else "int32")
+                if n == 0:
+                    offsets[:] = 0
+                capacity[k] = sizes[k]
+                kind = OXH_COL_BYTES64 if t == _capi.OXH_CSV_STRING64 else OXH_COL_BYTES32
+            elif t == _capi.OXH_CSV_BOOL:
+                values, offsets, kind = make((n + 7) // 8, "uint8"), None, OXH_COL_BOOL
+                capacity[k] = (n + 7) // 8
+            elif t in fixed:
+                values, offsets, kind = make(n, fixed[t][0]), None, fixed[t][1]   # OXH_COL_FIXED4 / 8 are their widths
+                capacity[k] = fixed[t][1] * n
+            else:
+                raise _capi.OxenError(f"unknown Parquet column type {t}", _capi.OXH_ERR_INVALID)
+            out.append(Column(kind, n, values, offsets, validity))
+        m = max(nsel, 1)
+        tables = [(ctypes.c_void_p * m)(*[ptr(getattr(c, field)) for c in out]) for field in ("values", "offsets", "validity")]
+        _, stats = self._call(nsel, col_idx, type_words, capacity, *tables)
+        return (out, stats) if with_stats else out
+
+
+def _parquet_frame(f: ParquetFile, schema, columns) -> dict:
+    names = f.names
+    if columns is None:
+        picked = list(range(len(names)))
+    else:
+        picked = []
+        for c in columns:
+            if isinstance(c, str) and c not in names:
+                raise _capi.OxenError(f"no column {c!r} among the Parquet names {names}", _capi.OXH_ERR_INVALID)
+            picked.append(names.index(c) if isinstance(c, str) else int(c))
+    native = f.types()
+    types = []
+    for c in picked:
+        given = None if schema is None else (schema.get(names[c]) if isinstance(schema, Mapping) else schema[c])
+        # a column this reader cannot read has no native word: any known one lets the library name the cause
+        types.append((native[c].type or _capi.OXH_CSV_INT64) if given is None else _parquet_type(given))
+    return dict(zip([names[c] for c in picked], f.columns(picked, types)))
+
+
+def read_parquet(path_or_bytes, schema=None, columns=None, ctx: Optional[_capi.Context] = None) -> dict:
+    """`read_df_parquet` (core/df/tabular.rs:111) on the device: an uncompressed Parquet file with a flat schema (a
+    path) or its bytes to the ordered {name: Column} in host memory that every function of this module takes. columns
+    selects and orders, by name or index. schema ({name: type} or one per selected column; polars' dtype names or
+    OXH_CSV_* words) widens an INT32 column to "Int64", a FLOAT column to "Float64", or picks "LargeString"; a column
+    without one is read as its physical type (`ParquetFile.types`). A compressed file raises with the codec's number:
+    that one goes to the CPU. `read_df` still refuses `.parquet`: this is the entry."""
+    data, _ = _csv_bytes(path_or_bytes)
+    with ParquetFile(data, ctx=ctx) as f:
+        return _parquet_frame(f, schema, columns)
+
+
+def read_parquet_device(d_bytes, schema=None, columns=None, ctx: Optional[_capi.Context] = None, stream=None) -> dict:
+    """`read_parquet` over the file's bytes already on the device (a uint8 torch tensor, as `write_parquet_device`
+    leaves them): device `Column`s that every `_device` function of this module accepts unchanged. Blocks."""
+    with ParquetFile(d_bytes, ctx=ctx, device=True, stream=stream) as f:
+        return _parquet_frame(f, schema, columns)
+
+
+def parquet_shape(path_or_bytes, ctx: Optional[_capi.Context] = None) -> tuple:
+    """(width, height) of the tabular metadata, by the footer alone."""
+    data, _ = _csv_bytes(path_or_bytes)
+    with ParquetFile(data, ctx=ctx) as f:
+        return f.stats.ncols, f.stats.rows
+
+
+def parquet_schema(path_or_bytes, ctx: Optional[_capi.Context] = None) -> list:
+    """[(name, dtype name)] of the tabular metadata: the names and the native types (None: a column this reader
+    cannot read)."""
+    data, _ = _csv_bytes(path_or_bytes)
+    with ParquetFile(data, ctx=ctx) as f:
+        return list(zip(f.names, [PARQUET_TYPE_NAMES.get(t.type) for t in f.types()]))
 
 
 def read_df(path, ctx: Optional[_capi.Context] = None) -> dict:
