@@ -1334,8 +1334,8 @@ int oxh_jsonl_columns_host(void* jsonl, uint32_t nsel, const uint32_t* col_idx, 
 /* ---------------------------------------------------------------- Parquet: the file's bytes to typed Arrow columns
  * The reference reads Parquet in read_df_parquet / scan_parquet (core/df/tabular.rs:111, :172), which feed every
  * `oxen df`, diff and workspace path once a file is committed as `.parquet`, and takes the height from the metadata
- * (ParquetReader::num_rows, :1445). oxh_parquet_* do it on the device: the bytes of an UNCOMPRESSED Parquet file
- * with a FLAT schema in HBM to a page index (a handle), then to the typed columns oxh_csv_columns_* produce, which
+ * (ParquetReader::num_rows, :1445). oxh_parquet_* do it on the device: the bytes of an UNCOMPRESSED or, with
+ * OXH_PARQUET_INFLATE, SNAPPY Parquet file with a FLAT schema in HBM to a page index (a handle), then to the typed columns oxh_csv_columns_* produce, which
  * every tabular entry above takes as they are and oxh_write_parquet_* writes back.
  *   Read. Leaf columns directly under the root, REQUIRED or OPTIONAL (max definition level 0 or 1). Physical types:
  *     BOOLEAN -> OXH_COL_BOOL; INT32, FLOAT -> OXH_COL_FIXED4; INT64, DOUBLE -> OXH_COL_FIXED8; BYTE_ARRAY ->
@@ -1349,14 +1349,24 @@ int oxh_jsonl_columns_host(void* jsonl, uint32_t nsel, const uint32_t* col_idx, 
  *     OXH_CSV_INT64 on an INT32 column (sign-extended), OXH_CSV_FLOAT64 on a FLOAT column (widened exactly), or
  *     OXH_CSV_STRING64 on a BYTE_ARRAY column. OXH_CSV_INT32 and OXH_CSV_FLOAT32 give the narrow kinds as they are
  *     (4-byte cells, values 4-byte aligned); only these entries know the two words, every writer refuses them.
- *   Refused at open, the message naming the column and the cause: a codec other than UNCOMPRESSED (the codec's number
+ *   Compression. Without OXH_PARQUET_INFLATE only UNCOMPRESSED chunks (codec 0) are read. With it, SNAPPY chunks
+ *     (codec 1) too, chunk by chunk, to the same columns: at open every compressed page is inflated ("Snappy" below,
+ *     the same kernel) into an image the handle owns, and the column entries read a page's body from the file or from
+ *     the image. Dictionary pages and V1 data pages are compressed whole (a V1 page's level length is the first 4
+ *     bytes of the inflated body); a V2 page's repetition and definition level bytes are stored as they are and are
+ *     copied into the image in front of the inflated values, so that the page is contiguous; a V2 page whose
+ *     is_compressed is false is stored whole and is read from the file where it lies (pyarrow writes a page so when
+ *     compressing it would not shrink it).
+ *     Cost: the handle holds the inflated size of ALL compressed pages of the file in device memory until
+ *     oxh_parquet_close, whichever columns are read later.
+ *   Refused at open, the message naming the column and the cause: a codec that is not read (the codec's number
  *     is named, so that a caller can route the file to the CPU; a V2 page's is_compressed flag means nothing without a
  *     codec and is ignored), nested fields, repeated fields, encrypted files. Refused at oxh_parquet_columns_* when the
  *     column is selected: INT96 and FIXED_LEN_BYTE_ARRAY (known from the footer: oxh_parquet_types says so), and what
  *     only the pages show -- DELTA_* and BYTE_STREAM_SPLIT or any other value encoding, repetition levels, level
  *     encodings other than RLE, index pages. An unselected column of these does not stop the others.
- *   Stated and not built: decompression (snappy, zstd: polars' default writer compresses, so this reader reads this
- *     library's files and any written with compression off); row-range and row-group selection; page and column
+ *   Stated and not built: zstd (polars' default), gzip, lz4 and brotli; inflating only the columns that are read;
+ *     row-range and row-group selection; page and column
  *     indexes; statistics pushdown; the `.arrow` form.
  *
  * The handle holds the footer's plan and the page table: one record per page (where its body starts, its kind, its
@@ -1369,19 +1379,24 @@ int oxh_jsonl_columns_host(void* jsonl, uint32_t nsel, const uint32_t* col_idx, 
  * on what working memory or the outputs held, and every load is bounded by the page or run it belongs to: a
  * malformed page (a run or a length chain that leaves its page, a dictionary index beyond its dictionary -- read as
  * index 0 --, a PLAIN page shorter than its values) makes oxh_parquet_columns_* return OXH_ERR_INVALID.
- *   stats8 = {rows, ncols, row groups, data pages, dictionary pages, footer bytes, columns this reader cannot read, 0}.
- * oxh_parquet_open_*: flags must be 0. OXH_ERR_INVALID, every message starting with "parquet open:", in this order:
+ *   stats8 = {rows, ncols, row groups, data pages, dictionary pages, footer bytes, columns this reader cannot read,
+ *   pages inflated (0 for a file without a compressed page)}.
+ * oxh_parquet_open_*: flags is 0 or OXH_PARQUET_INFLATE (bit 0 stays reserved). OXH_ERR_INVALID, every message starting with "parquet open:", in this order:
  * unknown flags; NULL bytes with nbytes > 0; NULL out; NULL stats8; then the footer's refusals -- fewer than 12
  * bytes; the magic PARE (encrypted); a tail, then a head, that is not PAR1; a footer length larger than the file; a
  * footer that is no FileMetaData; an encrypted footer; a schema without a root; a nested field; a repeated field;
  * more than 2^40 rows; per row group, in order: a chunk count that is not the schema's, a chunk without plain
- * metadata, a codec other than UNCOMPRESSED, a chunk that is not inside the file in front of the footer, a
+ * metadata, a codec other than UNCOMPRESSED (with OXH_PARQUET_INFLATE: other than that and SNAPPY), a chunk that is not inside the file in front of the footer, a
  * num_values that is not the group's rows; group rows that do not sum to num_rows. Chunks are NOT checked against
  * their neighbours: chunks that overlap are read as they stand (every load stays inside its own chunk). In the host form the footer is in
  * host memory and its refusals come BEFORE OXH_ERR_NODEVICE; in the device form it has to come down first, so
  * OXH_ERR_NODEVICE and a NULL ctx come before them. Then the page walk: a page header that runs past its chunk,
- * negative sizes, or pages whose values do not sum to the chunk's num_values are OXH_ERR_INVALID. A failed
- * allocation is OXH_ERR_NOMEM with the outputs untouched.
+ * negative sizes, sizes that differ on a page that is not compressed, or pages whose values do not sum to the chunk's
+ * num_values are OXH_ERR_INVALID. Then, from the page table and before the image is allocated: a compressed page
+ * whose uncompressed size is above 22 * its compressed size + 32 (no Snappy stream expands more than 64 / 3) is
+ * OXH_ERR_INVALID and names the column; after the inflation a page whose stream is malformed is OXH_ERR_INVALID and
+ * names the column and the cause. A failed allocation -- the image among them -- is OXH_ERR_NOMEM with the outputs
+ * untouched.
  * oxh_parquet_close: NULL is OXH_OK.
  * oxh_parquet_names: the names, by the size-then-fill contract of oxh_csv_header.
  * oxh_parquet_types: per column, types4[4 c ..] = {the type word it is read as natively (0: none), its physical
@@ -1393,6 +1408,7 @@ int oxh_jsonl_columns_host(void* jsonl, uint32_t nsel, const uint32_t* col_idx, 
  * {nulls, dictionary-coded values, pages (data and dictionary), value bytes}. Messages start with "parquet columns:". */
 #define OXH_CSV_INT32 6   /* oxh_parquet_columns_* only */
 #define OXH_CSV_FLOAT32 7 /* oxh_parquet_columns_* only */
+#define OXH_PARQUET_INFLATE 2u /* flags of oxh_parquet_open_*: read SNAPPY chunks too */
 int oxh_parquet_open_device(oxh_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, uint32_t flags, void** out, uint64_t* stats8, void* stream);
 int oxh_parquet_open_host(oxh_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, uint32_t flags, void** out, uint64_t* stats8);
 int oxh_parquet_close(void* parquet);
@@ -1404,6 +1420,51 @@ int oxh_parquet_columns_device(void* parquet, uint32_t nsel, const uint32_t* col
 int oxh_parquet_columns_host(void* parquet, uint32_t nsel, const uint32_t* col_idx, const uint32_t* types, const uint64_t* value_capacity,
                              void* const* values, void* const* offsets, uint8_t* const* validity, uint64_t* value_bytes,
                              uint64_t* stats4);
+
+/* ---------------------------------------------------------------- Snappy: many raw blocks inflated per call
+ * What a SNAPPY Parquet page holds (pyarrow, pandas, Spark and DuckDB write that codec by default), and what
+ * oxh_parquet_open_* with OXH_PARQUET_INFLATE runs over every compressed page. Raw blocks only: the framed stream
+ * format (the magic "sNaPpY" and chunk checksums) is not read.
+ *   A block is a preamble, then elements. The preamble is the uncompressed length as a varint (7 bits a byte, low
+ *   first, the top bit says another byte follows): at most 5 bytes and at most 2^32 - 1. The low 2 bits of an
+ *   element's tag byte choose it:
+ *     00 literal  length (tag >> 2) + 1 for tag >> 2 of 0..59; 60..63: length - 1 is the next 1..4 bytes, little
+ *                 endian; then the bytes themselves;
+ *     01 copy     length 4 + ((tag >> 2) & 7), offset ((tag >> 5) << 8) | the next byte;
+ *     10 copy     length (tag >> 2) + 1, offset the next 2 bytes, little endian;
+ *     11 copy     length (tag >> 2) + 1, offset the next 4 bytes, little endian.
+ *   A copy appends `length` bytes that start `offset` bytes in front of the output's end; an offset smaller than the
+ *   length repeats the pattern: byte i is out[dst - offset + i % offset].
+ * Block b reads src[src_offsets[b], src_offsets[b + 1]) and fills dst[dst_offsets[b], dst_offsets[b + 1]), whose
+ * length is the block's EXPECTED uncompressed length (the caller reads it from the preamble or, as Parquet does, knows
+ * it from elsewhere); any alignment, nblocks + 1 offsets each, not decreasing. status[b] = 0, or the first cause that
+ * ends the block, whose whole destination is then zeros:
+ *   OXH_SNAPPY_PREAMBLE       no preamble, one longer than 5 bytes or above 2^32 - 1, or not the expected length;
+ *   OXH_SNAPPY_INPUT          a tag's extra bytes or a literal's bytes leave the block's input;
+ *   OXH_SNAPPY_OFFSET_ZERO    a copy with offset 0;
+ *   OXH_SNAPPY_OFFSET_BEYOND  a copy whose offset is larger than the bytes produced so far;
+ *   OXH_SNAPPY_OVERRUN        an element that would pass the declared length (so does any element behind a full output);
+ *   OXH_SNAPPY_TRUNCATED      the input ends before the declared length is reached;
+ *   OXH_SNAPPY_RANGE          device form: the block's offsets decrease (nothing of it is read or written).
+ * No byte outside a block's own destination is written and none outside its own input is read, whatever the stream
+ * holds. A malformed block is NOT an error of the call: the call returns OXH_OK and *bad_blocks = the blocks with a
+ * cause. Both forms block until complete; stream orders the device form's work, the host form uses the ctx's stream
+ * and leaves dst, status and bad_blocks untouched unless it returns OXH_OK. OXH_ERR_INVALID, every message starting
+ * with "snappy inflate:", in this order: NULL bad_blocks; then nblocks == 0 is OXH_OK with *bad_blocks = 0; more than
+ * 2^32 blocks; NULL src, src_offsets, dst_offsets, status; host form: offsets that decrease (the block named), NULL
+ * dst with bytes to fill; then OXH_ERR_NODEVICE; then a NULL ctx. A failed allocation is OXH_ERR_NOMEM.
+ *   Stated and not built: a compressor; the framed format; zstd, gzip, lz4. */
+#define OXH_SNAPPY_PREAMBLE 1
+#define OXH_SNAPPY_INPUT 2
+#define OXH_SNAPPY_OFFSET_ZERO 3
+#define OXH_SNAPPY_OFFSET_BEYOND 4
+#define OXH_SNAPPY_OVERRUN 5
+#define OXH_SNAPPY_TRUNCATED 6
+#define OXH_SNAPPY_RANGE 7
+int oxh_snappy_inflate_device(oxh_ctx* ctx, uint64_t nblocks, const uint8_t* d_src, const uint64_t* d_src_offsets, uint8_t* d_dst,
+                              const uint64_t* d_dst_offsets, uint32_t* d_status, uint64_t* bad_blocks, void* stream);
+int oxh_snappy_inflate_host(oxh_ctx* ctx, uint64_t nblocks, const uint8_t* src, const uint64_t* src_offsets, uint8_t* dst,
+                            const uint64_t* dst_offsets, uint32_t* status, uint64_t* bad_blocks);
 
 /* ---------------------------------------------------------------- K2: merkle parent nodes */
 /* get_combined_hash (hasher.rs:67-80) x n on the device:

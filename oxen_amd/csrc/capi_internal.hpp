@@ -65,6 +65,9 @@
 //                      the host (parquet_read_host.hpp, parquet_bits.hpp), a lane per chunk chasing page headers, a wave
 //                      per page for the levels' and indices' hybrid runs, a lane per output row for the gather, the
 //                      strings' length chain through LDS windows
+//   snappy_inflate.hip many raw Snappy blocks inflated per launch (oxh_snappy_inflate_*; the Parquet open's SNAPPY pages):
+//                      a wave per block, the input through 1 KiB LDS windows, one lane chasing the tags into 64 cells,
+//                      the wave executing them -- literals first, copies in rounds picked by a ballot
 // There is no CPU hashing path: every digest this library returns was computed on the GPU.
 #pragma once
 
@@ -179,6 +182,16 @@ namespace oxh {
 // first occurrences (group_rows.hip), the filter's per-block counts (filter_rows.hip).
 uint64_t scan_tiles(uint64_t n);
 int exclusive_scan_u32(const uint32_t* d_in, uint64_t n, uint64_t* d_out, unsigned long long* d_sums, hipStream_t st);
+}  // namespace oxh
+
+// ---------------------------------------------------------------- batched Snappy inflate (snappy_inflate.hip)
+namespace oxh {
+// Block b of nblocks > 0: d_src[d_src_lo[b], d_src_hi[b]) inflates to d_dst[d_dst_lo[b], d_dst_hi[b]), whose length is
+// the block's expected one; d_status[b] = 0 or its OXH_SNAPPY_* cause (its destination is then zeros); *d_bad (one
+// device word) = the blocks with a cause. Enqueued on `st` (two launches). Callers: oxh_snappy_inflate_*
+// (capi_dispatch.hip), the Parquet open (parquet_read.hip).
+int snappy_inflate_enqueue(const uint8_t* d_src, const uint64_t* d_src_lo, const uint64_t* d_src_hi, uint8_t* d_dst, const uint64_t* d_dst_lo,
+                           const uint64_t* d_dst_hi, uint32_t* d_status, uint64_t nblocks, unsigned long long* d_bad, hipStream_t st);
 }  // namespace oxh
 
 // ---------------------------------------------------------------- runs of equal neighbours in a wave

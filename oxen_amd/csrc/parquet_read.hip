@@ -1,4 +1,4 @@
-// oxen_amd/csrc/parquet_read.hip -- the bytes of an uncompressed, flat Parquet file in HBM to a page index and to
+// oxen_amd/csrc/parquet_read.hip -- the bytes of an uncompressed or SNAPPY, flat Parquet file in HBM to a page index and to
 // typed Arrow columns (oxh_parquet_*): what read_df_parquet / scan_parquet (core/df/tabular.rs:111, :172) are for.
 // The format and the refusals are stated in include/oxen_hash.h "Parquet: the file's bytes"; the varint, the Thrift
 // reader, the PageHeader, the hybrid's run header and the bit extraction are parquet_bits.hpp's, the code
@@ -9,6 +9,11 @@
 // chunk's PageHeaders -- each is found only from the one before -- first counting, then filling one fixed record per
 // page. The table comes down; the host checks it and lists every column's data and dictionary pages with their row
 // and word bases (a prefix over the table), which is all the column kernels read of the file's structure.
+// With OXH_PARQUET_INFLATE the walk also takes the pages of SNAPPY chunks, whose sizes differ; between the table's
+// checks and the page lists, inflate_pages gives every compressed page a place in an image the handle owns, copies a
+// V2 page's stored levels there (pq_stored_kernel), inflates the rest (snappy_inflate.hip, the kernel of
+// oxh_snappy_inflate_*) and reads the V1 pages' level lengths out of the inflated bodies (pq_level_length_kernel). A
+// page's body is from then on in the file or in the image: pq_body / pq_at are the column kernels' only way to it.
 // Columns, per selected column, on one stream (launches order the steps, no workgroup waits for another):
 //   levels   pq_levels_kernel, a wave per data page of an OPTIONAL column: the run headers are chased by the whole
 //            wave (uniform control flow, every lane reads the same header), a run's bits are expanded by the 64 lanes
@@ -49,6 +54,7 @@ constexpr uint32_t kLongCell = csv::kLongCell;
 // What the column kernels read of one column.
 struct PqColumn {
     const uint8_t* bytes;
+    const uint8_t* image;  // the inflated bodies of the compressed pages (NULL: the file has none)
     const pqr::DataPage* pages;
     const pqr::DictPage* dicts;
     uint64_t nrows;
@@ -60,6 +66,19 @@ struct PqColumn {
     uint32_t *cell_at, *cell_len;  // PLAIN byte arrays: at row0 + rank, the cell in its page's body
     uint32_t *dict_at, *dict_len;  // per dictionary entry: the cell in its page's body
 };
+
+// Where a page's body starts: in the file, or in the image once inflated.
+template <class Page>
+__device__ __forceinline__ const uint8_t* pq_body(const PqColumn& c, const Page& pg) {
+    return (pg.in_image ? c.image : c.bytes) + pg.body;
+}
+// The same for a place the length pass hands to the copy: the top bit says the image.
+constexpr uint64_t kPqInImage = 1ull << 63;
+template <class Page>
+__device__ __forceinline__ uint64_t pq_place(const Page& pg, uint64_t at) { return (pg.body + at) | (pg.in_image ? kPqInImage : 0); }
+__device__ __forceinline__ const uint8_t* pq_at(const PqColumn& c, uint64_t place) {
+    return (place & kPqInImage ? c.image : c.bytes) + (place & ~kPqInImage);
+}
 
 __device__ __forceinline__ void pq_wave_lds_order() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -87,28 +106,40 @@ __global__ __launch_bounds__(64) void pq_walk_kernel(const uint8_t* __restrict__
         while (pos < c.bytes && seen < c.num_values) {
             pqr::Span s{bytes + c.at + pos, c.bytes - pos, 0, false};
             pqr::PageInfo h;
-            if (!pqr::page_header(s, h, skip_words[threadIdx.x]) || h.csize < 0 || h.usize < 0 || h.num_values < 0 || (uint64_t)h.csize > s.n - s.at || h.csize != h.usize) {
+            if (!pqr::page_header(s, h, skip_words[threadIdx.x]) || h.csize < 0 || h.usize < 0 || h.num_values < 0 || (uint64_t)h.csize > s.n - s.at) {
                 bad = true;
                 break;
             }
             const uint64_t body = pos + s.at;
             const bool data = h.type == pqr::kPageData || h.type == pqr::kPageDataV2;
-            pqr::PageRec r{c.at + body, (uint32_t)h.csize, (uint32_t)h.type, (uint32_t)h.num_values, (uint32_t)h.encoding, 0, 0, 0, 0};
+            // a SNAPPY chunk compresses every page this reader reads, but a V2 page that says it is stored
+            const bool packed = c.codec == pqr::kCodecSnappy && (h.type == pqr::kPageData || h.type == pqr::kPageDict || (h.type == pqr::kPageDataV2 && h.is_compressed));
+            if (!packed && h.csize != h.usize && (data || h.type == pqr::kPageDict || c.codec == pqr::kCodecNone)) {
+                bad = true;
+                break;
+            }
+            const uint32_t size = (uint32_t)(packed ? h.usize : h.csize);  // of the body the column kernels read
+            pqr::PageRec r{c.at + body, size, (uint32_t)h.type, (uint32_t)h.num_values, (uint32_t)h.encoding, 0, 0, 0, packed ? pqr::kPageInImage : 0u,
+                           (uint32_t)h.csize, 0};
             if (h.type == pqr::kPageData && c.optional) {  // V1: the levels' 4-byte length leads the body
-                if (h.csize < 4) {
+                if (size < 4) {
                     bad = true;
                     break;
                 }
-                r.def_at = 4, r.def_bytes = pqr::le32(bytes + c.at + body);
-                r.values_at = r.def_bytes <= (uint32_t)h.csize - 4 ? 4 + r.def_bytes : ~0u;  // the host refuses it
+                if (packed)
+                    r.flags |= pqr::kPageLevelsLater;  // the inflated body's: the open finishes the record
+                else
+                    pqr::finish_v1_levels(r, pqr::le32(bytes + c.at + body));
                 if (h.def_enc != pqr::kEncRle) r.flags |= 2;
             } else if (h.type == pqr::kPageDataV2) {
                 if (h.rep_len < 0 || h.def_len < 0) {
                     bad = true;
                     break;
                 }
+                const uint64_t levels = (uint64_t)h.rep_len + (uint64_t)h.def_len;
                 r.def_at = (uint32_t)h.rep_len, r.def_bytes = c.optional ? (uint32_t)h.def_len : 0;
-                r.values_at = (uint64_t)h.rep_len + (uint64_t)h.def_len <= (uint64_t)h.csize ? (uint32_t)(h.rep_len + h.def_len) : ~0u;
+                r.values_at = levels <= (uint64_t)h.csize && levels <= size ? (uint32_t)levels : ~0u;  // the host refuses it
+                if (packed) r.stored = r.values_at != ~0u ? (uint32_t)levels : 0;
                 if (h.rep_len) r.flags |= 1;
             }
             if (FILL) {
@@ -162,7 +193,7 @@ __global__ __launch_bounds__(256) void pq_levels_kernel(const PqColumn c, unsign
         const uint64_t n = pg.num_values, nwords = (n + 63) / 64;
         uint64_t* words = c.words + pg.word0;
         uint32_t* prefix = c.prefix + pg.word0;
-        pqr::Span s{c.bytes + pg.body + pg.def_at, pg.def_bytes, 0, false};
+        pqr::Span s{pq_body(c, pg) + pg.def_at, pg.def_bytes, 0, false};
         uint64_t pos = 0, acc = 0;
         uint32_t running = 0;
         bool ok = true;
@@ -211,7 +242,7 @@ __global__ __launch_bounds__(256) void pq_index_kernel(const PqColumn c, unsigne
         const bool dict = pg.dict != ~0u;
         if (!dict && pg.encoding != (uint32_t)pqr::kEncRle) continue;
         const uint64_t nvalid = c.optional ? c.page_valid[p] : pg.num_values;
-        const uint8_t* v = c.bytes + pg.body + pg.values_at;
+        const uint8_t* v = pq_body(c, pg) + pg.values_at;
         const uint64_t nb = pg.body_size - pg.values_at;
         uint32_t* out = c.idx + pg.row0;
         pqr::Span s{v, 0, 0, false};
@@ -264,11 +295,11 @@ __device__ __forceinline__ const uint8_t* pq_fixed_source(const PqColumn& c, con
         const pqr::DictPage& d = c.dicts[pg.dict];
         const uint64_t k = c.idx[pg.row0 + rank];
         if ((k + 1) * W > d.body_size) return bad = true, nullptr;
-        return c.bytes + d.body + k * W;
+        return pq_body(c, d) + k * W;
     }
     const uint64_t at = (uint64_t)pg.values_at + (uint64_t)rank * W;
     if (at + W > pg.body_size) return bad = true, nullptr;
-    return c.bytes + pg.body + at;
+    return pq_body(c, pg) + at;
 }
 
 // SRC: the bytes of a value in the file; DST: of a cell of `values`; a 4 -> 8 store sign-extends an integer and
@@ -329,7 +360,7 @@ __global__ __launch_bounds__(256) void pq_bool_kernel(const PqColumn c, uint8_t*
             } else if (valid) {
                 const uint64_t at = (uint64_t)pg.values_at + (rank >> 3);
                 if (at < pg.body_size)
-                    truth = (c.bytes[pg.body + at] >> (rank & 7)) & 1;
+                    truth = (pq_body(c, pg)[at] >> (rank & 7)) & 1;
                 else
                     bad = true;
             }
@@ -357,12 +388,12 @@ __global__ __launch_bounds__(256) void pq_chase_kernel(const PqColumn c, unsigne
         uint32_t *out_at, *out_len;
         if (DICT) {
             const pqr::DictPage d = c.dicts[p];
-            body = c.bytes + d.body, first = 0, nb = d.body_size, count = d.num_values;
+            body = pq_body(c, d), first = 0, nb = d.body_size, count = d.num_values;
             out_at = c.dict_at + d.entry0, out_len = c.dict_len + d.entry0;
         } else {
             const pqr::DataPage pg = c.pages[p];
             if (pg.dict != ~0u) continue;
-            body = c.bytes + pg.body, first = pg.values_at, nb = pg.body_size, count = c.optional ? c.page_valid[p] : pg.num_values;
+            body = pq_body(c, pg), first = pg.values_at, nb = pg.body_size, count = c.optional ? c.page_valid[p] : pg.num_values;
             out_at = c.cell_at + pg.row0, out_len = c.cell_len + pg.row0;
         }
         uint64_t cur = first, done = 0;  // the same in every lane
@@ -427,11 +458,11 @@ __global__ __launch_bounds__(256) void pq_strlen_kernel(const PqColumn c, uint32
                 const pqr::DictPage& d = c.dicts[pg.dict];
                 const uint32_t k = c.idx[pg.row0 + rank];
                 if (k < d.num_values)
-                    len = c.dict_len[d.entry0 + k], from = d.body + c.dict_at[d.entry0 + k];
+                    len = c.dict_len[d.entry0 + k], from = pq_place(d, c.dict_at[d.entry0 + k]);
                 else
                     bad = true;  // an empty dictionary
             } else if (valid) {
-                len = c.cell_len[pg.row0 + rank], from = pg.body + c.cell_at[pg.row0 + rank];
+                len = c.cell_len[pg.row0 + rank], from = pq_place(pg, c.cell_at[pg.row0 + rank]);
             }
             if (lens) lens[i] = len, src[i] = from;
         }
@@ -469,17 +500,34 @@ __global__ __launch_bounds__(256) void pq_strcopy_kernel(const PqColumn c, const
             }
         }
         const bool is_long = len >= pqr::kLongCell;
-        if (len && !is_long) copy_span_lane(values + at, c.bytes + from, len);
+        if (len && !is_long) copy_span_lane(values + at, pq_at(c, from), len);
         unsigned long long todo = __ballot(is_long);
         while (todo) {  // uniform in the wave
             const int who = __builtin_ctzll(todo);
             todo &= todo - 1;
-            const uint8_t* p = c.bytes + (uint64_t)__shfl((long long)from, who, 64);
+            const uint8_t* p = pq_at(c, (uint64_t)__shfl((long long)from, who, 64));
             uint8_t* d = values + (uint64_t)__shfl((long long)at, who, 64);
             copy_span_wave(d, p, __shfl(len, who, 64), lane);
         }
     }
     if (bad) __hip_atomic_fetch_or(&ctrl[pqr::kColErr], bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ---------------------------------------------------------------- open: the compressed pages
+// A wave per compressed V2 page: its levels, stored as they are in front of the compressed values, to the front of
+// its body in the image. jobs[3 j ..] = {where in the file, where in the image, bytes}.
+__global__ __launch_bounds__(256) void pq_stored_kernel(const uint8_t* __restrict__ bytes, uint8_t* __restrict__ image, const uint64_t* __restrict__ jobs,
+                                                        uint64_t njobs) {
+    const unsigned lane = threadIdx.x & 63;
+    for (uint64_t j = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); j < njobs; j += (uint64_t)gridDim.x * 4)
+        copy_span_wave(image + jobs[3 * j + 1], bytes + jobs[3 * j], jobs[3 * j + 2], lane);
+}
+
+// A lane per compressed V1 page of an OPTIONAL column: out[j] = the first 4 bytes of its inflated body, the
+// levels' length. at[j]: the body in the image (at least 4 bytes: the walk checked).
+__global__ __launch_bounds__(256) void pq_level_length_kernel(const uint8_t* __restrict__ image, const uint64_t* __restrict__ at, uint64_t n,
+                                                              uint32_t* __restrict__ out) {
+    for (uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += (uint64_t)gridDim.x * 256) out[j] = pqr::le32(image + at[j]);
 }
 
 // Device words to zero (a captured graph takes no memset; neither does this file).
@@ -503,6 +551,8 @@ struct ParquetHandle {
     int device = 0;
     const uint8_t* d_bytes = nullptr;
     uint8_t* owned = nullptr;  // the host form's device copy
+    uint8_t* image = nullptr;  // the inflated bodies of every compressed page, until close
+    uint64_t image_bytes = 0, pages_inflated = 0;
     uint64_t nbytes = 0;
     pqr::Footer footer;
     std::vector<pqr::ColumnPages> columns;  // per column; `cause` where the reader cannot read it
@@ -512,6 +562,7 @@ struct ParquetHandle {
     ~ParquetHandle() {
         magic = 0;
         if (owned) (void)hipFree(owned);
+        if (image) (void)hipFree(image);
     }
     uint64_t nrows() const { return footer.nrows; }
     uint64_t ncols() const { return footer.leaves.size(); }
@@ -546,6 +597,103 @@ void take_footer(ParquetHandle& h, pqr::Footer&& f) {
     }
 }
 
+const char* snappy_cause(uint32_t code) {
+    static const char* names[] = {"", "its preamble is not the page's uncompressed size", "a tag or a literal leaves the page", "a copy with offset 0",
+                                  "a copy from in front of the page's first byte", "an element passes the page's uncompressed size",
+                                  "the stream ends before the page's uncompressed size", "its range is not one"};
+    return code < 8 ? names[code] : "an unknown cause";
+}
+
+// Every compressed page of the table inflated into an image the handle owns, and the records that need the inflated
+// body finished: a record's body is then its place in the image. `lease`: the open's, whose walk is over.
+int inflate_pages(ParquetHandle& h, const std::vector<pqr::ChunkDesc>& chunks, const std::vector<uint32_t>& counts, std::vector<pqr::PageRec>& recs,
+                  oxh::ScratchLease& lease, hipStream_t st) {
+    using namespace oxh;
+    const uint64_t ncols = h.ncols();
+    auto where = [&](uint64_t page) {  // the chunk of a record
+        uint64_t ch = 0;
+        while (ch + 1 < chunks.size() && !(chunks[ch].page0 <= page && page - chunks[ch].page0 < counts[ch])) ++ch;
+        return "row group " + std::to_string(ch / ncols) + ", column '" + h.footer.leaves[ch % ncols].name + "'";
+    };
+    const pqr::ImagePlan plan = pqr::plan_image(recs);
+    if (plan.implausible != ~0ull) {
+        const pqr::PageRec& r = recs[plan.implausible];
+        return fail(OXH_ERR_INVALID, "parquet open: " + where(plan.implausible) + ": a page of " + std::to_string(r.file_size) + " compressed bytes claims " +
+                                         std::to_string(r.body_size) + " uncompressed ones, more than any Snappy stream gives (22 x + 32)");
+    }
+    if (!plan.pages) return OXH_OK;
+    // the blocks, the stored levels and the V1 pages whose level length is in the inflated body
+    std::vector<uint64_t> tables, stored, later;
+    std::vector<uint64_t> block_page;
+    for (size_t k = 0; k < recs.size(); ++k) {
+        const pqr::PageRec& r = recs[k];
+        if (!(r.flags & pqr::kPageInImage)) continue;
+        block_page.push_back(k);
+        if (r.stored) stored.insert(stored.end(), {r.body, plan.places[k], (uint64_t)r.stored});
+        if (r.flags & pqr::kPageLevelsLater) later.push_back(plan.places[k]);
+    }
+    const uint64_t nb = block_page.size(), nstored = stored.size() / 3, nlater = later.size();
+    tables.resize(4 * nb);  // src_lo | src_hi | dst_lo | dst_hi
+    for (uint64_t j = 0; j < nb; ++j) {
+        const pqr::PageRec& r = recs[block_page[j]];
+        tables[j] = r.body + r.stored, tables[nb + j] = r.body + r.file_size;
+        tables[2 * nb + j] = plan.places[block_page[j]] + r.stored, tables[3 * nb + j] = plan.places[block_page[j]] + r.body_size;
+    }
+    if (hipMalloc(&h.image, plan.bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        h.image = nullptr;
+        return fail(OXH_ERR_NOMEM, "parquet open: " + std::to_string(plan.bytes) + " B for the inflated pages on the device");
+    }
+    h.image_bytes = plan.bytes;
+    poison_device(h.image, plan.bytes, st);
+    csv::Carver carve;
+    const uint64_t at_bad = carve(8), at_tables = carve(tables.size() * 8), at_status = carve(nb * 4), at_stored = carve(stored.size() * 8),
+                   at_later = carve(nlater * 8), at_lengths = carve(nlater * 4);
+    void* lbase = nullptr;
+    if (lease.get(carve.at, &lbase) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(OXH_ERR_NOMEM, "parquet open: " + std::to_string(carve.at) + " B of block tables for the inflation");
+    }
+    uint8_t* b = (uint8_t*)lbase;
+    const uint64_t* d_tables = (const uint64_t*)(b + at_tables);
+    std::vector<uint32_t> status(nb), lengths(nlater);
+    unsigned long long bad = 0;
+    int rc = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(b + at_tables, tables.data(), tables.size() * 8, hipMemcpyHostToDevice, st));
+        if (nstored) {
+            HIP_TRY(hipMemcpyAsync(b + at_stored, stored.data(), stored.size() * 8, hipMemcpyHostToDevice, st));
+            pq_stored_kernel<<<wave_grid(nstored), 256, 0, st>>>(h.d_bytes, h.image, (const uint64_t*)(b + at_stored), nstored);
+            HIP_TRY(hipGetLastError());
+        }
+        int r = snappy_inflate_enqueue(h.d_bytes, d_tables, d_tables + nb, h.image, d_tables + 2 * nb, d_tables + 3 * nb, (uint32_t*)(b + at_status), nb,
+                                       (unsigned long long*)(b + at_bad), st);
+        if (r) return r;
+        if (nlater) {
+            HIP_TRY(hipMemcpyAsync(b + at_later, later.data(), nlater * 8, hipMemcpyHostToDevice, st));
+            pq_level_length_kernel<<<row_grid(nlater), 256, 0, st>>>(h.image, (const uint64_t*)(b + at_later), nlater, (uint32_t*)(b + at_lengths));
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(lengths.data(), b + at_lengths, nlater * 4, hipMemcpyDeviceToHost, st));
+        }
+        HIP_TRY(hipMemcpyAsync(status.data(), b + at_status, nb * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&bad, b + at_bad, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return OXH_OK;
+    }();
+    if (rc != OXH_OK) return (void)hipStreamSynchronize(st), rc;
+    for (uint64_t j = 0; j < nb; ++j)
+        if (status[j])
+            return fail(OXH_ERR_INVALID, "parquet open: " + where(block_page[j]) + ": a page's Snappy stream is malformed: " + snappy_cause(status[j]));
+    if (bad) return fail(OXH_ERR_HIP, "parquet open: the inflation counts a malformed page and names none");
+    uint64_t nth = 0;
+    for (uint64_t j = 0; j < nb; ++j) {
+        pqr::PageRec& r = recs[block_page[j]];
+        r.body = plan.places[block_page[j]];
+        if (r.flags & pqr::kPageLevelsLater) pqr::finish_v1_levels(r, lengths[nth++]);
+    }
+    h.pages_inflated = nb;
+    return OXH_OK;
+}
+
 // The page walk over h->d_bytes and every column's page lists; stats8 is filled on success.
 int open_run(ParquetHandle& h, uint64_t* stats8, hipStream_t st) {
     using namespace oxh;
@@ -553,7 +701,7 @@ int open_run(ParquetHandle& h, uint64_t* stats8, hipStream_t st) {
     const uint64_t ncols = h.ncols(), nchunks = f.chunks.size();
     std::vector<pqr::ChunkDesc> chunks(nchunks);
     for (uint64_t k = 0; k < nchunks; ++k)
-        chunks[k] = pqr::ChunkDesc{f.chunks[k].at, f.chunks[k].bytes, f.chunks[k].num_values, f.leaves[k % ncols].required ? 0u : 1u, 0};
+        chunks[k] = pqr::ChunkDesc{f.chunks[k].at, f.chunks[k].bytes, f.chunks[k].num_values, f.leaves[k % ncols].required ? 0u : 1u, 0, f.chunks[k].codec, 0};
     std::vector<uint32_t> counts(nchunks, 0);
     std::vector<pqr::PageRec> recs;
     if (nchunks) {
@@ -609,16 +757,18 @@ int open_run(ParquetHandle& h, uint64_t* stats8, hipStream_t st) {
         if (err) {
             const uint64_t ch = std::min<uint64_t>(err, nchunks) - 1;  // the last chunk that failed
             return fail(OXH_ERR_INVALID, "parquet open: row group " + std::to_string(ch / ncols) + ", column '" + f.leaves[ch % ncols].name +
-                                             "': a page header runs past its chunk, has negative or unequal sizes, or the pages' values are not the chunk's num_values");
+                                             "': a page header runs past its chunk, has negative sizes or unequal ones on a page that is not compressed, or the pages' values are not the chunk's num_values");
         }
         // a record names bytes of its own chunk only (the kernel checked; the table is what the column kernels trust)
         for (uint64_t k = 0; k < nchunks; ++k)
             for (uint32_t j = 0; j < counts[k]; ++j) {
                 const pqr::PageRec& r = recs[chunks[k].page0 + j];
-                if (r.body < chunks[k].at || r.body - chunks[k].at > chunks[k].bytes || r.body_size > chunks[k].bytes - (r.body - chunks[k].at) ||
-                    r.body_size > pqr::kMaxPage)
+                if (r.body < chunks[k].at || r.body - chunks[k].at > chunks[k].bytes || r.file_size > chunks[k].bytes - (r.body - chunks[k].at) ||
+                    r.body_size > pqr::kMaxPage || (!(r.flags & pqr::kPageInImage) && r.body_size != r.file_size))
                     return fail(OXH_ERR_HIP, "parquet open: a page record is not inside its chunk (did the buffer change during the call?)");
             }
+        rc = inflate_pages(h, chunks, counts, recs, lease, st);
+        if (rc) return rc;
     }
     uint64_t unreadable = 0;
     h.columns.resize(ncols);
@@ -631,7 +781,7 @@ int open_run(ParquetHandle& h, uint64_t* stats8, hipStream_t st) {
     }
     for (const pqr::PageRec& r : recs) (r.kind == (uint32_t)pqr::kPageDict ? h.dict_pages : h.data_pages) += 1;
     stats8[0] = f.nrows, stats8[1] = ncols, stats8[2] = f.group_rows.size(), stats8[3] = h.data_pages, stats8[4] = h.dict_pages;
-    stats8[5] = f.footer_bytes, stats8[6] = unreadable, stats8[7] = 0;
+    stats8[5] = f.footer_bytes, stats8[6] = unreadable, stats8[7] = h.pages_inflated;
     STEP("parquet open: %llu B, %llu rows x %llu columns, %llu pages", (unsigned long long)h.nbytes, (unsigned long long)f.nrows,
          (unsigned long long)ncols, (unsigned long long)recs.size());
     return OXH_OK;
@@ -693,7 +843,7 @@ int columns_device(ParquetHandle& h, const Selection& s, bool write, void* const
             const pqr::ColumnPages& cp = h.columns[col];
             const pqr::Leaf& leaf = h.footer.leaves[col];
             unsigned long long* c = d_ctrl + (size_t)k * pqr::kColWords;
-            PqColumn v{h.d_bytes, (const pqr::DataPage*)(b + at.pages), (const pqr::DictPage*)(b + at.dicts), n, (uint32_t)cp.data.size(),
+            PqColumn v{h.d_bytes, h.image, (const pqr::DataPage*)(b + at.pages), (const pqr::DictPage*)(b + at.dicts), n, (uint32_t)cp.data.size(),
                        (uint32_t)cp.dicts.size(), leaf.required ? 0u : 1u, (uint64_t*)(b + at.words), (uint32_t*)(b + at.prefix),
                        (uint32_t*)(b + at.page_valid), (uint32_t*)(b + at.idx), (uint32_t*)(b + at.cell_at), (uint32_t*)(b + at.cell_len),
                        (uint32_t*)(b + at.dict_at), (uint32_t*)(b + at.dict_len)};
@@ -818,7 +968,7 @@ int columns_run(ParquetHandle& h, const csv::ColumnsArgs& a, void* const* d_valu
     return OXH_OK;
 }
 
-int open_args(const uint8_t* bytes, uint64_t nbytes, uint32_t flags, void** out, uint64_t* stats8) {
+int open_args(const uint8_t* bytes, uint64_t nbytes, uint32_t flags, void* const* out, const uint64_t* stats8) {
     const std::string what = pqr::open_error(bytes, nbytes, flags, out, stats8);
     return what.empty() ? OXH_OK : fail(OXH_ERR_INVALID, "parquet open: " + what);
 }
@@ -853,7 +1003,7 @@ int oxh_parquet_open_device(oxh_ctx* ctx, const uint8_t* d_bytes, uint64_t nbyte
         HIP_TRY(hipMemcpyAsync(meta.data(), d_bytes + at, len, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
-    pqr::Footer f = pqr::read_footer(meta.data(), len, at, nbytes);
+    pqr::Footer f = pqr::read_footer(meta.data(), len, at, nbytes, flags & OXH_PARQUET_INFLATE);
     if (!f.error.empty()) return fail(OXH_ERR_INVALID, "parquet open: " + f.error);
     take_footer(*h, std::move(f));
     uint64_t stats[8] = {};
@@ -871,7 +1021,7 @@ int oxh_parquet_open_host(oxh_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, u
     const uint8_t none[8] = {};
     const std::string what = pqr::footer_place(nbytes >= 12 ? bytes : none, nbytes >= 12 ? bytes + nbytes - 8 : none, nbytes, at, len);
     if (!what.empty()) return fail(OXH_ERR_INVALID, "parquet open: " + what);
-    pqr::Footer f = pqr::read_footer(bytes + at, len, at, nbytes);
+    pqr::Footer f = pqr::read_footer(bytes + at, len, at, nbytes, flags & OXH_PARQUET_INFLATE);
     if (!f.error.empty()) return fail(OXH_ERR_INVALID, "parquet open: " + f.error);
     if ((rc = device_enter(ctx))) return rc;
     hipStream_t st = ctx->stream;
@@ -899,7 +1049,7 @@ int oxh_parquet_close(void* parquet) {
     if (!parquet) return OXH_OK;
     ParquetHandle* h = handle_of(parquet);
     if (!h) return fail(OXH_ERR_INVALID, "parquet close: not a Parquet handle");
-    if (h->owned) (void)hipSetDevice(h->device);
+    if (h->owned || h->image) (void)hipSetDevice(h->device);
     delete h;
     return OXH_OK;
 }

@@ -52,7 +52,13 @@ struct Leaf {
 
 struct Chunk {
     uint64_t at = 0, bytes = 0, num_values = 0;
+    uint32_t codec = 0;  // kCodecNone, or with OXH_PARQUET_INFLATE kCodecSnappy
 };
+constexpr uint32_t kCodecNone = 0, kCodecSnappy = 1;
+
+// No Snappy stream expands more than 64 / 3 (a 3-byte copy gives 64 bytes); the preamble and a short last element
+// are the 32. A page that claims more is refused before anything is allocated for it.
+inline bool inflated_size_plausible(uint64_t csize, uint64_t usize) { return usize <= 22 * csize + 32; }
 
 struct Footer {
     std::vector<Leaf> leaves;
@@ -64,7 +70,7 @@ struct Footer {
 
 // "" when oxh_parquet_open_*'s arguments are well formed.
 inline std::string open_error(const uint8_t* bytes, uint64_t nbytes, uint32_t flags, void* const* out, const uint64_t* stats8) {
-    if (flags) return "unknown flags";
+    if (flags & ~(uint32_t)OXH_PARQUET_INFLATE) return "unknown flags";
     if (nbytes && !bytes) return "bytes is NULL";
     if (!out) return "out is NULL";
     if (!stats8) return "stats8 is NULL";
@@ -162,9 +168,10 @@ inline ChunkMeta column_chunk(Span& s) {
 // Refusals, in this order: a footer that is no FileMetaData; an encrypted footer; a schema without a root or whose
 // elements are not the root's children (a nested field, named); a repeated field; more than 2^40 rows; and per
 // row group, in order: a column count that is not the schema's, a chunk without metadata or with encrypted
-// metadata, a codec other than UNCOMPRESSED (its number named), a chunk outside the file's pages, a num_values
-// that is not the group's rows; then group rows that do not sum to num_rows.
-inline Footer read_footer(const uint8_t* meta, uint64_t len, uint64_t meta_at, uint64_t nbytes) {
+// metadata, a codec other than UNCOMPRESSED -- with `inflate` (OXH_PARQUET_INFLATE) other than that and SNAPPY -- (its
+// number named), a chunk outside the file's pages, a num_values that is not the group's rows; then group rows that do
+// not sum to num_rows.
+inline Footer read_footer(const uint8_t* meta, uint64_t len, uint64_t meta_at, uint64_t nbytes, bool inflate = false) {
     using namespace detail;
     Footer f;
     uint64_t st[kSkipDepth];
@@ -245,14 +252,17 @@ inline Footer read_footer(const uint8_t* meta, uint64_t len, uint64_t meta_at, u
             const ChunkMeta& m = groups[g][c];
             const std::string col = where + ", column '" + f.leaves[c].name + "'";
             if (!m.has_meta || m.encrypted) return f.error = col + ": its chunk has no plain metadata in the footer", f;
-            if (m.codec != 0) return f.error = col + ": compression codec " + std::to_string(m.codec) + " (only UNCOMPRESSED, 0, is read on the device)", f;
+            if (m.codec != kCodecNone && !(inflate && m.codec == kCodecSnappy))
+                return f.error = col + ": compression codec " + std::to_string(m.codec) +
+                                 (inflate ? " (UNCOMPRESSED, 0, and SNAPPY, 1, are read on the device)"
+                                          : " (only UNCOMPRESSED, 0, is read on the device; OXH_PARQUET_INFLATE adds SNAPPY, 1)"), f;
             const int64_t first = m.dict_at > 0 && m.dict_at < m.data_at ? m.dict_at : m.data_at;
             if (first < 4 || m.compressed < 0 || (uint64_t)first > meta_at || (uint64_t)m.compressed > meta_at - (uint64_t)first)
                 return f.error = col + ": its chunk (" + std::to_string(m.compressed) + " bytes at " + std::to_string(first) + ") is not inside the file's " +
                                  std::to_string(nbytes) + " bytes in front of the footer", f;
             if (m.num_values != group_rows[g])
                 return f.error = col + ": num_values " + std::to_string(m.num_values) + " is not the group's " + std::to_string(group_rows[g]) + " rows", f;
-            f.chunks.push_back(Chunk{(uint64_t)first, (uint64_t)m.compressed, (uint64_t)m.num_values});
+            f.chunks.push_back(Chunk{(uint64_t)first, (uint64_t)m.compressed, (uint64_t)m.num_values, (uint32_t)m.codec});
         }
         f.group_rows.push_back((uint64_t)group_rows[g]);
         sum += (uint64_t)group_rows[g];
@@ -266,14 +276,46 @@ inline Footer read_footer(const uint8_t* meta, uint64_t len, uint64_t meta_at, u
 struct ChunkDesc {
     uint64_t at, bytes, num_values;
     uint32_t optional, page0;  // page0: where its records start in the table (the fill pass)
+    uint32_t codec, pad;
 };
 
 struct PageRec {
-    uint64_t body;  // where the page's body starts in the file
-    uint32_t body_size, kind, num_values, encoding;
+    uint64_t body;  // where the page's body starts in the file; once inflated (kPageInImage), in the handle's image
+    uint32_t body_size, kind, num_values, encoding;  // body_size: of the body the column kernels read (the inflated one)
     uint32_t def_at, def_bytes, values_at;  // in the body: the definition levels' runs, then the values
-    uint32_t flags;                         // bit 0: repetition levels, bit 1: a V1 level encoding that is not RLE
+    uint32_t flags;                         // bit 0: repetition levels, bit 1: a V1 level encoding that is not RLE, kPage*
+    uint32_t file_size, stored;             // the body's bytes in the file; of those, a V2 page's levels, stored as they are
 };
+constexpr uint32_t kPageInImage = 4;      // a compressed page: its body is inflated into the image
+constexpr uint32_t kPageLevelsLater = 8;  // a compressed V1 page of an OPTIONAL column: its levels' length is in the inflated body
+
+// A compressed V1 page's levels, once the first 4 bytes of its inflated body (`def_bytes`) are known: what the walk
+// leaves of a page that is not compressed.
+OXH_PQR_BOTH void finish_v1_levels(PageRec& r, uint32_t def_bytes) {
+    r.def_at = 4, r.def_bytes = def_bytes;
+    r.values_at = r.body_size >= 4 && def_bytes <= r.body_size - 4 ? 4 + def_bytes : ~0u;  // ~0u: column_pages refuses it
+    r.flags &= ~kPageLevelsLater;
+}
+
+// The image of the compressed pages: each inflated body in table order on a 16-byte grid. places[k]: where page k's
+// body starts in it (compressed pages only). A page whose claimed size no Snappy stream reaches stops the plan:
+// `implausible` is that page, else ~0.
+struct ImagePlan {
+    std::vector<uint64_t> places;
+    uint64_t bytes = 0, pages = 0, implausible = ~0ull;
+};
+inline ImagePlan plan_image(const std::vector<PageRec>& recs) {
+    ImagePlan plan;
+    plan.places.assign(recs.size(), 0);
+    for (size_t k = 0; k < recs.size(); ++k) {
+        const PageRec& r = recs[k];
+        if (!(r.flags & kPageInImage)) continue;
+        if (r.stored > r.file_size || r.stored > r.body_size || !inflated_size_plausible(r.file_size - r.stored, r.body_size - r.stored))
+            return plan.implausible = k, plan;
+        plan.places[k] = plan.bytes, plan.bytes += ((uint64_t)r.body_size + 15) & ~15ull, ++plan.pages;
+    }
+    return plan;
+}
 
 // What the column kernels read per data page and per dictionary page of one column.
 struct DataPage {
@@ -281,11 +323,12 @@ struct DataPage {
     uint64_t body;
     uint32_t num_values, body_size, def_at, def_bytes, values_at, encoding;
     uint32_t dict;         // its chunk's dictionary page in the column's list, ~0u: none
-    uint32_t pad;
+    uint32_t in_image;     // its body is at `body` of the handle's image, not of the file
 };
 struct DictPage {
     uint64_t body, entry0;  // entry0: its first entry in the column's dictionary tables
     uint32_t body_size, num_values;
+    uint32_t in_image, pad;
 };
 
 struct ColumnPages {
@@ -318,7 +361,7 @@ inline ColumnPages column_pages(const Footer& f, uint64_t c, const std::vector<C
                     return out.cause = where + ": dictionary encoding " + std::to_string(r.encoding) + " is not read", out;
                 if (physical == kBoolean) return out.cause = where + ": a dictionary of booleans", out;
                 dict = (uint32_t)out.dicts.size();
-                out.dicts.push_back(DictPage{r.body, out.entries, r.body_size, r.num_values});
+                out.dicts.push_back(DictPage{r.body, out.entries, r.body_size, r.num_values, r.flags & kPageInImage ? 1u : 0u, 0});
                 out.entries += r.num_values;
                 continue;
             }
@@ -332,7 +375,7 @@ inline ColumnPages column_pages(const Footer& f, uint64_t c, const std::vector<C
             if (indexed && dict == ~0u) return out.cause = where + ": dictionary-coded values without a dictionary page", out;
             out.indices |= indexed || rle_bool;
             out.data.push_back(DataPage{row0, out.words, r.body, r.num_values, r.body_size, r.def_at, r.def_bytes, r.values_at, r.encoding,
-                                        indexed ? dict : ~0u, 0});
+                                        indexed ? dict : ~0u, r.flags & kPageInImage ? 1u : 0u});
             row0 += r.num_values, out.words += (r.num_values + 63) / 64;
         }
     }

@@ -44,7 +44,8 @@ core/df/tabular.rs:1492-1547) -- `write_csv`, `write_csv_device`, `write_df`; `o
 JSON array (`write_df`'s jsonl / ndjson / json arms, and the text of a data-frame view) -- `write_jsonl`, `write_json` and
 their `_device` forms; `oxh_write_parquet_*` as an uncompressed Parquet file (what `write_df`'s parquet arm is for) --
 `write_parquet`, `write_parquet_device`; and `oxh_parquet_*` read such a file back (`ParquetFile`, `read_parquet`,
-`read_parquet_device`, `parquet_shape`, `parquet_schema`).
+`read_parquet_device`, `parquet_shape`, `parquet_schema`), SNAPPY pages included: `oxh_snappy_inflate_*` inflate many raw
+Snappy blocks per call (`snappy_inflate`, `snappy_inflate_device`) and the Parquet open runs the same kernel.
 
 A frame is an ordered mapping from column name to `Column`. A row's bytes are, over the columns in the
 frame's order: nothing for a null, the raw little-endian bytes of Int8 / Int32 / Float32 / Int64 /
@@ -2665,7 +2666,7 @@ _PARQUET_PHYSICAL = ("BOOLEAN", "INT32", "INT64", "INT96", "FLOAT", "DOUBLE", "B
 
 
 class ParquetStats(NamedTuple):
-    """stats8 of oxh_parquet_open_* (without its last, unused word)."""
+    """stats8 of oxh_parquet_open_*."""
     rows: int
     ncols: int
     row_groups: int
@@ -2673,6 +2674,7 @@ class ParquetStats(NamedTuple):
     dict_pages: int
     footer_bytes: int
     unreadable_columns: int
+    pages_inflated: int = 0
 
 
 class ParquetColumnStats(NamedTuple):
@@ -2704,10 +2706,13 @@ class ParquetFile:
     """The page index of one Parquet buffer (an oxh_parquet_open_* handle), the twin of `JsonlFile`: `stats`,
     `names`, `types`, `measure`, `columns`. data: bytes / a uint8 numpy array (the host form, which owns a device
     copy), or with device=True a uint8 torch tensor on the device, which the object keeps alive. The rules are
-    include/oxen_hash.h's "Parquet: the file's bytes": uncompressed files with a flat schema, the physical bits."""
+    include/oxen_hash.h's "Parquet: the file's bytes": uncompressed and, with inflate (OXH_PARQUET_INFLATE, the
+    default), SNAPPY files with a flat schema, the physical bits. The handle holds the inflated size of every
+    compressed page on the device until `close`; `stats.pages_inflated` counts them."""
 
-    def __init__(self, data, ctx: Optional[_capi.Context] = None, device: bool = False, stream=None):
+    def __init__(self, data, ctx: Optional[_capi.Context] = None, device: bool = False, stream=None, inflate: bool = True):
         self.device = device
+        flags = _capi.OXH_PARQUET_INFLATE if inflate else 0
         self.ctx = ctx
         self.stream = stream
         self.handle = None
@@ -2720,16 +2725,16 @@ class ParquetFile:
             if data.element_size() != 1 or not data.is_contiguous():
                 raise _capi.OxenError("the Parquet bytes are a contiguous uint8 tensor", _capi.OXH_ERR_INVALID)
             self.data = data
-            _capi.check(_capi.lib().oxh_parquet_open_device(_handle(ctx), data.data_ptr() if data.numel() else None, data.numel(), 0,
+            _capi.check(_capi.lib().oxh_parquet_open_device(_handle(ctx), data.data_ptr() if data.numel() else None, data.numel(), flags,
                                                             ctypes.byref(out), stats.ctypes.data_as(_capi._u64p), _stream(stream)),
                         "oxh_parquet_open_device")
         else:
             self.data = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
-            _capi.check(_capi.lib().oxh_parquet_open_host(_handle(ctx), self.data.ctypes.data if self.data.size else None, self.data.size, 0,
+            _capi.check(_capi.lib().oxh_parquet_open_host(_handle(ctx), self.data.ctypes.data if self.data.size else None, self.data.size, flags,
                                                           ctypes.byref(out), stats.ctypes.data_as(_capi._u64p)),
                         "oxh_parquet_open_host")
         self.handle = out
-        self.stats = ParquetStats(*(int(x) for x in stats[:7]))
+        self.stats = ParquetStats(*(int(x) for x in stats[:8]))
         self._names = None
 
     def close(self) -> None:
@@ -2854,38 +2859,93 @@ def _parquet_frame(f: ParquetFile, schema, columns) -> dict:
     return dict(zip([names[c] for c in picked], f.columns(picked, types)))
 
 
-def read_parquet(path_or_bytes, schema=None, columns=None, ctx: Optional[_capi.Context] = None) -> dict:
-    """`read_df_parquet` (core/df/tabular.rs:111) on the device: an uncompressed Parquet file with a flat schema (a
+def read_parquet(path_or_bytes, schema=None, columns=None, ctx: Optional[_capi.Context] = None, inflate: bool = True) -> dict:
+    """`read_df_parquet` (core/df/tabular.rs:111) on the device: an uncompressed or SNAPPY Parquet file with a flat schema (a
     path) or its bytes to the ordered {name: Column} in host memory that every function of this module takes. columns
     selects and orders, by name or index. schema ({name: type} or one per selected column; polars' dtype names or
     OXH_CSV_* words) widens an INT32 column to "Int64", a FLOAT column to "Float64", or picks "LargeString"; a column
-    without one is read as its physical type (`ParquetFile.types`). A compressed file raises with the codec's number:
-    that one goes to the CPU. `read_df` still refuses `.parquet`: this is the entry."""
+    without one is read as its physical type (`ParquetFile.types`). SNAPPY pages are inflated on the device at open
+    (inflate=False refuses them as any other codec); a file of another codec raises with the codec's number: that one
+    goes to the CPU. `read_df` still refuses `.parquet`: this is the entry."""
     data, _ = _csv_bytes(path_or_bytes)
-    with ParquetFile(data, ctx=ctx) as f:
+    with ParquetFile(data, ctx=ctx, inflate=inflate) as f:
         return _parquet_frame(f, schema, columns)
 
 
-def read_parquet_device(d_bytes, schema=None, columns=None, ctx: Optional[_capi.Context] = None, stream=None) -> dict:
+def read_parquet_device(d_bytes, schema=None, columns=None, ctx: Optional[_capi.Context] = None, stream=None, inflate: bool = True) -> dict:
     """`read_parquet` over the file's bytes already on the device (a uint8 torch tensor, as `write_parquet_device`
     leaves them): device `Column`s that every `_device` function of this module accepts unchanged. Blocks."""
-    with ParquetFile(d_bytes, ctx=ctx, device=True, stream=stream) as f:
+    with ParquetFile(d_bytes, ctx=ctx, device=True, stream=stream, inflate=inflate) as f:
         return _parquet_frame(f, schema, columns)
 
 
-def parquet_shape(path_or_bytes, ctx: Optional[_capi.Context] = None) -> tuple:
+def parquet_shape(path_or_bytes, ctx: Optional[_capi.Context] = None, inflate: bool = True) -> tuple:
     """(width, height) of the tabular metadata, by the footer alone."""
     data, _ = _csv_bytes(path_or_bytes)
-    with ParquetFile(data, ctx=ctx) as f:
+    with ParquetFile(data, ctx=ctx, inflate=inflate) as f:
         return f.stats.ncols, f.stats.rows
 
 
-def parquet_schema(path_or_bytes, ctx: Optional[_capi.Context] = None) -> list:
+def parquet_schema(path_or_bytes, ctx: Optional[_capi.Context] = None, inflate: bool = True) -> list:
     """[(name, dtype name)] of the tabular metadata: the names and the native types (None: a column this reader
     cannot read)."""
     data, _ = _csv_bytes(path_or_bytes)
-    with ParquetFile(data, ctx=ctx) as f:
+    with ParquetFile(data, ctx=ctx, inflate=inflate) as f:
         return list(zip(f.names, [PARQUET_TYPE_NAMES.get(t.type) for t in f.types()]))
+
+
+# ---------------------------------------------------------------- Snappy: raw blocks inflated in one call (oxh_snappy_inflate_*)
+def _snappy_length(block) -> int:
+    """The uncompressed length a raw Snappy block declares: its varint preamble (0 where it has none that is valid --
+    the library then names the cause)."""
+    value = 0
+    for i, byte in enumerate(bytes(block[:5])):
+        value |= (byte & 127) << (7 * i)
+        if not byte & 128:
+            return value if value < 1 << 32 else 0
+    return 0
+
+
+def snappy_inflate(blocks, ctx: Optional[_capi.Context] = None) -> list:
+    """oxh_snappy_inflate_host: every raw Snappy block (bytes) inflated on the device in one call, as a list of bytes.
+    The lengths come from the blocks' preambles, read here. A malformed block raises, naming the first and its cause
+    (include/oxen_hash.h "Snappy")."""
+    blocks = [bytes(b) for b in blocks]
+    n = len(blocks)
+    src = np.frombuffer(b"".join(blocks) or b"\0", dtype=np.uint8)
+    src_offsets = np.concatenate([[0], np.cumsum([len(b) for b in blocks])]).astype(np.uint64)
+    dst_offsets = np.concatenate([[0], np.cumsum([_snappy_length(b) for b in blocks])]).astype(np.uint64)
+    dst, status, bad = np.zeros(max(int(dst_offsets[-1]), 1), dtype=np.uint8), np.zeros(max(n, 1), dtype=np.uint32), ctypes.c_uint64(0)
+    _capi.check(_capi.lib().oxh_snappy_inflate_host(_handle(ctx), n, src.ctypes.data, src_offsets.ctypes.data_as(_capi._u64p), dst.ctypes.data,
+                                                    dst_offsets.ctypes.data_as(_capi._u64p), status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                                    ctypes.byref(bad)), "oxh_snappy_inflate_host")
+    if bad.value:
+        first = int(np.flatnonzero(status[:n])[0])
+        raise _capi.OxenError(f"snappy inflate: {bad.value} malformed block(s); block {first}: {_capi.OXH_SNAPPY_CAUSES[int(status[first])]}",
+                              _capi.OXH_ERR_INVALID)
+    raw = dst.tobytes()
+    return [raw[int(dst_offsets[k]):int(dst_offsets[k + 1])] for k in range(n)]
+
+
+def snappy_inflate_device(d_src, d_src_offsets, d_dst, d_dst_offsets, d_status, ctx: Optional[_capi.Context] = None, stream=None) -> int:
+    """oxh_snappy_inflate_device over torch tensors on the device: block b of d_src (uint8) between d_src_offsets[b] and
+    [b + 1] (int64 / uint64, n + 1 of them) fills d_dst between d_dst_offsets[b] and [b + 1], the block's expected
+    length; d_status (n int32 / uint32) receives 0 or the cause. Returns the number of malformed blocks. Blocks."""
+    from .device import _require_cuda, _stream
+
+    for t in (d_src, d_src_offsets, d_dst, d_dst_offsets, d_status):
+        _require_cuda(t)
+        if not t.is_contiguous():
+            raise _capi.OxenError("the Snappy tensors are contiguous", _capi.OXH_ERR_INVALID)
+    if d_src.element_size() != 1 or d_dst.element_size() != 1 or d_src_offsets.element_size() != 8 or d_dst_offsets.element_size() != 8 or d_status.element_size() != 4:
+        raise _capi.OxenError("uint8 bytes, 8-byte offsets and 4-byte statuses", _capi.OXH_ERR_INVALID)
+    n = d_status.numel()
+    if d_src_offsets.numel() != n + 1 or d_dst_offsets.numel() != n + 1:
+        raise _capi.OxenError("one more offset than blocks in both tables", _capi.OXH_ERR_INVALID)
+    bad = ctypes.c_uint64(0)
+    _capi.check(_capi.lib().oxh_snappy_inflate_device(_handle(ctx), n, d_src.data_ptr(), d_src_offsets.data_ptr(), d_dst.data_ptr(), d_dst_offsets.data_ptr(),
+                                                      d_status.data_ptr(), ctypes.byref(bad), _stream(stream)), "oxh_snappy_inflate_device")
+    return int(bad.value)
 
 
 def read_df(path, ctx: Optional[_capi.Context] = None) -> dict:
