@@ -1200,11 +1200,23 @@ int oxh_write_json_host(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const uint
  *   Statistics, per column chunk: null_count for every column; min_value and max_value for INT64 (signed) and for
  *     DOUBLE by the format's rule (NaNs left out; neither written when every cell is NaN or null; a zero min is -0.0,
  *     a zero max is +0.0). Booleans and strings get null_count only. There are no page statistics or indexes.
- *   Stated and not built: compression; dictionary encoding; nested and narrower types; the `arrow`
+ *   Compression. With OXH_PARQUET_SNAPPY every page body (levels and values) is one raw Snappy block, compressed on
+ *     the device by the kernel of oxh_snappy_compress_* ("Snappy, compress" below); the pages stay DataPage V1, and a
+ *     V1 page of a SNAPPY chunk is always compressed, also when it does not shrink. The call emits the uncompressed
+ *     file into an image it owns, compresses the bodies, brings the streams' sizes down and plans again on the host:
+ *     compressed_page_size of every PageHeader, the pages' places, per chunk codec SNAPPY, total_compressed_size and
+ *     total_uncompressed_size (the headers as written plus the uncompressed bodies), the row groups' sizes, the
+ *     footer; a pack pass then writes headers and bodies to out, every byte once. Statistics, tiles, row groups and
+ *     page cuts are the uncompressed writer's: page_bytes counts uncompressed bytes. Sizing: the file's size is known
+ *     only after compressing, so with out NULL out_bytes (and stats4[0]) is a CAPACITY that always suffices -- the
+ *     uncompressed file, 32 + n / 6 + 5 bytes a page and 10 bytes for each size and offset of the footer --, not the
+ *     size; a capacity below it is the "capacity below the need" error with nothing written; the writing call sets
+ *     out_bytes and stats4[0] to the file's size. Working memory: the uncompressed file and 65 KiB per 64 KiB of it.
+ *   Stated and not built: zstd; dictionary encoding; nested and narrower types; the `arrow`
  *     arm of `write_df`.
  *
  * Inputs: as oxh_write_json_* (names and name_offsets are always read; host memory in both forms), then
- * rows_per_group, page_bytes and flags (none defined). Outputs: the file's bytes in out (capacity bytes; device
+ * rows_per_group, page_bytes and flags (0 or OXH_PARQUET_SNAPPY; bit 0 stays reserved). Outputs: the file's bytes in out (capacity bytes; device
  * memory in _device, host memory in _host); out_bytes = the file's size; stats4 = {bytes, row groups, pages, null
  * cells}. With out NULL the call only measures. With a capacity below the need nothing is written to out, out_bytes
  * and stats4 are set and the call returns OXH_ERR_INVALID. nrows == 0 gives a valid file with the schema and no row
@@ -1212,7 +1224,7 @@ int oxh_write_json_host(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const uint
  * through one device block and uses the ctx's stream. Every byte of the file is written by the call: the result
  * does not depend on what out held. A pair of offsets that is negative or decreases is never read through.
  * OXH_ERR_INVALID, every message starting with "parquet write:", before OXH_ERR_NODEVICE (there is no CPU path), in
- * this order: NULL types, kinds, values, offsets, validity or bit_offsets; ncols == 0; non-zero flags; a
+ * this order: NULL types, kinds, values, offsets, validity or bit_offsets; ncols == 0; unknown flags; a
  * rows_per_group that is no multiple of 1 024; an unknown type; a column whose kind does not fit its type; NULL
  * name_offsets, name_offsets that decrease, NULL names with name bytes; NULL out_bytes or stats4; more than 2^40 rows;
  * with rows, per column: a byte column without offsets, another column without values, and in the host form offsets
@@ -1221,6 +1233,7 @@ int oxh_write_json_host(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const uint
  * and no values, a string cell of 2^32 bytes or more, a page above INT32_MAX bytes, more than 32 767 row groups (a RowGroup's
  * ordinal is an int16); then a capacity below the need.
  * A failed allocation is OXH_ERR_NOMEM with the outputs untouched. */
+#define OXH_PARQUET_SNAPPY 2u /* flags of oxh_write_parquet_*: SNAPPY pages */
 int oxh_write_parquet_device(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const uint32_t* types, const uint32_t* kinds,
                              const void* const* d_values, const void* const* d_offsets, const uint8_t* const* d_validity,
                              const uint64_t* bit_offsets, const uint8_t* names, const uint64_t* name_offsets,
@@ -1453,7 +1466,7 @@ int oxh_parquet_columns_host(void* parquet, uint32_t nsel, const uint32_t* col_i
  * with "snappy inflate:", in this order: NULL bad_blocks; then nblocks == 0 is OXH_OK with *bad_blocks = 0; more than
  * 2^32 blocks; NULL src, src_offsets, dst_offsets, status; host form: offsets that decrease (the block named), NULL
  * dst with bytes to fill; then OXH_ERR_NODEVICE; then a NULL ctx. A failed allocation is OXH_ERR_NOMEM.
- *   Stated and not built: a compressor; the framed format; zstd, gzip, lz4. */
+ *   Stated and not built: the framed format; zstd, gzip, lz4. */
 #define OXH_SNAPPY_PREAMBLE 1
 #define OXH_SNAPPY_INPUT 2
 #define OXH_SNAPPY_OFFSET_ZERO 3
@@ -1465,6 +1478,45 @@ int oxh_snappy_inflate_device(oxh_ctx* ctx, uint64_t nblocks, const uint8_t* d_s
                               const uint64_t* d_dst_offsets, uint32_t* d_status, uint64_t* bad_blocks, void* stream);
 int oxh_snappy_inflate_host(oxh_ctx* ctx, uint64_t nblocks, const uint8_t* src, const uint64_t* src_offsets, uint8_t* dst,
                             const uint64_t* dst_offsets, uint32_t* status, uint64_t* bad_blocks);
+
+/* ---------------------------------------------------------------- Snappy, compress: many blocks to raw streams per call
+ * The counterpart of the inflate above: a caller who holds bytes in HBM gets raw Snappy blocks ("Snappy" states the
+ * format) without a round trip of the bytes through host memory. Any decoder of the raw format reads the streams.
+ *   The stream of a block is its varint preamble, then literals, copies with a 1-byte offset (length 4..11, offset
+ *   below 2 048) and copies with a 2-byte offset (length 1..64, offset up to 65 535); the 4-byte-offset copy is never
+ *   written. A block is cut into fragments of at most 64 KiB and a copy never reaches outside its fragment (the
+ *   reference Snappy makes the same cut), so an offset never passes 65 535. Which matches are found is this library's
+ *   own choice (a table of 4 096 positions per fragment, probed 64 positions at a time; a match whose source lies among
+ *   the same 64 positions is not found) -- the bytes differ from other compressors', the content does not. The same
+ *   input gives the same bytes on every run and in both forms.
+ *   oxh_snappy_bound(n) = 32 + n + n / 6, Snappy's customary bound, so buffers sized by other libraries' rule fit; it
+ *   needs no device. This compressor stays below it: a literal of g bytes costs g + 1, + 2 above 60, + 3 above 256; a
+ *   copy of m >= 4 bytes costs at most 3 bytes per 64, never more than m - 1. Alternating short literals and 4-byte
+ *   copies therefore never grow (a 1-byte literal and a 4-byte copy are 2 + 3 bytes for 5), and a literal with the copy
+ *   behind it adds at most 2 bytes, only when the literal has more than 60. A fragment of f bytes gives at most
+ *   f + f / 65 + 3 and a block of n bytes at most 5 + n + n / 65 + 3 * ceil(n / 65536), which is below 32 + n + n / 6
+ *   for every n (up to 9 fragments by the 32, from there on by n / 6 - n / 65).
+ * Block b reads src[src_offsets[b], src_offsets[b + 1]) and writes its stream at the START of
+ * dst[dst_offsets[b], dst_offsets[b + 1]), a range of at least oxh_snappy_bound() of the block; sizes[b] = the
+ * stream's length; what lies behind it inside the range is not written. Any alignment, nblocks + 1 offsets each.
+ * status[b] = 0, or OXH_SNAPPY_RANGE with sizes[b] = 0 and nothing written for a block whose source or destination
+ * offsets decrease or whose destination range is below the bound; such a block is NOT an error of the call and does
+ * not touch its neighbours. No byte outside a block's own destination range is written and none outside its own
+ * source is read. Both forms block until complete; stream orders the device form's work (the two offset tables come
+ * down first: 16 bytes a block), the host form uses the ctx's stream and leaves dst, sizes and status untouched
+ * unless it returns OXH_OK. Working memory: 65 KiB per fragment, held for the call.
+ * OXH_ERR_INVALID, every message starting with "snappy compress:", in this order: nblocks == 0 is OXH_OK before
+ * anything else; more than 2^32 blocks; NULL src, src_offsets, dst_offsets, sizes, status; device form: NULL dst;
+ * host form: a block above 2^32 - 1 bytes (the block named), NULL dst with a block to write; then OXH_ERR_NODEVICE
+ * (there is no CPU path); then a NULL ctx; device form, once the tables are down: a block above 2^32 - 1 bytes. A
+ * failed allocation is OXH_ERR_NOMEM.
+ *   Stated and not built: matches whose source lies inside the lane's own batch of 64 positions; lazy or
+ *   streamed compression; the framed format; zstd. */
+uint64_t oxh_snappy_bound(uint64_t n);
+int oxh_snappy_compress_device(oxh_ctx* ctx, uint64_t nblocks, const uint8_t* d_src, const uint64_t* d_src_offsets, uint8_t* d_dst,
+                               const uint64_t* d_dst_offsets, uint64_t* d_sizes, uint32_t* d_status, void* stream);
+int oxh_snappy_compress_host(oxh_ctx* ctx, uint64_t nblocks, const uint8_t* src, const uint64_t* src_offsets, uint8_t* dst,
+                             const uint64_t* dst_offsets, uint64_t* sizes, uint32_t* status);
 
 /* ---------------------------------------------------------------- K2: merkle parent nodes */
 /* get_combined_hash (hasher.rs:67-80) x n on the device:

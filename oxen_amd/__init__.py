@@ -53,7 +53,8 @@ _FROM_TABULAR = ("KeyedDiff", "STATUS_NAMES", "keyed_diff_digests", "keyed_diff_
                  "write_jsonl_device", "write_json", "write_json_device", "ParquetWriteStats",
                  "write_parquet", "write_parquet_device", "JsonlStats", "JsonlFile", "read_jsonl", "read_jsonl_device",
                  "jsonl_shape", "jsonl_schema", "read_df", "ParquetStats", "ParquetColumnStats", "ParquetColumnType", "ParquetFile",
-                 "read_parquet", "read_parquet_device", "parquet_shape", "parquet_schema")
+                 "read_parquet", "read_parquet_device", "parquet_shape", "parquet_schema", "snappy_bound", "snappy_compress",
+                 "snappy_compress_device")
 
 
 def __getattr__(name):

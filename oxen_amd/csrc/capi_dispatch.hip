@@ -334,6 +334,201 @@ int oxh_snappy_inflate_host(oxh_ctx* ctx, uint64_t nblocks, const uint8_t* src, 
     return rc;
 }
 
+// ---------------------------------------------------------------- Snappy, compress (the kernels: snappy_compress.hip)
+uint64_t oxh_snappy_bound(uint64_t n) { return oxh::snappy_bound(n); }
+
+static int snappy_compress_args(uint64_t nblocks, const void* src, const void* src_offsets, const void* dst_offsets, const void* sizes,
+                                const void* status) {
+    if (nblocks > 0xFFFFFFFFull) return fail(OXH_ERR_INVALID, "snappy compress: more than 2^32 blocks");
+    if (!src) return fail(OXH_ERR_INVALID, "snappy compress: src is NULL");
+    if (!src_offsets) return fail(OXH_ERR_INVALID, "snappy compress: src_offsets is NULL");
+    if (!dst_offsets) return fail(OXH_ERR_INVALID, "snappy compress: dst_offsets is NULL");
+    if (!sizes) return fail(OXH_ERR_INVALID, "snappy compress: sizes is NULL");
+    if (!status) return fail(OXH_ERR_INVALID, "snappy compress: status is NULL");
+    return OXH_OK;
+}
+
+static int snappy_compress_enter(oxh_ctx* ctx) {
+    int rc = check_device(ctx ? ctx->device : 0);  // there is no CPU path
+    if (rc) return rc;
+    if (!ctx) return fail(OXH_ERR_INVALID, "snappy compress: ctx is NULL");
+    HIP_TRY(hipSetDevice(ctx->device));
+    return OXH_OK;
+}
+
+namespace {
+// The fragments of a call, from the offset tables on the host: good[b] = the block is compressed (its offsets do
+// not decrease and its destination holds snappy_bound() of it); frag0 and frag_block as SnappyWork wants them.
+struct SnappyPlan {
+    std::vector<uint8_t> good;
+    std::vector<uint64_t> frag0;
+    std::vector<uint32_t> frag_block;
+};
+
+int snappy_plan(uint64_t nblocks, const uint64_t* src_offsets, const uint64_t* dst_offsets, SnappyPlan& p) {
+    try {
+        p.good.assign(nblocks, 0), p.frag0.assign(nblocks + 1, 0);
+        for (uint64_t b = 0; b < nblocks; ++b) {
+            p.frag0[b] = p.frag_block.size();
+            if (src_offsets[b + 1] < src_offsets[b] || dst_offsets[b + 1] < dst_offsets[b]) continue;
+            const uint64_t n = src_offsets[b + 1] - src_offsets[b];
+            if (n > 0xFFFFFFFFull)
+                return fail(OXH_ERR_INVALID, "snappy compress: block " + std::to_string(b) + " has " + std::to_string(n) + " B: more than 2^32 - 1");
+            if (dst_offsets[b + 1] - dst_offsets[b] < oxh::snappy_bound(n)) continue;
+            p.good[b] = 1;
+            p.frag_block.insert(p.frag_block.end(), oxh::snappy_fragments(n), (uint32_t)b);
+        }
+        p.frag0[nblocks] = p.frag_block.size();
+    } catch (const std::bad_alloc&) {
+        return fail(OXH_ERR_NOMEM, "snappy compress: the fragment tables on the host");
+    }
+    return OXH_OK;
+}
+
+using oxh::SnappyLayout;
+
+// The tables go up and every fragment is compressed into its slot.
+int snappy_run_fragments(const SnappyPlan& p, const SnappyLayout& lay, uint8_t* d, const uint8_t* d_src, const uint64_t* d_src_lo,
+                         const uint64_t* d_src_hi, hipStream_t st) {
+    HIP_TRY(hipMemcpyAsync(d + lay.at_frag0, p.frag0.data(), p.frag0.size() * 8, hipMemcpyHostToDevice, st));
+    if (!p.frag_block.empty()) HIP_TRY(hipMemcpyAsync(d + lay.at_block, p.frag_block.data(), p.frag_block.size() * 4, hipMemcpyHostToDevice, st));
+    return oxh::snappy_fragments_enqueue(d_src, d_src_lo, d_src_hi, lay.work(d, p.frag_block.size()), st);
+}
+
+int snappy_ctrl_error(unsigned long long ctrl) {
+    return ctrl ? fail(OXH_ERR_HIP, "snappy compress: a fragment's stream is not what the tables say (did the input change during the call?)") : OXH_OK;
+}
+}  // namespace
+
+int oxh_snappy_compress_device(oxh_ctx* ctx, uint64_t nblocks, const uint8_t* d_src, const uint64_t* d_src_offsets, uint8_t* d_dst,
+                               const uint64_t* d_dst_offsets, uint64_t* d_sizes, uint32_t* d_status, void* stream) {
+    if (nblocks == 0) return OXH_OK;
+    int rc = snappy_compress_args(nblocks, d_src, d_src_offsets, d_dst_offsets, d_sizes, d_status);
+    if (rc) return rc;
+    if (!d_dst) return fail(OXH_ERR_INVALID, "snappy compress: dst is NULL");
+    if ((rc = snappy_compress_enter(ctx))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    // the offset tables come down: the fragments are cut on the host
+    std::vector<uint64_t> tables;
+    try {
+        tables.resize(2 * (nblocks + 1));
+    } catch (const std::bad_alloc&) {
+        return fail(OXH_ERR_NOMEM, "snappy compress: the offset tables on the host");
+    }
+    HIP_TRY(hipMemcpyAsync(tables.data(), d_src_offsets, (nblocks + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(tables.data() + nblocks + 1, d_dst_offsets, (nblocks + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    SnappyPlan plan;
+    if ((rc = snappy_plan(nblocks, tables.data(), tables.data() + nblocks + 1, plan))) return rc;
+    const SnappyLayout lay(0, nblocks, plan.frag_block.size());
+    oxh::ScratchLease lease(st);
+    void* base = nullptr;
+    if (lease.get(lay.total, &base) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(OXH_ERR_NOMEM, "snappy compress: " + std::to_string(lay.total) + " B of fragment slots on the device");
+    }
+    uint8_t* d = (uint8_t*)base;
+    unsigned long long ctrl = 0;
+    if ((rc = snappy_run_fragments(plan, lay, d, d_src, d_src_offsets, d_src_offsets + 1, st))) return rc;
+    if ((rc = oxh::snappy_pack_enqueue(d_src_offsets, d_src_offsets + 1, d_dst, d_dst_offsets, d_dst_offsets + 1, d_sizes, d_status, nblocks, true,
+                                       lay.work(d, plan.frag_block.size()), st)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(&ctrl, d + lay.at_ctrl, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return snappy_ctrl_error(ctrl);
+}
+
+int oxh_snappy_compress_host(oxh_ctx* ctx, uint64_t nblocks, const uint8_t* src, const uint64_t* src_offsets, uint8_t* dst,
+                             const uint64_t* dst_offsets, uint64_t* sizes, uint32_t* status) {
+    if (nblocks == 0) return OXH_OK;
+    int rc = snappy_compress_args(nblocks, src, src_offsets, dst_offsets, sizes, status);
+    if (rc) return rc;
+    SnappyPlan plan;
+    if ((rc = snappy_plan(nblocks, src_offsets, dst_offsets, plan))) return rc;
+    const uint64_t nfrags = plan.frag_block.size();
+    // the bytes the good blocks name, in one piece
+    uint64_t lo = UINT64_MAX, hi = 0, ngood = 0;
+    for (uint64_t b = 0; b < nblocks; ++b)
+        if (plan.good[b]) lo = std::min(lo, src_offsets[b]), hi = std::max(hi, src_offsets[b + 1]), ++ngood;
+    if (!ngood) lo = hi = 0;
+    if (ngood && !dst) return fail(OXH_ERR_INVALID, "snappy compress: dst is NULL");
+    if ((rc = snappy_compress_enter(ctx))) return rc;
+    hipStream_t st = ctx->stream;
+    // one device block: the input, four offset tables from 0, the sizes, the statuses, then the call's working memory
+    const uint64_t up16 = 15, at_tables = (hi - lo + up16) & ~up16, at_sizes = at_tables + 4 * nblocks * 8, at_status = at_sizes + nblocks * 8;
+    const SnappyLayout lay(at_status + nblocks * 4, nblocks, nfrags);
+    std::vector<uint64_t> tables, got_sizes;
+    std::vector<uint32_t> frag_size, got_status;
+    try {
+        tables.assign(4 * nblocks, 0), got_sizes.resize(nblocks), frag_size.resize(nfrags), got_status.resize(nblocks);
+    } catch (const std::bad_alloc&) {
+        return fail(OXH_ERR_NOMEM, "snappy compress: the offset tables on the host");
+    }
+    for (uint64_t b = 0; b < nblocks; ++b)
+        if (plan.good[b]) tables[b] = src_offsets[b] - lo, tables[nblocks + b] = src_offsets[b + 1] - lo;
+    uint8_t *d = nullptr, *d_out = nullptr;
+    if (hipMalloc(&d, lay.total) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(OXH_ERR_NOMEM, "snappy compress: " + std::to_string(lay.total) + " B for the blocks on the device");
+    }
+    oxh::poison_device(d, lay.total, st);
+    rc = [&]() -> int {
+        if (hi > lo) HIP_TRY(hipMemcpyAsync(d, src + lo, hi - lo, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d + at_tables, tables.data(), 2 * nblocks * 8, hipMemcpyHostToDevice, st));
+        const uint64_t *d_lo = (const uint64_t*)(d + at_tables), *d_hi = d_lo + nblocks, *d_dlo = d_hi + nblocks, *d_dhi = d_dlo + nblocks;
+        int r = snappy_run_fragments(plan, lay, d, d, d_lo, d_hi, st);
+        if (r) return r;
+        unsigned long long ctrl = 0;
+        if (nfrags) HIP_TRY(hipMemcpyAsync(frag_size.data(), d + lay.at_size, nfrags * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&ctrl, d + lay.at_ctrl, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if ((r = snappy_ctrl_error(ctrl))) return r;
+        // the streams' sizes are known: they are packed one behind the other and come down block by block
+        uint64_t packed = 0;
+        for (uint64_t b = 0; b < nblocks; ++b) {
+            tables[2 * nblocks + b] = packed;
+            if (plan.good[b]) {
+                uint64_t n = src_offsets[b + 1] - src_offsets[b];
+                do ++packed; while (n >>= 7);
+                for (uint64_t f = plan.frag0[b]; f < plan.frag0[b + 1]; ++f) packed += frag_size[f];
+            }
+            tables[3 * nblocks + b] = packed;
+        }
+        if (hipMalloc(&d_out, std::max<uint64_t>(packed, 1)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(OXH_ERR_NOMEM, "snappy compress: " + std::to_string(packed) + " B for the streams on the device");
+        }
+        oxh::poison_device(d_out, packed, st);
+        HIP_TRY(hipMemcpyAsync(d + at_tables + 2 * nblocks * 8, tables.data() + 2 * nblocks, 2 * nblocks * 8, hipMemcpyHostToDevice, st));
+        if ((r = oxh::snappy_pack_enqueue(d_lo, d_hi, d_out, d_dlo, d_dhi, (uint64_t*)(d + at_sizes), (uint32_t*)(d + at_status), nblocks, false,
+                                          lay.work(d, nfrags), st)))
+            return r;
+        HIP_TRY(hipMemcpyAsync(got_sizes.data(), d + at_sizes, nblocks * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(got_status.data(), d + at_status, nblocks * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&ctrl, d + lay.at_ctrl, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if ((r = snappy_ctrl_error(ctrl))) return r;
+        for (uint64_t b = 0; b < nblocks; ++b)
+            if (plan.good[b] && (got_status[b] || got_sizes[b] != tables[3 * nblocks + b] - tables[2 * nblocks + b])) return snappy_ctrl_error(1);
+        // the packed streams come down in one copy and go to their ranges from there
+        std::vector<uint8_t> streams;
+        try {
+            streams.resize(packed);
+        } catch (const std::bad_alloc&) {
+            return fail(OXH_ERR_NOMEM, "snappy compress: " + std::to_string(packed) + " B for the streams on the host");
+        }
+        if (packed) HIP_TRY(hipMemcpy(streams.data(), d_out, packed, hipMemcpyDeviceToHost));
+        for (uint64_t b = 0; b < nblocks; ++b)
+            if (plan.good[b]) memcpy(dst + dst_offsets[b], streams.data() + tables[2 * nblocks + b], got_sizes[b]);
+        for (uint64_t b = 0; b < nblocks; ++b) sizes[b] = plan.good[b] ? got_sizes[b] : 0, status[b] = plan.good[b] ? 0 : OXH_SNAPPY_RANGE;
+        return OXH_OK;
+    }();
+    if (rc != OXH_OK) (void)hipStreamSynchronize(st);
+    (void)hipFree(d);
+    if (d_out) (void)hipFree(d_out);
+    return rc;
+}
+
 int oxh_format_hex(uint64_t lo, uint64_t hi, char* out) {
     if (!out) return 0;
     unsigned __int128 v = ((unsigned __int128)hi << 64) | lo;

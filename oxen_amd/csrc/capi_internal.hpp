@@ -68,6 +68,10 @@
 //   snappy_inflate.hip many raw Snappy blocks inflated per launch (oxh_snappy_inflate_*; the Parquet open's SNAPPY pages):
 //                      a wave per block, the input through 1 KiB LDS windows, one lane chasing the tags into 64 cells,
 //                      the wave executing them -- literals first, copies in rounds picked by a ballot
+//   snappy_compress.hip many blocks compressed to raw Snappy streams per launch (oxh_snappy_compress_*): a wave per 64 KiB
+//                      fragment, 64 positions a batch probing a table of positions in LDS (atomic max), every lane
+//                      extending its own match, a uniform greedy selection, the batch's elements placed by a prefix
+//                      sum and staged in LDS; then a wave per block packs the fragments' streams behind the preamble
 // There is no CPU hashing path: every digest this library returns was computed on the GPU.
 #pragma once
 
@@ -192,6 +196,48 @@ namespace oxh {
 // (capi_dispatch.hip), the Parquet open (parquet_read.hip).
 int snappy_inflate_enqueue(const uint8_t* d_src, const uint64_t* d_src_lo, const uint64_t* d_src_hi, uint8_t* d_dst, const uint64_t* d_dst_lo,
                            const uint64_t* d_dst_hi, uint32_t* d_status, uint64_t nblocks, unsigned long long* d_bad, hipStream_t st);
+}  // namespace oxh
+
+// ---------------------------------------------------------------- batched Snappy compress (snappy_compress.hip)
+namespace oxh {
+constexpr uint32_t kSnappyFragment = 65536;         // a block is cut at its multiples; a copy stays inside its fragment
+constexpr uint32_t kSnappySlot = 65536 + 1024;      // scratch bytes of one fragment's stream (the derivation: snappy_compress.hip)
+__host__ __device__ inline uint64_t snappy_bound(uint64_t n) { return 32 + n + n / 6; }  // oxh_snappy_bound
+__host__ __device__ inline uint64_t snappy_fragments(uint64_t n) { return (n + kSnappyFragment - 1) / kSnappyFragment; }
+
+// A call's working memory on the device. The tables are built on the host from the blocks' lengths: d_frag_block[f]
+// = the block of fragment f (u32), d_frag0[b] = the first fragment of block b (nblocks + 1 u64; a block that is
+// refused has none). d_slots: nfrags * kSnappySlot bytes, d_frag_size: nfrags u32, d_ctrl: one word.
+struct SnappyWork {
+    const uint32_t* d_frag_block;
+    const uint64_t* d_frag0;
+    uint64_t nfrags;
+    uint8_t* d_slots;
+    uint32_t* d_frag_size;
+    unsigned long long* d_ctrl;
+};
+// Where the tables and the slots lie in a call's working memory, which starts with `front` bytes of the caller's own.
+struct SnappyLayout {
+    uint64_t at_ctrl, at_frag0, at_block, at_size, at_slots, total;
+    SnappyLayout(uint64_t front, uint64_t nblocks, uint64_t nfrags) {
+        const uint64_t up16 = 15;
+        at_ctrl = (front + up16) & ~up16, at_frag0 = at_ctrl + 16, at_block = at_frag0 + (((nblocks + 1) * 8 + up16) & ~up16);
+        at_size = at_block + ((nfrags * 4 + up16) & ~up16), at_slots = at_size + ((nfrags * 4 + up16) & ~up16);
+        total = at_slots + nfrags * kSnappySlot;
+    }
+    SnappyWork work(uint8_t* d, uint64_t nfrags) const {
+        return SnappyWork{(const uint32_t*)(d + at_block), (const uint64_t*)(d + at_frag0), nfrags, d + at_slots, (uint32_t*)(d + at_size),
+                          (unsigned long long*)(d + at_ctrl)};
+    }
+};
+// Every fragment of blocks d_src[d_src_lo[b], d_src_hi[b]) compressed into its slot, d_frag_size[f] = its stream's
+// bytes; *d_ctrl is cleared first and is not 0 afterwards where a fragment passed its slot. Enqueued on `st`.
+int snappy_fragments_enqueue(const uint8_t* d_src, const uint64_t* d_src_lo, const uint64_t* d_src_hi, const SnappyWork& w, hipStream_t st);
+// Then, per block, the preamble and the fragments' streams to d_dst[d_dst_lo[b] ..): d_sizes[b] = the stream's bytes,
+// d_status[b] = 0; or OXH_SNAPPY_RANGE with nothing written (snappy_pack_kernel states when; `strict`: a destination
+// below snappy_bound() of the block is one). Enqueued on `st`. Callers: oxh_snappy_compress_* (capi_dispatch.hip).
+int snappy_pack_enqueue(const uint64_t* d_src_lo, const uint64_t* d_src_hi, uint8_t* d_dst, const uint64_t* d_dst_lo, const uint64_t* d_dst_hi,
+                        uint64_t* d_sizes, uint32_t* d_status, uint64_t nblocks, bool strict, const SnappyWork& w, hipStream_t st);
 }  // namespace oxh
 
 // ---------------------------------------------------------------- runs of equal neighbours in a wave

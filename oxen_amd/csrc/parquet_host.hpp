@@ -23,6 +23,7 @@ constexpr uint64_t kDefaultPageBytes = 1048576;
 constexpr uint64_t kMaxRows = 1ull << 40;
 constexpr uint64_t kMaxCell = 1ull << 32;            // a BYTE_ARRAY's length is a u32
 constexpr uint64_t kMaxPage = 0x7FFFFFFFull;         // PageHeader's sizes are i32
+constexpr uint32_t kFlagSnappy = 2;                  // OXH_PARQUET_SNAPPY: every page body is one raw Snappy block
 constexpr const char* kCreatedBy = "oxen_amd parquet writer (gfx950)";
 
 // What the measure kernel leaves per (tile, column), entry tile * ncols + column.
@@ -155,7 +156,7 @@ inline std::string write_error(const Args& a, bool host) {
     if (!a.types || !a.kinds || !a.values || !a.offsets || !a.validity || !a.bit_offsets)
         return "types, kinds, values, offsets, validity or bit_offsets is NULL";
     if (a.ncols == 0) return "ncols is 0";
-    if (a.flags) return "unknown flags";
+    if (a.flags & ~kFlagSnappy) return "unknown flags";
     if (a.rows_per_group % kTileRows) return "rows_per_group is not a multiple of 1024";
     for (uint32_t c = 0; c < a.ncols; ++c)
         if (!known_type(a.types[c])) return "column " + std::to_string(c) + " has unknown type " + std::to_string(a.types[c]);
@@ -211,8 +212,10 @@ struct Plan {
     std::vector<Page> pages;
     std::vector<Place> places;     // ntiles * ncols
     std::vector<uint8_t> blob;     // the pages' heads, one after the other
+    std::vector<uint32_t> header_len;  // per page: the bytes of its PageHeader, the front of its head; the body starts behind
     std::vector<uint8_t> footer;   // FileMetaData, its u32 length, "PAR1"
     uint64_t out_bytes = 0, row_groups = 0, null_cells = 0;
+    uint64_t stored_bytes = 0, plain_bytes = 0;  // the row groups' total_compressed_size and total_byte_size, summed
     std::string error;             // not empty: the file is refused
 };
 
@@ -227,28 +230,33 @@ inline void put_u32(std::vector<uint8_t>& out, uint32_t v) {
 }
 
 struct ChunkMeta {
-    uint64_t first_page_at = 0, bytes = 0, rows = 0, nulls = 0;
+    uint64_t first_page_at = 0, bytes = 0, plain_bytes = 0, rows = 0, nulls = 0;  // bytes: as stored; plain_bytes: uncompressed
     MinMax mm;
 };
 
 inline int32_t parquet_type(uint32_t t) { return t == OXH_CSV_INT64 ? 2 : t == OXH_CSV_FLOAT64 ? 5 : t == OXH_CSV_BOOL ? 0 : 6; }
 
 // tiles: ceil(nrows / 1024) * ncols entries. The names are read as write_error() left them.
+// stored: NULL for an uncompressed file; else the plan of the SNAPPY file whose page k's body is stored in stored[k]
+// bytes (the pages in this function's own order: the same cuts as the uncompressed plan's, whose page_bytes counts
+// uncompressed bytes). Such a plan's pages name where the header goes (file_at, head_src, header_len) and how long
+// the stored body is (values_bytes); its chunks are codec SNAPPY, total_compressed_size the stored bytes and
+// total_uncompressed_size the headers as written plus the uncompressed bodies, the format's rule.
 inline Plan make_plan(uint64_t nrows, uint32_t ncols, const uint32_t* types, const uint8_t* names, const uint64_t* name_offsets,
-                      uint64_t rows_per_group, uint64_t page_bytes, const Tile* tiles) {
+                      uint64_t rows_per_group, uint64_t page_bytes, const Tile* tiles, const uint64_t* stored = nullptr) {
     Plan p;
     const uint64_t group_rows = group_rows_of(rows_per_group), budget = page_bytes_of(page_bytes);
     const uint64_t ntiles = (nrows + kTileRows - 1) / kTileRows, group_tiles = group_rows / kTileRows;
     p.places.resize(ntiles * ncols);
     uint64_t at = 4;  // behind "PAR1"
     struct Group {
-        uint64_t rows, at, bytes;
+        uint64_t rows, at, bytes, plain_bytes;
         std::vector<ChunkMeta> chunks;
     };
     std::vector<Group> groups;
     for (uint64_t t0 = 0; t0 < ntiles; t0 += group_tiles) {
         const uint64_t t1 = std::min(ntiles, t0 + group_tiles);
-        Group g{std::min(nrows, t1 * kTileRows) - t0 * kTileRows, at, 0, std::vector<ChunkMeta>(ncols)};
+        Group g{std::min(nrows, t1 * kTileRows) - t0 * kTileRows, at, 0, 0, std::vector<ChunkMeta>(ncols)};
         for (uint32_t c = 0; c < ncols; ++c) {
             ChunkMeta& m = g.chunks[c];
             m.first_page_at = at;
@@ -280,11 +288,14 @@ inline Plan make_plan(uint64_t nrows, uint32_t ncols, const uint32_t* types, con
                     return p.error = "a page of column " + std::to_string(c) + " has " + std::to_string(body) + " B: more than a PageHeader's int32", p;
                 Thrift th;
                 th.i32(1, 0);  // DATA_PAGE
-                th.i32(2, (int32_t)body), th.i32(3, (int32_t)body);
+                const uint64_t kept = stored ? stored[p.pages.size()] : body;
+                if (kept > kMaxPage) return p.error = "a compressed page of column " + std::to_string(c) + " has more than a PageHeader's int32", p;
+                th.i32(2, (int32_t)body), th.i32(3, (int32_t)kept);
                 th.begin(5);
                 th.i32(1, (int32_t)rows), th.i32(2, 0), th.i32(3, 3), th.i32(4, 3);  // PLAIN, RLE, RLE
                 th.end();
                 th.out.push_back(0);
+                p.header_len.push_back((uint32_t)th.out.size());
                 put_u32(th.out, (uint32_t)run);
                 if (nulls) {
                     th.varint((((rows + 7) / 8) << 1) | 1);
@@ -296,12 +307,14 @@ inline Plan make_plan(uint64_t nrows, uint32_t ncols, const uint32_t* types, con
                 pg.level_bytes = nulls ? (uint32_t)((rows + 7) / 8) : 0;
                 pg.values_bytes = vbytes, pg.rows = (uint32_t)rows, pg.nvalid = (uint32_t)valid;
                 p.blob.insert(p.blob.end(), th.out.begin(), th.out.end());
-                const uint64_t whole = pg.head_len + pg.level_bytes + vbytes;  // == the header's bytes + body
-                at += whole, m.bytes += whole, m.rows += rows, m.nulls += rows - valid;
+                const uint64_t plain_whole = pg.head_len + pg.level_bytes + vbytes;  // == the header's bytes + body
+                const uint64_t whole = stored ? p.header_len.back() + kept : plain_whole;
+                if (stored) pg.values_bytes = kept;
+                at += whole, m.bytes += whole, m.plain_bytes += plain_whole, m.rows += rows, m.nulls += rows - valid;
                 p.pages.push_back(pg);
             }
             m.mm.finish(types[c]);
-            g.bytes += m.bytes, p.null_cells += m.nulls;
+            g.bytes += m.bytes, g.plain_bytes += m.plain_bytes, p.null_cells += m.nulls;
         }
         groups.push_back(std::move(g));
     }
@@ -337,8 +350,8 @@ inline Plan make_plan(uint64_t nrows, uint32_t ncols, const uint32_t* types, con
             f.i32(1, parquet_type(types[c]));
             f.list(2, kTI32, 2), f.varint(Thrift::zigzag(0)), f.varint(Thrift::zigzag(3));  // PLAIN, RLE
             f.list(3, kTBinary, 1), f.raw_binary(names + name_offsets[c], name_offsets[c + 1] - name_offsets[c]);
-            f.i32(4, 0);  // UNCOMPRESSED
-            f.i64(5, (int64_t)m.rows), f.i64(6, (int64_t)m.bytes), f.i64(7, (int64_t)m.bytes);
+            f.i32(4, stored ? 1 : 0);  // SNAPPY, UNCOMPRESSED
+            f.i64(5, (int64_t)m.rows), f.i64(6, (int64_t)m.plain_bytes), f.i64(7, (int64_t)m.bytes);
             f.i64(9, (int64_t)m.first_page_at);
             f.begin(12);
             f.i64(3, (int64_t)m.nulls);
@@ -347,7 +360,7 @@ inline Plan make_plan(uint64_t nrows, uint32_t ncols, const uint32_t* types, con
             f.end();
             f.end();
         }
-        f.i64(2, (int64_t)g.bytes), f.i64(3, (int64_t)g.rows), f.i64(5, (int64_t)g.at), f.i64(6, (int64_t)g.bytes);
+        f.i64(2, (int64_t)g.plain_bytes), f.i64(3, (int64_t)g.rows), f.i64(5, (int64_t)g.at), f.i64(6, (int64_t)g.bytes);
         f.i16(7, (int16_t)gi);
         f.end();
     }
@@ -361,8 +374,22 @@ inline Plan make_plan(uint64_t nrows, uint32_t ncols, const uint32_t* types, con
     put_u32(p.footer, (uint32_t)meta);
     p.footer.insert(p.footer.end(), {'P', 'A', 'R', '1'});
     p.row_groups = groups.size();
+    for (const Group& g : groups) p.stored_bytes += g.bytes, p.plain_bytes += g.plain_bytes;
     p.out_bytes = at + p.footer.size();
     return p;
+}
+
+// A capacity that holds the SNAPPY file of an uncompressed plan whatever its pages hold: every body at Snappy's
+// bound (32 + n + n / 6), every PageHeader with a 5-byte compressed size, and 10 bytes more for each of the footer's
+// sizes and offsets (5 a chunk, 4 a row group), which can only grow where pages do.
+inline uint64_t snappy_capacity(const Plan& plain, uint32_t ncols) {
+    uint64_t bytes = plain.out_bytes + 10 * plain.row_groups * (5ull * ncols + 4);
+    for (size_t k = 0; k < plain.pages.size(); ++k) {
+        const Page& pg = plain.pages[k];
+        const uint64_t body = pg.head_len - plain.header_len[k] + pg.level_bytes + pg.values_bytes;
+        bytes += 32 + body / 6 + 5;
+    }
+    return bytes;
 }
 
 }  // namespace oxh::parquet

@@ -369,6 +369,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void p
     if (bad) __hip_atomic_fetch_or(&ctrl[kPqErr], bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// OXH_PARQUET_SNAPPY: page k's PageHeader, heads[k].len bytes from blob[heads[k].src ..), to out[heads[k].at ..); a
+// wave a page. The compressed bodies behind them are snappy_pack_kernel's.
+struct PqHead {
+    uint64_t at;
+    uint32_t src, len;
+};
+__global__ __launch_bounds__(64) void pqw_heads_kernel(const PqHead* __restrict__ heads, uint64_t npages, const uint8_t* __restrict__ blob, uint8_t* out) {
+    for (uint64_t k = blockIdx.x; k < npages; k += gridDim.x) copy_span_wave(out + heads[k].at, blob + heads[k].src, heads[k].len, threadIdx.x);
+}
+
 }  // namespace oxh
 
 namespace {
@@ -391,7 +401,10 @@ int device_enter(oxh_ctx* ctx) {
 // its pinned mirror live as long as the call.
 struct WriteCall {
     explicit WriteCall(hipStream_t stream) : st(stream), lease(stream) {}
-    ~WriteCall() { (void)hipStreamSynchronize(st); }
+    ~WriteCall() {
+        (void)hipStreamSynchronize(st);
+        if (d_image) (void)hipFree(d_image);
+    }
     hipStream_t st;
     oxh::ScratchLease lease;
     oxh::PqArgs args{};
@@ -404,6 +417,18 @@ struct WriteCall {
     int measure(const pq::Args& a, const void* const* d_values, const void* const* d_offsets, const uint8_t* const* d_validity,
                 const uint64_t* bits);
     int emit(uint8_t* d_out);
+    // OXH_PARQUET_SNAPPY, after measure(): compress() emits the uncompressed file into an image the call owns,
+    // compresses every page body -- one raw Snappy block each, snappy_compress.hip -- into the fragments' slots and
+    // re-plans with the streams' sizes: `stored` is the SNAPPY file's plan, stored.out_bytes its size. pack() then
+    // writes that file to d_out, every byte once: the headers (pqw_heads_kernel), the bodies (snappy_pack_kernel),
+    // the magic and the footer.
+    pq::Args a{};
+    const pq::Tile* tiles = nullptr;
+    pq::Plan stored;
+    uint8_t* d_image = nullptr;  // [the image | the page tables | the Snappy working memory]
+    uint64_t at_tab = 0, at_sizes = 0, at_status = 0, at_heads = 0, at_blob = 0, nfrags = 0;
+    int compress();
+    int pack(uint8_t* d_out);
 };
 
 int column_error(unsigned long long e) {
@@ -417,8 +442,8 @@ int column_error(unsigned long long e) {
 int WriteCall::measure(const pq::Args& a, const void* const* d_values, const void* const* d_offsets, const uint8_t* const* d_validity,
                        const uint64_t* bits) {
     const uint64_t n = a.nrows, ntiles = (n + pq::kTileRows - 1) / pq::kTileRows, items = ntiles * a.ncols;
-    std::vector<pq::Tile> none;
-    const pq::Tile* tiles = none.data();
+    this->a = a;
+    tiles = nullptr;
     if (n) {
         // [ctrl | columns] [tiles] [places | pages | heads]
         const uint64_t cols_at = oxh::kPqCtrlWords * 8, small = align256(cols_at + a.ncols * sizeof(oxh::PqCol));
@@ -454,6 +479,8 @@ int WriteCall::measure(const pq::Args& a, const void* const* d_values, const voi
         if (rc) return rc;
         tiles = (const pq::Tile*)(h_base + tiles_at);
     }
+    static const pq::Tile none{};
+    if (!tiles) tiles = &none;  // never read: there is no tile
     plan = pq::make_plan(n, a.ncols, a.types, a.names, a.name_offsets, a.rows_per_group, a.page_bytes, tiles);
     if (!plan.error.empty()) return fail(OXH_ERR_INVALID, "parquet write: " + plan.error);
     STEP("parquet write: %llu rows x %u columns, %llu B, %llu row groups, %llu pages", (unsigned long long)n, a.ncols,
@@ -485,9 +512,89 @@ int WriteCall::emit(uint8_t* d_out) {
     return OXH_OK;
 }
 
-void report(const pq::Args& a, const WriteCall& call) {
-    *a.out_bytes = call.plan.out_bytes;
-    a.stats4[0] = call.plan.out_bytes, a.stats4[1] = call.plan.row_groups;
+int WriteCall::compress() {
+    const uint64_t np = plan.pages.size();
+    if (!np) return stored = plan, OXH_OK;  // no page: the file is the magic and the footer
+    std::vector<uint64_t> tab(2 * np), frag0(np + 1), kept(np);
+    std::vector<uint32_t> frag_block, frag_size;
+    for (uint64_t k = 0; k < np; ++k) {
+        const pq::Page& pg = plan.pages[k];
+        tab[k] = pg.file_at + plan.header_len[k], tab[np + k] = pg.file_at + pg.head_len + pg.level_bytes + pg.values_bytes;
+        frag0[k] = frag_block.size();
+        frag_block.insert(frag_block.end(), oxh::snappy_fragments(tab[np + k] - tab[k]), (uint32_t)k);
+    }
+    frag0[np] = nfrags = frag_block.size();
+    frag_size.resize(nfrags);
+    const uint64_t up16 = 15;
+    at_tab = (plan.out_bytes + up16) & ~up16, at_sizes = at_tab + 4 * np * 8, at_status = at_sizes + np * 8;
+    at_heads = (at_status + np * 4 + up16) & ~up16, at_blob = at_heads + np * sizeof(oxh::PqHead);
+    const oxh::SnappyLayout lay(at_blob + np * 64, np, nfrags);  // a PageHeader is below 64 bytes
+    if (hipMalloc(&d_image, lay.total) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(OXH_ERR_NOMEM, "parquet write: " + std::to_string(lay.total) + " B for the uncompressed image and the Snappy fragments");
+    }
+    oxh::poison_device(d_image, lay.total, st);
+    int rc = emit(d_image);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(d_image + at_tab, tab.data(), 2 * np * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_image + lay.at_frag0, frag0.data(), (np + 1) * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_image + lay.at_block, frag_block.data(), nfrags * 4, hipMemcpyHostToDevice, st));
+    const uint64_t* d_lo = (const uint64_t*)(d_image + at_tab);
+    if ((rc = oxh::snappy_fragments_enqueue(d_image, d_lo, d_lo + np, lay.work(d_image, nfrags), st))) return rc;
+    unsigned long long ctrl = 0;
+    HIP_TRY(hipMemcpyAsync(frag_size.data(), d_image + lay.at_size, nfrags * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&ctrl, d_image + lay.at_ctrl, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (ctrl) return fail(OXH_ERR_HIP, "parquet write: a page's Snappy fragment passed its slot");
+    for (uint64_t k = 0; k < np; ++k) {
+        kept[k] = pq::varint_len(tab[np + k] - tab[k]);
+        for (uint64_t f = frag0[k]; f < frag0[k + 1]; ++f) kept[k] += frag_size[f];
+    }
+    stored = pq::make_plan(a.nrows, a.ncols, a.types, a.names, a.name_offsets, a.rows_per_group, a.page_bytes, tiles, kept.data());
+    if (!stored.error.empty()) return fail(OXH_ERR_INVALID, "parquet write: " + stored.error);
+    if (stored.pages.size() != np) return fail(OXH_ERR_HIP, "parquet write: the SNAPPY plan has other pages than the uncompressed one");
+    return OXH_OK;
+}
+
+int WriteCall::pack(uint8_t* d_out) {
+    const uint64_t np = plan.pages.size();
+    if (!np) return emit(d_out);
+    std::vector<uint64_t> tab(2 * np);
+    std::vector<oxh::PqHead> heads(np);
+    std::vector<uint8_t> blob;
+    std::vector<uint32_t> status(np);
+    for (uint64_t k = 0; k < np; ++k) {
+        const pq::Page& pg = stored.pages[k];
+        const uint32_t len = stored.header_len[k];
+        heads[k] = oxh::PqHead{pg.file_at, (uint32_t)blob.size(), len};
+        blob.insert(blob.end(), stored.blob.begin() + pg.head_src, stored.blob.begin() + pg.head_src + len);
+        tab[k] = pg.file_at + len, tab[np + k] = pg.file_at + len + pg.values_bytes;
+    }
+    if (blob.size() > np * 64) return fail(OXH_ERR_HIP, "parquet write: the page headers outgrew their room");
+    const oxh::SnappyLayout lay(at_blob + np * 64, np, nfrags);
+    HIP_TRY(hipMemcpyAsync(d_out, "PAR1", 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_out + stored.out_bytes - stored.footer.size(), stored.footer.data(), stored.footer.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_image + at_tab + 2 * np * 8, tab.data(), 2 * np * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_image + at_heads, heads.data(), np * sizeof(oxh::PqHead), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_image + at_blob, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+    const uint64_t* d_lo = (const uint64_t*)(d_image + at_tab);
+    int rc = oxh::snappy_pack_enqueue(d_lo, d_lo + np, d_out, d_lo + 2 * np, d_lo + 3 * np, (uint64_t*)(d_image + at_sizes),
+                                      (uint32_t*)(d_image + at_status), np, false, lay.work(d_image, nfrags), st);
+    if (rc) return rc;
+    oxh::pqw_heads_kernel<<<(unsigned)std::min<uint64_t>(np, oxh::kPqMaxGroups), 64, 0, st>>>((const oxh::PqHead*)(d_image + at_heads), np, d_image + at_blob, d_out);
+    HIP_TRY(hipGetLastError());
+    unsigned long long ctrl = 0;
+    HIP_TRY(hipMemcpyAsync(status.data(), d_image + at_status, np * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&ctrl, d_image + lay.at_ctrl, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (ctrl || std::any_of(status.begin(), status.end(), [](uint32_t s) { return s != 0; }))
+        return fail(OXH_ERR_HIP, "parquet write: a page's Snappy stream is not what was planned");
+    return OXH_OK;
+}
+
+void report(const pq::Args& a, const WriteCall& call, uint64_t bytes) {
+    *a.out_bytes = bytes;
+    a.stats4[0] = bytes, a.stats4[1] = call.plan.row_groups;
     a.stats4[2] = call.plan.pages.size(), a.stats4[3] = call.plan.null_cells;
 }
 
@@ -512,9 +619,17 @@ int oxh_write_parquet_device(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const
     if (rc) return rc;
     WriteCall call((hipStream_t)stream);
     if ((rc = call.measure(a, d_values, d_offsets, d_validity, bit_offsets))) return rc;
-    const uint64_t need = call.plan.out_bytes;
-    if (d_out && capacity >= need && (rc = call.emit(d_out))) return rc;
-    report(a, call);
+    const bool snappy = flags & pq::kFlagSnappy;
+    // with the flag the size is known only after compressing: `need` is a capacity that always suffices
+    const uint64_t need = snappy ? pq::snappy_capacity(call.plan, ncols) : call.plan.out_bytes;
+    if (d_out && capacity >= need && (rc = snappy ? call.compress() : call.emit(d_out))) return rc;
+    if (snappy && d_out && capacity >= need) {
+        if (call.stored.out_bytes > capacity) return fail(OXH_ERR_HIP, "parquet write: the SNAPPY file passed its bound");
+        if ((rc = call.pack(d_out))) return rc;
+        report(a, call, call.stored.out_bytes);
+        return OXH_OK;
+    }
+    report(a, call, need);
     return d_out && capacity < need ? too_small(a, need) : OXH_OK;
 }
 
@@ -557,19 +672,25 @@ int oxh_write_parquet_host(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const u
         WriteCall call(st);
         int r = call.measure(a, d_values.data(), d_offsets.data(), d_validity.data(), bits.data());
         if (r) return r;
-        need = call.plan.out_bytes;
+        const bool snappy = flags & pq::kFlagSnappy;
+        need = snappy ? pq::snappy_capacity(call.plan, ncols) : call.plan.out_bytes;
         fits = out && capacity >= need;
+        uint64_t bytes = need;
         if (fits) {
-            if (hipMalloc(&d_out, need) != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(OXH_ERR_NOMEM, "parquet write: " + std::to_string(need) + " B for the file on the device");
+            if (snappy) {
+                if ((r = call.compress())) return r;
+                if ((bytes = call.stored.out_bytes) > capacity) return fail(OXH_ERR_HIP, "parquet write: the SNAPPY file passed its bound");
             }
-            oxh::poison_device(d_out, need, st);
-            if ((r = call.emit(d_out))) return r;
-            HIP_TRY(hipMemcpyAsync(out, d_out, need, hipMemcpyDeviceToHost, st));
+            if (hipMalloc(&d_out, bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(OXH_ERR_NOMEM, "parquet write: " + std::to_string(bytes) + " B for the file on the device");
+            }
+            oxh::poison_device(d_out, bytes, st);
+            if ((r = snappy ? call.pack(d_out) : call.emit(d_out))) return r;
+            HIP_TRY(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
         }
-        report(a, call);
+        report(a, call, bytes);
         return OXH_OK;
     }();
     if (rc != OXH_OK) (void)hipStreamSynchronize(st);

@@ -24,6 +24,7 @@
 // length before its cell exists. A copy's source is inside [0, produced) before any load: 0 < offset <= produced.
 #include "capi_internal.hpp"
 #include "columns.hpp"
+#include "snappy_wave.hpp"  // snp_lds_order, snp_span_wave
 
 namespace oxh {
 
@@ -35,34 +36,11 @@ constexpr unsigned kSnappyMaxGroups = 2048;
 constexpr uint32_t kLiteral = 0, kCopy = 1, kNone = 2;
 }  // namespace snp
 
-__device__ __forceinline__ void snp_lds_order() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // The wave's global stores so far are visible to its loads from here on.
 __device__ __forceinline__ void snp_global_order() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-// Exactly n bytes by the 64 lanes: the bytes up to the destination's 16-byte grid a lane each, then 16 bytes a lane
-// (any source alignment, aligned stores), then the last bytes a lane each. ZERO: zeros, src is not read.
-template <bool ZERO>
-__device__ __forceinline__ void snp_span_wave(uint8_t* dst, const uint8_t* src, uint64_t n, unsigned lane) {
-    uint64_t head = (16 - ((uintptr_t)dst & 15)) & 15;
-    if (head > n) head = n;
-    if (lane < head) dst[lane] = ZERO ? (uint8_t)0 : src[lane];
-    const uint64_t body = (n - head) & ~15ull;
-    for (uint64_t b = head + 16ull * lane; b < head + body; b += 16ull * 64) {
-        ulonglong2 v{0, 0};
-        if (!ZERO) v.x = ld64u(src + b), v.y = ld64u(src + b + 8);
-        *reinterpret_cast<ulonglong2*>(dst + b) = v;
-    }
-    const uint64_t tail = head + body;
-    if (tail + lane < n) dst[tail + lane] = ZERO ? (uint8_t)0 : src[tail + lane];
 }
 
 // Block b: src_all[src_lo[b], src_hi[b]) inflates to dst_all[dst_lo[b], dst_hi[b]); status[b] = 0 or the cause;

@@ -42,10 +42,12 @@ or more frames written one after the other, as copies -- `concat`, `concat_devic
 `oxh_write_csv_*` writes them back as the file's bytes, which is how every path of the reference ends (`write_df`,
 core/df/tabular.rs:1492-1547) -- `write_csv`, `write_csv_device`, `write_df`; `oxh_write_json_*` as JSON Lines or one
 JSON array (`write_df`'s jsonl / ndjson / json arms, and the text of a data-frame view) -- `write_jsonl`, `write_json` and
-their `_device` forms; `oxh_write_parquet_*` as an uncompressed Parquet file (what `write_df`'s parquet arm is for) --
+their `_device` forms; `oxh_write_parquet_*` as a Parquet file, uncompressed or with SNAPPY pages (what `write_df`'s parquet arm is for) --
 `write_parquet`, `write_parquet_device`; and `oxh_parquet_*` read such a file back (`ParquetFile`, `read_parquet`,
 `read_parquet_device`, `parquet_shape`, `parquet_schema`), SNAPPY pages included: `oxh_snappy_inflate_*` inflate many raw
-Snappy blocks per call (`snappy_inflate`, `snappy_inflate_device`) and the Parquet open runs the same kernel.
+Snappy blocks per call (`snappy_inflate`, `snappy_inflate_device`) and the Parquet open runs the same kernel;
+`oxh_snappy_compress_*` compress many blocks per call to such streams (`snappy_compress`, `snappy_compress_device`,
+`snappy_bound`).
 
 A frame is an ordered mapping from column name to `Column`. A row's bytes are, over the columns in the
 frame's order: nothing for a null, the raw little-endian bytes of Int8 / Int32 / Float32 / Int64 /
@@ -2402,10 +2404,13 @@ class ParquetWriteStats(NamedTuple):
     nulls: int
 
 
-def _parquet_head(frame: Mapping, rows_per_group, page_bytes, types):
+def _parquet_head(frame: Mapping, rows_per_group, page_bytes, types, compression=None):
     # the columns, types and names as the CSV writer's call takes them; its own tail (separator, quote, header) is not used
+    if compression not in (None, "none", "snappy"):
+        raise _capi.OxenError(f"compression {compression!r}: None, 'none' or 'snappy'", _capi.OXH_ERR_INVALID)
     cols, type_words, name_bytes, name_offsets, _ = _write_head(frame, ",", '"', True, types)
-    return cols, type_words, name_bytes, name_offsets, (int(rows_per_group or 0), int(page_bytes or 0), 0)
+    flags = _capi.OXH_PARQUET_SNAPPY if compression == "snappy" else 0
+    return cols, type_words, name_bytes, name_offsets, (int(rows_per_group or 0), int(page_bytes or 0), flags)
 
 
 def _parquet_call(*args):
@@ -2414,14 +2419,16 @@ def _parquet_call(*args):
 
 
 def write_parquet(frame: Mapping, path=None, rows_per_group=None, page_bytes=None, types=None, ctx: Optional[_capi.Context] = None,
-                  with_stats: bool = False):
+                  with_stats: bool = False, compression=None):
     """oxh_write_parquet_host: the frame (an ordered {name: Column}, or what `column` takes, in host memory) as the bytes
     of a Parquet file by the rules of include/oxen_hash.h "Parquet" -- uncompressed, PLAIN values, DataPage V1, what
     `write_df`'s parquet arm (core/df/tabular.rs:1508-1517) is for; polars, pyarrow and DuckDB read it. rows_per_group
     (None: 1 048 576; a multiple of 1 024) and page_bytes (None: 1 MiB) cut the row groups and pages. path, types and
-    the key order are `write_csv`'s. `write_df` itself still refuses `.parquet`: this is the entry."""
+    the key order are `write_csv`'s. compression: None or "none", or "snappy" (OXH_PARQUET_SNAPPY: every page body one raw
+    Snappy block, compressed on the device; the first call then gives a capacity that suffices, the second the size).
+    `write_df` itself still refuses `.parquet`: this is the entry."""
     frame = _as_frame(frame)
-    cols, type_words, name_bytes, name_offsets, tail = _parquet_head(frame, rows_per_group, page_bytes, types)
+    cols, type_words, name_bytes, name_offsets, tail = _parquet_head(frame, rows_per_group, page_bytes, types, compression)
     keep = []
 
     def ptr(a):
@@ -2445,15 +2452,16 @@ def write_parquet(frame: Mapping, path=None, rows_per_group=None, page_bytes=Non
 
 
 def write_parquet_device(frame: Mapping, rows_per_group=None, page_bytes=None, types=None, ctx: Optional[_capi.Context] = None,
-                         capacity: Optional[int] = None, stream=None, with_stats: bool = False):
+                         capacity: Optional[int] = None, stream=None, with_stats: bool = False, compression=None):
     """oxh_write_parquet_device over device `Column`s; the file's bytes as a uint8 torch tensor on the device. It
     measures, allocates, then writes; a caller's `capacity` (bytes) skips the measure, and a capacity below the need is
-    the library's error. Blocks."""
+    the library's error. compression as `write_parquet`'s: with "snappy" the tensor is allocated at the bound and
+    returned sliced to the file's size. Blocks."""
     import torch
 
     from .device import _require_cuda, _stream
 
-    cols, type_words, name_bytes, name_offsets, tail = _parquet_head(frame, rows_per_group, page_bytes, types)
+    cols, type_words, name_bytes, name_offsets, tail = _parquet_head(frame, rows_per_group, page_bytes, types, compression)
     tensors = [t for c in cols for t in (c.values, c.offsets, c.validity) if t is not None]
     _require_cuda(*tensors)
     if any(not t.is_contiguous() for t in tensors):
@@ -2946,6 +2954,52 @@ def snappy_inflate_device(d_src, d_src_offsets, d_dst, d_dst_offsets, d_status, 
     _capi.check(_capi.lib().oxh_snappy_inflate_device(_handle(ctx), n, d_src.data_ptr(), d_src_offsets.data_ptr(), d_dst.data_ptr(), d_dst_offsets.data_ptr(),
                                                       d_status.data_ptr(), ctypes.byref(bad), _stream(stream)), "oxh_snappy_inflate_device")
     return int(bad.value)
+
+
+# ---------------------------------------------------------------- Snappy, compress: blocks to raw streams in one call (oxh_snappy_compress_*)
+def snappy_bound(n: int) -> int:
+    """oxh_snappy_bound: a destination of this many bytes always holds the stream of a block of n bytes (32 + n + n / 6)."""
+    return int(_capi.lib().oxh_snappy_bound(int(n)))
+
+
+def snappy_compress(blocks, ctx: Optional[_capi.Context] = None) -> list:
+    """oxh_snappy_compress_host: every block (bytes) compressed on the device in one call to a raw Snappy stream, as a
+    list of bytes; `snappy_inflate`, or any decoder of the raw format, gives the blocks back (include/oxen_hash.h
+    "Snappy, compress")."""
+    blocks = [bytes(b) for b in blocks]
+    n = len(blocks)
+    src = np.frombuffer(b"".join(blocks) or b"\0", dtype=np.uint8)
+    src_offsets = np.concatenate([[0], np.cumsum([len(b) for b in blocks])]).astype(np.uint64)
+    dst_offsets = np.concatenate([[0], np.cumsum([snappy_bound(len(b)) for b in blocks])]).astype(np.uint64)
+    dst, sizes, status = np.zeros(max(int(dst_offsets[-1]), 1), dtype=np.uint8), np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint32)
+    _capi.check(_capi.lib().oxh_snappy_compress_host(_handle(ctx), n, src.ctypes.data, src_offsets.ctypes.data_as(_capi._u64p), dst.ctypes.data,
+                                                     dst_offsets.ctypes.data_as(_capi._u64p), sizes.ctypes.data_as(_capi._u64p),
+                                                     status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))), "oxh_snappy_compress_host")
+    if status[:n].any():   # the ranges are this function's own
+        raise _capi.OxenError(f"snappy compress: block {int(np.flatnonzero(status[:n])[0])} was refused", _capi.OXH_ERR_INVALID)
+    return [dst[int(dst_offsets[k]):int(dst_offsets[k]) + int(sizes[k])].tobytes() for k in range(n)]
+
+
+def snappy_compress_device(d_src, d_src_offsets, d_dst, d_dst_offsets, d_sizes, d_status, ctx: Optional[_capi.Context] = None, stream=None) -> None:
+    """oxh_snappy_compress_device over torch tensors on the device: block b of d_src (uint8) between d_src_offsets[b] and
+    [b + 1] (int64 / uint64, n + 1 of them) is compressed to the start of d_dst between d_dst_offsets[b] and [b + 1], a
+    range of at least `snappy_bound` of the block; d_sizes (n int64 / uint64) receives the streams' lengths and d_status
+    (n int32 / uint32) 0 or 7, a range that decreases or is below the bound. Blocks."""
+    from .device import _require_cuda, _stream
+
+    for t in (d_src, d_src_offsets, d_dst, d_dst_offsets, d_sizes, d_status):
+        _require_cuda(t)
+        if not t.is_contiguous():
+            raise _capi.OxenError("the Snappy tensors are contiguous", _capi.OXH_ERR_INVALID)
+    if (d_src.element_size() != 1 or d_dst.element_size() != 1 or d_src_offsets.element_size() != 8 or d_dst_offsets.element_size() != 8
+            or d_sizes.element_size() != 8 or d_status.element_size() != 4):
+        raise _capi.OxenError("uint8 bytes, 8-byte offsets and sizes and 4-byte statuses", _capi.OXH_ERR_INVALID)
+    n = d_status.numel()
+    if d_src_offsets.numel() != n + 1 or d_dst_offsets.numel() != n + 1 or d_sizes.numel() != n:
+        raise _capi.OxenError("one more offset than blocks in both tables, and a size a block", _capi.OXH_ERR_INVALID)
+    _capi.check(_capi.lib().oxh_snappy_compress_device(_handle(ctx), n, d_src.data_ptr(), d_src_offsets.data_ptr(), d_dst.data_ptr(),
+                                                       d_dst_offsets.data_ptr(), d_sizes.data_ptr(), d_status.data_ptr(), _stream(stream)),
+                "oxh_snappy_compress_device")
 
 
 def read_df(path, ctx: Optional[_capi.Context] = None) -> dict:
