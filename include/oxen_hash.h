@@ -1363,8 +1363,9 @@ int oxh_jsonl_columns_host(void* jsonl, uint32_t nsel, const uint32_t* col_idx, 
  *     OXH_CSV_STRING64 on a BYTE_ARRAY column. OXH_CSV_INT32 and OXH_CSV_FLOAT32 give the narrow kinds as they are
  *     (4-byte cells, values 4-byte aligned); only these entries know the two words, every writer refuses them.
  *   Compression. Without OXH_PARQUET_INFLATE only UNCOMPRESSED chunks (codec 0) are read. With it, SNAPPY chunks
- *     (codec 1) too, chunk by chunk, to the same columns: at open every compressed page is inflated ("Snappy" below,
- *     the same kernel) into an image the handle owns, and the column entries read a page's body from the file or from
+ *     (codec 1) too, and with OXH_PARQUET_INFLATE_ZSTD ZSTD chunks (codec 6), chunk by chunk -- a file may mix them
+ *     --, to the same columns: at open every compressed page is inflated ("Snappy" and "Zstandard" below, the same
+ *     kernels, one launch per codec) into an image the handle owns, and the column entries read a page's body from the file or from
  *     the image. Dictionary pages and V1 data pages are compressed whole (a V1 page's level length is the first 4
  *     bytes of the inflated body); a V2 page's repetition and definition level bytes are stored as they are and are
  *     copied into the image in front of the inflated values, so that the page is contiguous; a V2 page whose
@@ -1378,7 +1379,7 @@ int oxh_jsonl_columns_host(void* jsonl, uint32_t nsel, const uint32_t* col_idx, 
  *     column is selected: INT96 and FIXED_LEN_BYTE_ARRAY (known from the footer: oxh_parquet_types says so), and what
  *     only the pages show -- DELTA_* and BYTE_STREAM_SPLIT or any other value encoding, repetition levels, level
  *     encodings other than RLE, index pages. An unselected column of these does not stop the others.
- *   Stated and not built: zstd (polars' default), gzip, lz4 and brotli; inflating only the columns that are read;
+ *   Stated and not built: gzip, lz4 and brotli; inflating only the columns that are read;
  *     row-range and row-group selection; page and column
  *     indexes; statistics pushdown; the `.arrow` form.
  *
@@ -1394,19 +1395,20 @@ int oxh_jsonl_columns_host(void* jsonl, uint32_t nsel, const uint32_t* col_idx, 
  * index 0 --, a PLAIN page shorter than its values) makes oxh_parquet_columns_* return OXH_ERR_INVALID.
  *   stats8 = {rows, ncols, row groups, data pages, dictionary pages, footer bytes, columns this reader cannot read,
  *   pages inflated (0 for a file without a compressed page)}.
- * oxh_parquet_open_*: flags is 0 or OXH_PARQUET_INFLATE (bit 0 stays reserved). OXH_ERR_INVALID, every message starting with "parquet open:", in this order:
+ * oxh_parquet_open_*: flags is 0 or any of OXH_PARQUET_INFLATE and OXH_PARQUET_INFLATE_ZSTD (bit 0 stays reserved). OXH_ERR_INVALID, every message starting with "parquet open:", in this order:
  * unknown flags; NULL bytes with nbytes > 0; NULL out; NULL stats8; then the footer's refusals -- fewer than 12
  * bytes; the magic PARE (encrypted); a tail, then a head, that is not PAR1; a footer length larger than the file; a
  * footer that is no FileMetaData; an encrypted footer; a schema without a root; a nested field; a repeated field;
  * more than 2^40 rows; per row group, in order: a chunk count that is not the schema's, a chunk without plain
- * metadata, a codec other than UNCOMPRESSED (with OXH_PARQUET_INFLATE: other than that and SNAPPY), a chunk that is not inside the file in front of the footer, a
+ * metadata, a codec other than UNCOMPRESSED (with OXH_PARQUET_INFLATE: other than that and SNAPPY; with OXH_PARQUET_INFLATE_ZSTD: and ZSTD), a chunk that is not inside the file in front of the footer, a
  * num_values that is not the group's rows; group rows that do not sum to num_rows. Chunks are NOT checked against
  * their neighbours: chunks that overlap are read as they stand (every load stays inside its own chunk). In the host form the footer is in
  * host memory and its refusals come BEFORE OXH_ERR_NODEVICE; in the device form it has to come down first, so
  * OXH_ERR_NODEVICE and a NULL ctx come before them. Then the page walk: a page header that runs past its chunk,
  * negative sizes, sizes that differ on a page that is not compressed, or pages whose values do not sum to the chunk's
  * num_values are OXH_ERR_INVALID. Then, from the page table and before the image is allocated: a compressed page
- * whose uncompressed size is above 22 * its compressed size + 32 (no Snappy stream expands more than 64 / 3) is
+ * whose uncompressed size is above 22 * its compressed size + 32 (no Snappy stream expands more than 64 / 3), or in
+ * a ZSTD chunk above 128 KiB for every 3 bytes of it (a block costs 3 bytes and yields at most 128 KiB), is
  * OXH_ERR_INVALID and names the column; after the inflation a page whose stream is malformed is OXH_ERR_INVALID and
  * names the column and the cause. A failed allocation -- the image among them -- is OXH_ERR_NOMEM with the outputs
  * untouched.
@@ -1422,6 +1424,7 @@ int oxh_jsonl_columns_host(void* jsonl, uint32_t nsel, const uint32_t* col_idx, 
 #define OXH_CSV_INT32 6   /* oxh_parquet_columns_* only */
 #define OXH_CSV_FLOAT32 7 /* oxh_parquet_columns_* only */
 #define OXH_PARQUET_INFLATE 2u /* flags of oxh_parquet_open_*: read SNAPPY chunks too */
+#define OXH_PARQUET_INFLATE_ZSTD 4u /* flags of oxh_parquet_open_*: read ZSTD chunks too */
 int oxh_parquet_open_device(oxh_ctx* ctx, const uint8_t* d_bytes, uint64_t nbytes, uint32_t flags, void** out, uint64_t* stats8, void* stream);
 int oxh_parquet_open_host(oxh_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, uint32_t flags, void** out, uint64_t* stats8);
 int oxh_parquet_close(void* parquet);
@@ -1478,6 +1481,61 @@ int oxh_snappy_inflate_device(oxh_ctx* ctx, uint64_t nblocks, const uint8_t* d_s
                               const uint64_t* d_dst_offsets, uint32_t* d_status, uint64_t* bad_blocks, void* stream);
 int oxh_snappy_inflate_host(oxh_ctx* ctx, uint64_t nblocks, const uint8_t* src, const uint64_t* src_offsets, uint8_t* dst,
                             const uint64_t* dst_offsets, uint32_t* status, uint64_t* bad_blocks);
+
+/* ---------------------------------------------------------------- Zstandard: many frames inflated per call
+ * What a ZSTD Parquet page holds (polars writes that codec by default, so every Parquet file Oxen itself writes), and
+ * what oxh_parquet_open_* with OXH_PARQUET_INFLATE_ZSTD runs over every compressed page of a ZSTD chunk. One
+ * Zstandard frame (RFC 8878) a block:
+ *   Frame header. The magic FD2FB528; every Frame_Header_Descriptor form: single segment or a Window_Descriptor, a
+ *     Frame_Content_Size that is absent or 1, 2, 4 or 8 bytes wide (a content size that is present must be the
+ *     block's expected length), the content-checksum flag. The window size is NOT a limit: an offset may reach any
+ *     byte of the frame's output so far. A dictionary id other than 0, the reserved bit and a skippable frame are
+ *     refused; so are bytes behind the frame's end (a second frame is not read).
+ *   Blocks. Raw, RLE and Compressed, at most 128 KiB each, up to the Last_Block bit. Literals: Raw, RLE, Huffman
+ *     with 1 and 4 streams, treeless (the table of the frame's previous Huffman block); weights FSE-compressed or
+ *     direct; codes of at most 11 bits. Sequences: the 1, 2 and 3-byte counts and 0; the Predefined, RLE,
+ *     FSE_Compressed and Repeat modes for each of the literal-length, offset and match-length codes (accuracy logs up
+ *     to 9, 8, 9); offset codes up to 31; the three repeat offsets with the shifted meaning at literal length 0.
+ *   NOT verified: the content checksum -- its 4 bytes are skipped; the window size; that a stream's unused
+ *     probability or weight forms follow the encoder's conventions beyond what decoding needs.
+ * The parameters, the block list, alignment, blocking, the streams and the argument checks (in the same order, every
+ * message starting with "zstd inflate:") are oxh_snappy_inflate_*'s. The length of dst's range is the frame's EXPECTED
+ * length: a frame without a content size has no length of its own. Source and destination ranges are below 2^32
+ * bytes each. status[b] = 0, or the first cause that ends the frame, whose whole destination is then zeros:
+ *   OXH_ZSTD_FRAME      not the magic; a skippable frame, a dictionary id, the reserved bit; bytes behind the frame;
+ *   OXH_ZSTD_HEADER     a content size that is not the expected length;
+ *   OXH_ZSTD_INPUT      the frame header, a block header, a block or the checksum leaves the input;
+ *   OXH_ZSTD_BLOCK      the reserved block type, a block above 128 KiB, a section that leaves its block;
+ *   OXH_ZSTD_LITERALS   Huffman: a tree description that is none (weights above 11, a sum that no last weight
+ *                       completes to a power of two), a treeless block without a table, stream sizes that do not
+ *                       fit, a stream that is not consumed exactly, more than 128 KiB of literals;
+ *   OXH_ZSTD_TABLE      FSE: an accuracy log above the maximum, probabilities that overrun or underrun the total, a
+ *                       zero-repeat run past the alphabet, an RLE symbol outside it, Repeat without a table;
+ *   OXH_ZSTD_SEQUENCES  no count, reserved mode bits, a bitstream without an end mark, one that ends before its
+ *                       sequences do or holds bits behind them, literal lengths above the literals;
+ *   OXH_ZSTD_OFFSET     an offset of 0 or larger than the bytes produced so far;
+ *   OXH_ZSTD_OVERRUN    a block, a literals section or a sequence that would pass the expected length;
+ *   OXH_ZSTD_TRUNCATED  the last block ends before the expected length is reached;
+ *   OXH_ZSTD_RANGE      device form: the block's offsets decrease, or a range of 2^32 bytes and more.
+ * No byte outside a block's own destination is written and none outside its own input is read, whatever the frame
+ * holds; the same frame gives the same bytes every run. Working memory: 128 KiB per resident wave (at most 512) for
+ * decoded literals, from the device's scratch (device form) or the call's own block (host form).
+ *   Stated and not built: checksum verification; dictionaries; concatenated and skippable frames; a compressor. */
+#define OXH_ZSTD_FRAME 1
+#define OXH_ZSTD_HEADER 2
+#define OXH_ZSTD_INPUT 3
+#define OXH_ZSTD_BLOCK 4
+#define OXH_ZSTD_LITERALS 5
+#define OXH_ZSTD_TABLE 6
+#define OXH_ZSTD_SEQUENCES 7
+#define OXH_ZSTD_OFFSET 8
+#define OXH_ZSTD_OVERRUN 9
+#define OXH_ZSTD_TRUNCATED 10
+#define OXH_ZSTD_RANGE 11
+int oxh_zstd_inflate_device(oxh_ctx* ctx, uint64_t nblocks, const uint8_t* d_src, const uint64_t* d_src_offsets, uint8_t* d_dst,
+                            const uint64_t* d_dst_offsets, uint32_t* d_status, uint64_t* bad_blocks, void* stream);
+int oxh_zstd_inflate_host(oxh_ctx* ctx, uint64_t nblocks, const uint8_t* src, const uint64_t* src_offsets, uint8_t* dst,
+                          const uint64_t* dst_offsets, uint32_t* status, uint64_t* bad_blocks);
 
 /* ---------------------------------------------------------------- Snappy, compress: many blocks to raw streams per call
  * The counterpart of the inflate above: a caller who holds bytes in HBM gets raw Snappy blocks ("Snappy" states the

@@ -76,6 +76,8 @@ OXH_JSON_LINES = 0      # flags of oxh_write_json_*: one object per row and line
 OXH_JSON_ARRAY = 1      # one array of the rows' objects
 OXH_PARQUET_SNAPPY = 2   # flags of oxh_write_parquet_*: every page body one raw Snappy block
 OXH_PARQUET_INFLATE = 2  # flags of oxh_parquet_open_*: read SNAPPY chunks too
+OXH_PARQUET_INFLATE_ZSTD = 4  # flags of oxh_parquet_open_*: read ZSTD chunks too
+OXH_ZSTD_CAUSES = ("", "frame", "header", "input", "block", "literals", "table", "sequences", "offset", "overrun", "truncated", "range")   # OXH_ZSTD_* by number
 OXH_SNAPPY_CAUSES = ("", "preamble", "input", "offset zero", "offset beyond", "overrun", "truncated", "range")   # OXH_SNAPPY_* by number
 
 _u64 = ctypes.c_uint64
@@ -249,6 +251,8 @@ SIGNATURES = {
                                         ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u64p, _u64p]),
     "oxh_snappy_inflate_device": (_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64p, _vp]),
     "oxh_snappy_inflate_host": (_int, [_vp, _u64, _vp, _u64p, _vp, _u64p, ctypes.POINTER(_u32), _u64p]),
+    "oxh_zstd_inflate_device": (_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64p, _vp]),
+    "oxh_zstd_inflate_host": (_int, [_vp, _u64, _vp, _u64p, _vp, _u64p, ctypes.POINTER(_u32), _u64p]),
     "oxh_snappy_bound": (_u64, [_u64]),
     "oxh_snappy_compress_device": (_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "oxh_snappy_compress_host": (_int, [_vp, _u64, _vp, _u64p, _vp, _u64p, _u64p, ctypes.POINTER(_u32)]),

@@ -334,6 +334,109 @@ int oxh_snappy_inflate_host(oxh_ctx* ctx, uint64_t nblocks, const uint8_t* src, 
     return rc;
 }
 
+// ---------------------------------------------------------------- Zstandard (the kernel: zstd_inflate.hip)
+static int zstd_args(uint64_t nblocks, const void* src, const void* src_offsets, const void* dst_offsets, const void* status,
+                     const uint64_t* bad_blocks) {
+    if (!bad_blocks) return fail(OXH_ERR_INVALID, "zstd inflate: bad_blocks is NULL");
+    if (nblocks == 0) return OXH_OK;
+    if (nblocks > 0xFFFFFFFFull) return fail(OXH_ERR_INVALID, "zstd inflate: more than 2^32 blocks");
+    if (!src) return fail(OXH_ERR_INVALID, "zstd inflate: src is NULL");
+    if (!src_offsets) return fail(OXH_ERR_INVALID, "zstd inflate: src_offsets is NULL");
+    if (!dst_offsets) return fail(OXH_ERR_INVALID, "zstd inflate: dst_offsets is NULL");
+    if (!status) return fail(OXH_ERR_INVALID, "zstd inflate: status is NULL");
+    return OXH_OK;
+}
+
+static int zstd_enter(oxh_ctx* ctx) {
+    int rc = check_device(ctx ? ctx->device : 0);  // there is no CPU path
+    if (rc) return rc;
+    if (!ctx) return fail(OXH_ERR_INVALID, "zstd inflate: ctx is NULL");
+    HIP_TRY(hipSetDevice(ctx->device));
+    return OXH_OK;
+}
+
+int oxh_zstd_inflate_device(oxh_ctx* ctx, uint64_t nblocks, const uint8_t* d_src, const uint64_t* d_src_offsets, uint8_t* d_dst,
+                            const uint64_t* d_dst_offsets, uint32_t* d_status, uint64_t* bad_blocks, void* stream) {
+    int rc = zstd_args(nblocks, d_src, d_src_offsets, d_dst_offsets, d_status, bad_blocks);
+    if (rc) return rc;
+    if (nblocks == 0) return *bad_blocks = 0, OXH_OK;
+    if ((rc = zstd_enter(ctx))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    oxh::ScratchLease lease(st);  // the waves' literal slots, then the count
+    const uint64_t at_bad = oxh::zstd_slot_bytes(nblocks), total = at_bad + 8;
+    void* base = nullptr;
+    if (lease.get(total, &base) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(OXH_ERR_NOMEM, "zstd inflate: " + std::to_string(total) + " B of literal slots on the device");
+    }
+    uint8_t* d = (uint8_t*)base;
+    unsigned long long bad = 0;
+    rc = [&]() -> int {
+        int r = oxh::zstd_inflate_enqueue(d_src, d_src_offsets, d_src_offsets + 1, d_dst, d_dst_offsets, d_dst_offsets + 1, d_status, nblocks, d,
+                                          (unsigned long long*)(d + at_bad), st);
+        if (r) return r;
+        HIP_TRY(hipMemcpyAsync(&bad, d + at_bad, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return OXH_OK;
+    }();
+    if (rc != OXH_OK) (void)hipStreamSynchronize(st);
+    if (rc == OXH_OK) *bad_blocks = bad;
+    return rc;
+}
+
+int oxh_zstd_inflate_host(oxh_ctx* ctx, uint64_t nblocks, const uint8_t* src, const uint64_t* src_offsets, uint8_t* dst,
+                          const uint64_t* dst_offsets, uint32_t* status, uint64_t* bad_blocks) {
+    int rc = zstd_args(nblocks, src, src_offsets, dst_offsets, status, bad_blocks);
+    if (rc) return rc;
+    if (nblocks == 0) return *bad_blocks = 0, OXH_OK;
+    for (uint64_t b = 0; b < nblocks; ++b) {
+        if (src_offsets[b + 1] < src_offsets[b]) return fail(OXH_ERR_INVALID, "zstd inflate: src_offsets decrease at block " + std::to_string(b));
+        if (dst_offsets[b + 1] < dst_offsets[b]) return fail(OXH_ERR_INVALID, "zstd inflate: dst_offsets decrease at block " + std::to_string(b));
+    }
+    const uint64_t src_lo = src_offsets[0], src_bytes = src_offsets[nblocks] - src_lo, dst_lo = dst_offsets[0], dst_bytes = dst_offsets[nblocks] - dst_lo;
+    if (dst_bytes && !dst) return fail(OXH_ERR_INVALID, "zstd inflate: dst is NULL");
+    if ((rc = zstd_enter(ctx))) return rc;
+    hipStream_t st = ctx->stream;
+    // one device block: the input, the output, both offset tables from 0, the statuses, the count, the literal slots
+    const uint64_t up16 = 15, at_dst = (src_bytes + up16) & ~up16, at_so = at_dst + ((dst_bytes + up16) & ~up16), at_do = at_so + (nblocks + 1) * 8,
+                   at_status = at_do + (nblocks + 1) * 8, at_bad = (at_status + nblocks * 4 + 7) & ~7ull, at_slots = (at_bad + 8 + up16) & ~up16,
+                   total = at_slots + oxh::zstd_slot_bytes(nblocks);
+    std::vector<uint64_t> tables;
+    try {
+        tables.resize(2 * (nblocks + 1));
+    } catch (const std::bad_alloc&) {
+        return fail(OXH_ERR_NOMEM, "zstd inflate: the offset tables on the host");
+    }
+    for (uint64_t b = 0; b <= nblocks; ++b) tables[b] = src_offsets[b] - src_lo, tables[nblocks + 1 + b] = dst_offsets[b] - dst_lo;
+    uint8_t* d = nullptr;
+    if (hipMalloc(&d, total) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(OXH_ERR_NOMEM, "zstd inflate: " + std::to_string(total) + " B for the blocks on the device");
+    }
+    oxh::poison_device(d, total, st);
+    std::vector<uint32_t> got(nblocks);
+    unsigned long long bad = 0;
+    rc = [&]() -> int {
+        if (src_bytes) HIP_TRY(hipMemcpyAsync(d, src + src_lo, src_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d + at_so, tables.data(), tables.size() * 8, hipMemcpyHostToDevice, st));
+        const uint64_t *d_so = (const uint64_t*)(d + at_so), *d_do = (const uint64_t*)(d + at_do);
+        int r = oxh::zstd_inflate_enqueue(d, d_so, d_so + 1, d + at_dst, d_do, d_do + 1, (uint32_t*)(d + at_status), nblocks, d + at_slots,
+                                          (unsigned long long*)(d + at_bad), st);
+        if (r) return r;
+        HIP_TRY(hipMemcpyAsync(got.data(), d + at_status, nblocks * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&bad, d + at_bad, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        // the caller's arrays stay untouched unless everything succeeded
+        if (dst_bytes) HIP_TRY(hipMemcpy(dst + dst_lo, d + at_dst, dst_bytes, hipMemcpyDeviceToHost));
+        memcpy(status, got.data(), nblocks * 4);
+        *bad_blocks = bad;
+        return OXH_OK;
+    }();
+    if (rc != OXH_OK) (void)hipStreamSynchronize(st);
+    (void)hipFree(d);
+    return rc;
+}
+
 // ---------------------------------------------------------------- Snappy, compress (the kernels: snappy_compress.hip)
 uint64_t oxh_snappy_bound(uint64_t n) { return oxh::snappy_bound(n); }
 

@@ -72,6 +72,9 @@
 //                      fragment, 64 positions a batch probing a table of positions in LDS (atomic max), every lane
 //                      extending its own match, a uniform greedy selection, the batch's elements placed by a prefix
 //                      sum and staged in LDS; then a wave per block packs the fragments' streams behind the preamble
+//   zstd_inflate.hip   many Zstandard frames inflated per launch (oxh_zstd_inflate_*; the Parquet open's ZSTD pages): a wave
+//                      per frame, Huffman and FSE tables in LDS (zstd_tables.hpp), a lane per Huffman stream, one lane
+//                      chasing the sequence bitstream into 64 cells, the wave executing them as the Snappy inflate does
 // There is no CPU hashing path: every digest this library returns was computed on the GPU.
 #pragma once
 
@@ -196,6 +199,18 @@ namespace oxh {
 // (capi_dispatch.hip), the Parquet open (parquet_read.hip).
 int snappy_inflate_enqueue(const uint8_t* d_src, const uint64_t* d_src_lo, const uint64_t* d_src_hi, uint8_t* d_dst, const uint64_t* d_dst_lo,
                            const uint64_t* d_dst_hi, uint32_t* d_status, uint64_t nblocks, unsigned long long* d_bad, hipStream_t st);
+}  // namespace oxh
+
+// ---------------------------------------------------------------- batched Zstandard inflate (zstd_inflate.hip)
+namespace oxh {
+constexpr uint32_t kZstdSlot = 131072;   // a resident wave's decoded literals: one block's at most
+constexpr unsigned kZstdMaxGroups = 512;  // the grid's cap, so d_slots is at most 64 MiB
+inline unsigned zstd_grid(uint64_t nblocks) { return (unsigned)std::min<uint64_t>(nblocks, kZstdMaxGroups); }
+inline uint64_t zstd_slot_bytes(uint64_t nblocks) { return (uint64_t)zstd_grid(nblocks) * kZstdSlot; }
+// snappy_inflate_enqueue's list with one Zstandard frame a block and OXH_ZSTD_* causes; d_slots: zstd_slot_bytes(nblocks)
+// of working memory. Callers: oxh_zstd_inflate_* (capi_dispatch.hip), the Parquet open (parquet_read.hip).
+int zstd_inflate_enqueue(const uint8_t* d_src, const uint64_t* d_src_lo, const uint64_t* d_src_hi, uint8_t* d_dst, const uint64_t* d_dst_lo,
+                         const uint64_t* d_dst_hi, uint32_t* d_status, uint64_t nblocks, uint8_t* d_slots, unsigned long long* d_bad, hipStream_t st);
 }  // namespace oxh
 
 // ---------------------------------------------------------------- batched Snappy compress (snappy_compress.hip)

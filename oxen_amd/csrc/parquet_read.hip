@@ -112,14 +112,14 @@ __global__ __launch_bounds__(64) void pq_walk_kernel(const uint8_t* __restrict__
             }
             const uint64_t body = pos + s.at;
             const bool data = h.type == pqr::kPageData || h.type == pqr::kPageDataV2;
-            // a SNAPPY chunk compresses every page this reader reads, but a V2 page that says it is stored
-            const bool packed = c.codec == pqr::kCodecSnappy && (h.type == pqr::kPageData || h.type == pqr::kPageDict || (h.type == pqr::kPageDataV2 && h.is_compressed));
+            // a SNAPPY or ZSTD chunk compresses every page this reader reads, but a V2 page that says it is stored
+            const bool packed = c.codec != pqr::kCodecNone && (h.type == pqr::kPageData || h.type == pqr::kPageDict || (h.type == pqr::kPageDataV2 && h.is_compressed));
             if (!packed && h.csize != h.usize && (data || h.type == pqr::kPageDict || c.codec == pqr::kCodecNone)) {
                 bad = true;
                 break;
             }
             const uint32_t size = (uint32_t)(packed ? h.usize : h.csize);  // of the body the column kernels read
-            pqr::PageRec r{c.at + body, size, (uint32_t)h.type, (uint32_t)h.num_values, (uint32_t)h.encoding, 0, 0, 0, packed ? pqr::kPageInImage : 0u,
+            pqr::PageRec r{c.at + body, size, (uint32_t)h.type, (uint32_t)h.num_values, (uint32_t)h.encoding, 0, 0, 0, packed ? pqr::kPageInImage | (c.codec == pqr::kCodecZstd ? pqr::kPageZstd : 0u) : 0u,
                            (uint32_t)h.csize, 0};
             if (h.type == pqr::kPageData && c.optional) {  // V1: the levels' 4-byte length leads the body
                 if (size < 4) {
@@ -603,6 +603,14 @@ const char* snappy_cause(uint32_t code) {
                                   "the stream ends before the page's uncompressed size", "its range is not one"};
     return code < 8 ? names[code] : "an unknown cause";
 }
+const char* zstd_cause(uint32_t code) {
+    static const char* names[] = {"", "not a frame this reader reads (magic, dictionary, reserved bit, bytes behind it)",
+                                  "its content size is not the page's uncompressed size", "the frame leaves the page", "a block or one of its sections is malformed",
+                                  "Huffman literals are malformed", "an FSE table is malformed", "a sequence bitstream is malformed",
+                                  "an offset of 0 or from in front of the page's first byte", "the frame passes the page's uncompressed size",
+                                  "the frame ends before the page's uncompressed size", "its range is not one"};
+    return code < 12 ? names[code] : "an unknown cause";
+}
 
 // Every compressed page of the table inflated into an image the handle owns, and the records that need the inflated
 // body finished: a record's body is then its place in the image. `lease`: the open's, whose walk is over.
@@ -619,19 +627,23 @@ int inflate_pages(ParquetHandle& h, const std::vector<pqr::ChunkDesc>& chunks, c
     if (plan.implausible != ~0ull) {
         const pqr::PageRec& r = recs[plan.implausible];
         return fail(OXH_ERR_INVALID, "parquet open: " + where(plan.implausible) + ": a page of " + std::to_string(r.file_size) + " compressed bytes claims " +
-                                         std::to_string(r.body_size) + " uncompressed ones, more than any Snappy stream gives (22 x + 32)");
+                                         std::to_string(r.body_size) + " uncompressed ones, more than any " +
+                                         (r.flags & pqr::kPageZstd ? "Zstandard frame gives (128 KiB per 3 bytes behind the header)" : "Snappy stream gives (22 x + 32)"));
     }
     if (!plan.pages) return OXH_OK;
     // the blocks, the stored levels and the V1 pages whose level length is in the inflated body
     std::vector<uint64_t> tables, stored, later;
-    std::vector<uint64_t> block_page;
+    std::vector<uint64_t> block_page, zstd_page;  // the SNAPPY pages; the ZSTD pages go behind them: a launch per codec
     for (size_t k = 0; k < recs.size(); ++k) {
         const pqr::PageRec& r = recs[k];
         if (!(r.flags & pqr::kPageInImage)) continue;
-        block_page.push_back(k);
+        (r.flags & pqr::kPageZstd ? zstd_page : block_page).push_back(k);
         if (r.stored) stored.insert(stored.end(), {r.body, plan.places[k], (uint64_t)r.stored});
-        if (r.flags & pqr::kPageLevelsLater) later.push_back(plan.places[k]);
     }
+    const uint64_t nsnappy = block_page.size(), nzstd = zstd_page.size();
+    block_page.insert(block_page.end(), zstd_page.begin(), zstd_page.end());
+    for (uint64_t k : block_page)  // in the blocks' order: the lengths come back in it
+        if (recs[k].flags & pqr::kPageLevelsLater) later.push_back(plan.places[k]);
     const uint64_t nb = block_page.size(), nstored = stored.size() / 3, nlater = later.size();
     tables.resize(4 * nb);  // src_lo | src_hi | dst_lo | dst_hi
     for (uint64_t j = 0; j < nb; ++j) {
@@ -647,7 +659,7 @@ int inflate_pages(ParquetHandle& h, const std::vector<pqr::ChunkDesc>& chunks, c
     h.image_bytes = plan.bytes;
     poison_device(h.image, plan.bytes, st);
     csv::Carver carve;
-    const uint64_t at_bad = carve(8), at_tables = carve(tables.size() * 8), at_status = carve(nb * 4), at_stored = carve(stored.size() * 8),
+    const uint64_t at_bad = carve(16), at_slots = carve(nzstd ? zstd_slot_bytes(nzstd) : 0), at_tables = carve(tables.size() * 8), at_status = carve(nb * 4), at_stored = carve(stored.size() * 8),
                    at_later = carve(nlater * 8), at_lengths = carve(nlater * 4);
     void* lbase = nullptr;
     if (lease.get(carve.at, &lbase) != hipSuccess) {
@@ -657,7 +669,7 @@ int inflate_pages(ParquetHandle& h, const std::vector<pqr::ChunkDesc>& chunks, c
     uint8_t* b = (uint8_t*)lbase;
     const uint64_t* d_tables = (const uint64_t*)(b + at_tables);
     std::vector<uint32_t> status(nb), lengths(nlater);
-    unsigned long long bad = 0;
+    unsigned long long bad[2] = {0, 0};
     int rc = [&]() -> int {
         HIP_TRY(hipMemcpyAsync(b + at_tables, tables.data(), tables.size() * 8, hipMemcpyHostToDevice, st));
         if (nstored) {
@@ -665,8 +677,14 @@ int inflate_pages(ParquetHandle& h, const std::vector<pqr::ChunkDesc>& chunks, c
             pq_stored_kernel<<<wave_grid(nstored), 256, 0, st>>>(h.d_bytes, h.image, (const uint64_t*)(b + at_stored), nstored);
             HIP_TRY(hipGetLastError());
         }
-        int r = snappy_inflate_enqueue(h.d_bytes, d_tables, d_tables + nb, h.image, d_tables + 2 * nb, d_tables + 3 * nb, (uint32_t*)(b + at_status), nb,
+        int r = OXH_OK;
+        if (nsnappy)
+            r = snappy_inflate_enqueue(h.d_bytes, d_tables, d_tables + nb, h.image, d_tables + 2 * nb, d_tables + 3 * nb, (uint32_t*)(b + at_status), nsnappy,
                                        (unsigned long long*)(b + at_bad), st);
+        if (r) return r;
+        if (nzstd)
+            r = zstd_inflate_enqueue(h.d_bytes, d_tables + nsnappy, d_tables + nb + nsnappy, h.image, d_tables + 2 * nb + nsnappy, d_tables + 3 * nb + nsnappy,
+                                     (uint32_t*)(b + at_status) + nsnappy, nzstd, b + at_slots, (unsigned long long*)(b + at_bad) + 1, st);
         if (r) return r;
         if (nlater) {
             HIP_TRY(hipMemcpyAsync(b + at_later, later.data(), nlater * 8, hipMemcpyHostToDevice, st));
@@ -675,15 +693,16 @@ int inflate_pages(ParquetHandle& h, const std::vector<pqr::ChunkDesc>& chunks, c
             HIP_TRY(hipMemcpyAsync(lengths.data(), b + at_lengths, nlater * 4, hipMemcpyDeviceToHost, st));
         }
         HIP_TRY(hipMemcpyAsync(status.data(), b + at_status, nb * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(&bad, b + at_bad, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(bad, b + at_bad, 16, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         return OXH_OK;
     }();
     if (rc != OXH_OK) return (void)hipStreamSynchronize(st), rc;
     for (uint64_t j = 0; j < nb; ++j)
         if (status[j])
-            return fail(OXH_ERR_INVALID, "parquet open: " + where(block_page[j]) + ": a page's Snappy stream is malformed: " + snappy_cause(status[j]));
-    if (bad) return fail(OXH_ERR_HIP, "parquet open: the inflation counts a malformed page and names none");
+            return fail(OXH_ERR_INVALID, "parquet open: " + where(block_page[j]) + (j < nsnappy ? ": a page's Snappy stream is malformed: " + std::string(snappy_cause(status[j]))
+                                                                                                : ": a page's Zstandard frame is malformed: " + std::string(zstd_cause(status[j]))));
+    if ((nsnappy && bad[0]) || (nzstd && bad[1])) return fail(OXH_ERR_HIP, "parquet open: the inflation counts a malformed page and names none");
     uint64_t nth = 0;
     for (uint64_t j = 0; j < nb; ++j) {
         pqr::PageRec& r = recs[block_page[j]];
@@ -1003,7 +1022,7 @@ int oxh_parquet_open_device(oxh_ctx* ctx, const uint8_t* d_bytes, uint64_t nbyte
         HIP_TRY(hipMemcpyAsync(meta.data(), d_bytes + at, len, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
-    pqr::Footer f = pqr::read_footer(meta.data(), len, at, nbytes, flags & OXH_PARQUET_INFLATE);
+    pqr::Footer f = pqr::read_footer(meta.data(), len, at, nbytes, flags & OXH_PARQUET_INFLATE, flags & OXH_PARQUET_INFLATE_ZSTD);
     if (!f.error.empty()) return fail(OXH_ERR_INVALID, "parquet open: " + f.error);
     take_footer(*h, std::move(f));
     uint64_t stats[8] = {};
@@ -1021,7 +1040,7 @@ int oxh_parquet_open_host(oxh_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, u
     const uint8_t none[8] = {};
     const std::string what = pqr::footer_place(nbytes >= 12 ? bytes : none, nbytes >= 12 ? bytes + nbytes - 8 : none, nbytes, at, len);
     if (!what.empty()) return fail(OXH_ERR_INVALID, "parquet open: " + what);
-    pqr::Footer f = pqr::read_footer(bytes + at, len, at, nbytes, flags & OXH_PARQUET_INFLATE);
+    pqr::Footer f = pqr::read_footer(bytes + at, len, at, nbytes, flags & OXH_PARQUET_INFLATE, flags & OXH_PARQUET_INFLATE_ZSTD);
     if (!f.error.empty()) return fail(OXH_ERR_INVALID, "parquet open: " + f.error);
     if ((rc = device_enter(ctx))) return rc;
     hipStream_t st = ctx->stream;

@@ -52,13 +52,17 @@ struct Leaf {
 
 struct Chunk {
     uint64_t at = 0, bytes = 0, num_values = 0;
-    uint32_t codec = 0;  // kCodecNone, or with OXH_PARQUET_INFLATE kCodecSnappy
+    uint32_t codec = 0;  // kCodecNone, or with OXH_PARQUET_INFLATE kCodecSnappy, with OXH_PARQUET_INFLATE_ZSTD kCodecZstd
 };
-constexpr uint32_t kCodecNone = 0, kCodecSnappy = 1;
+constexpr uint32_t kCodecNone = 0, kCodecSnappy = 1, kCodecZstd = 6;
 
 // No Snappy stream expands more than 64 / 3 (a 3-byte copy gives 64 bytes); the preamble and a short last element
 // are the 32. A page that claims more is refused before anything is allocated for it.
 inline bool inflated_size_plausible(uint64_t csize, uint64_t usize) { return usize <= 22 * csize + 32; }
+// A Zstandard frame is a header of at least 5 bytes (the magic and the descriptor) and blocks that each cost at least
+// 3 bytes (the block header) and yield at most 128 KiB: an RLE block of 4 bytes gives that much, so Snappy's bound
+// is wrong here.
+inline bool zstd_size_plausible(uint64_t csize, uint64_t usize) { return csize >= 5 && usize <= (csize - 5) / 3 * 131072; }
 
 struct Footer {
     std::vector<Leaf> leaves;
@@ -70,7 +74,7 @@ struct Footer {
 
 // "" when oxh_parquet_open_*'s arguments are well formed.
 inline std::string open_error(const uint8_t* bytes, uint64_t nbytes, uint32_t flags, void* const* out, const uint64_t* stats8) {
-    if (flags & ~(uint32_t)OXH_PARQUET_INFLATE) return "unknown flags";
+    if (flags & ~(uint32_t)(OXH_PARQUET_INFLATE | OXH_PARQUET_INFLATE_ZSTD)) return "unknown flags";
     if (nbytes && !bytes) return "bytes is NULL";
     if (!out) return "out is NULL";
     if (!stats8) return "stats8 is NULL";
@@ -168,10 +172,10 @@ inline ChunkMeta column_chunk(Span& s) {
 // Refusals, in this order: a footer that is no FileMetaData; an encrypted footer; a schema without a root or whose
 // elements are not the root's children (a nested field, named); a repeated field; more than 2^40 rows; and per
 // row group, in order: a column count that is not the schema's, a chunk without metadata or with encrypted
-// metadata, a codec other than UNCOMPRESSED -- with `inflate` (OXH_PARQUET_INFLATE) other than that and SNAPPY -- (its
-// number named), a chunk outside the file's pages, a num_values that is not the group's rows; then group rows that do
+// metadata, a codec other than UNCOMPRESSED -- with `inflate` (OXH_PARQUET_INFLATE) other than that and SNAPPY, with
+// `zstd` (OXH_PARQUET_INFLATE_ZSTD) and ZSTD -- (its number named), a chunk outside the file's pages, a num_values that is not the group's rows; then group rows that do
 // not sum to num_rows.
-inline Footer read_footer(const uint8_t* meta, uint64_t len, uint64_t meta_at, uint64_t nbytes, bool inflate = false) {
+inline Footer read_footer(const uint8_t* meta, uint64_t len, uint64_t meta_at, uint64_t nbytes, bool inflate = false, bool zstd = false) {
     using namespace detail;
     Footer f;
     uint64_t st[kSkipDepth];
@@ -252,9 +256,11 @@ inline Footer read_footer(const uint8_t* meta, uint64_t len, uint64_t meta_at, u
             const ChunkMeta& m = groups[g][c];
             const std::string col = where + ", column '" + f.leaves[c].name + "'";
             if (!m.has_meta || m.encrypted) return f.error = col + ": its chunk has no plain metadata in the footer", f;
-            if (m.codec != kCodecNone && !(inflate && m.codec == kCodecSnappy))
+            if (m.codec != kCodecNone && !(inflate && m.codec == kCodecSnappy) && !(zstd && m.codec == kCodecZstd))
                 return f.error = col + ": compression codec " + std::to_string(m.codec) +
-                                 (inflate ? " (UNCOMPRESSED, 0, and SNAPPY, 1, are read on the device)"
+                                 (zstd ? (inflate ? " (UNCOMPRESSED, 0, SNAPPY, 1, and ZSTD, 6, are read on the device)"
+                                                  : " (UNCOMPRESSED, 0, and ZSTD, 6, are read on the device; OXH_PARQUET_INFLATE adds SNAPPY, 1)")
+                                  : inflate ? " (UNCOMPRESSED, 0, and SNAPPY, 1, are read on the device)"
                                           : " (only UNCOMPRESSED, 0, is read on the device; OXH_PARQUET_INFLATE adds SNAPPY, 1)"), f;
             const int64_t first = m.dict_at > 0 && m.dict_at < m.data_at ? m.dict_at : m.data_at;
             if (first < 4 || m.compressed < 0 || (uint64_t)first > meta_at || (uint64_t)m.compressed > meta_at - (uint64_t)first)
@@ -288,6 +294,7 @@ struct PageRec {
 };
 constexpr uint32_t kPageInImage = 4;      // a compressed page: its body is inflated into the image
 constexpr uint32_t kPageLevelsLater = 8;  // a compressed V1 page of an OPTIONAL column: its levels' length is in the inflated body
+constexpr uint32_t kPageZstd = 16;        // a compressed page of a ZSTD chunk: a Zstandard frame, not a Snappy block
 
 // A compressed V1 page's levels, once the first 4 bytes of its inflated body (`def_bytes`) are known: what the walk
 // leaves of a page that is not compressed.
@@ -298,7 +305,7 @@ OXH_PQR_BOTH void finish_v1_levels(PageRec& r, uint32_t def_bytes) {
 }
 
 // The image of the compressed pages: each inflated body in table order on a 16-byte grid. places[k]: where page k's
-// body starts in it (compressed pages only). A page whose claimed size no Snappy stream reaches stops the plan:
+// body starts in it (compressed pages only). A page whose claimed size no stream of its codec reaches stops the plan:
 // `implausible` is that page, else ~0.
 struct ImagePlan {
     std::vector<uint64_t> places;
@@ -310,7 +317,8 @@ inline ImagePlan plan_image(const std::vector<PageRec>& recs) {
     for (size_t k = 0; k < recs.size(); ++k) {
         const PageRec& r = recs[k];
         if (!(r.flags & kPageInImage)) continue;
-        if (r.stored > r.file_size || r.stored > r.body_size || !inflated_size_plausible(r.file_size - r.stored, r.body_size - r.stored))
+        if (r.stored > r.file_size || r.stored > r.body_size ||
+            !(r.flags & kPageZstd ? zstd_size_plausible : inflated_size_plausible)(r.file_size - r.stored, r.body_size - r.stored))
             return plan.implausible = k, plan;
         plan.places[k] = plan.bytes, plan.bytes += ((uint64_t)r.body_size + 15) & ~15ull, ++plan.pages;
     }

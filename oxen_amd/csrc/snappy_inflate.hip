@@ -24,7 +24,7 @@
 // length before its cell exists. A copy's source is inside [0, produced) before any load: 0 < offset <= produced.
 #include "capi_internal.hpp"
 #include "columns.hpp"
-#include "snappy_wave.hpp"  // snp_lds_order, snp_span_wave
+#include "snappy_wave.hpp"  // snp_lds_order, snp_global_order, snp_span_wave
 
 namespace oxh {
 
@@ -35,13 +35,6 @@ constexpr uint32_t kLongLiteral = 256;   // a literal of this many bytes and mor
 constexpr unsigned kSnappyMaxGroups = 2048;
 constexpr uint32_t kLiteral = 0, kCopy = 1, kNone = 2;
 }  // namespace snp
-
-// The wave's global stores so far are visible to its loads from here on.
-__device__ __forceinline__ void snp_global_order() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 
 // Block b: src_all[src_lo[b], src_hi[b]) inflates to dst_all[dst_lo[b], dst_hi[b]); status[b] = 0 or the cause;
 // bad_count += the blocks with a cause.

@@ -1,5 +1,6 @@
-// oxen_amd/csrc/snappy_wave.hpp -- what the two Snappy kernels share (snappy_inflate.hip, snappy_compress.hip): the
-// order of a wave's LDS operations and the whole-wave span copy with aligned 16-byte stores.
+// oxen_amd/csrc/snappy_wave.hpp -- what the Snappy kernels and the Zstandard inflate share (snappy_inflate.hip,
+// snappy_compress.hip, zstd_inflate.hip): the order of a wave's LDS and global operations and the whole-wave span copy
+// with aligned 16-byte stores.
 #pragma once
 
 #include "xxh3_device.hpp"
@@ -12,6 +13,13 @@ __device__ __forceinline__ void snp_lds_order() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// The wave's global stores so far are visible to its loads from here on.
+__device__ __forceinline__ void snp_global_order() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
 // Exactly n bytes by the 64 lanes: the bytes up to the destination's 16-byte grid a lane each, then 16 bytes a lane

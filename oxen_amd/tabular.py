@@ -45,7 +45,8 @@ JSON array (`write_df`'s jsonl / ndjson / json arms, and the text of a data-fram
 their `_device` forms; `oxh_write_parquet_*` as a Parquet file, uncompressed or with SNAPPY pages (what `write_df`'s parquet arm is for) --
 `write_parquet`, `write_parquet_device`; and `oxh_parquet_*` read such a file back (`ParquetFile`, `read_parquet`,
 `read_parquet_device`, `parquet_shape`, `parquet_schema`), SNAPPY pages included: `oxh_snappy_inflate_*` inflate many raw
-Snappy blocks per call (`snappy_inflate`, `snappy_inflate_device`) and the Parquet open runs the same kernel;
+Snappy blocks per call (`snappy_inflate`, `snappy_inflate_device`) and `oxh_zstd_inflate_*` many Zstandard frames
+(`zstd_inflate`, `zstd_inflate_device`), and the Parquet open runs the same kernels over SNAPPY and ZSTD pages;
 `oxh_snappy_compress_*` compress many blocks per call to such streams (`snappy_compress`, `snappy_compress_device`,
 `snappy_bound`).
 
@@ -2714,13 +2715,13 @@ class ParquetFile:
     """The page index of one Parquet buffer (an oxh_parquet_open_* handle), the twin of `JsonlFile`: `stats`,
     `names`, `types`, `measure`, `columns`. data: bytes / a uint8 numpy array (the host form, which owns a device
     copy), or with device=True a uint8 torch tensor on the device, which the object keeps alive. The rules are
-    include/oxen_hash.h's "Parquet: the file's bytes": uncompressed and, with inflate (OXH_PARQUET_INFLATE, the
-    default), SNAPPY files with a flat schema, the physical bits. The handle holds the inflated size of every
+    include/oxen_hash.h's "Parquet: the file's bytes": uncompressed and, with inflate (OXH_PARQUET_INFLATE and
+    OXH_PARQUET_INFLATE_ZSTD, the default), SNAPPY and ZSTD files with a flat schema, the physical bits. The handle holds the inflated size of every
     compressed page on the device until `close`; `stats.pages_inflated` counts them."""
 
     def __init__(self, data, ctx: Optional[_capi.Context] = None, device: bool = False, stream=None, inflate: bool = True):
         self.device = device
-        flags = _capi.OXH_PARQUET_INFLATE if inflate else 0
+        flags = _capi.OXH_PARQUET_INFLATE | _capi.OXH_PARQUET_INFLATE_ZSTD if inflate else 0
         self.ctx = ctx
         self.stream = stream
         self.handle = None
@@ -2953,6 +2954,71 @@ def snappy_inflate_device(d_src, d_src_offsets, d_dst, d_dst_offsets, d_status, 
     bad = ctypes.c_uint64(0)
     _capi.check(_capi.lib().oxh_snappy_inflate_device(_handle(ctx), n, d_src.data_ptr(), d_src_offsets.data_ptr(), d_dst.data_ptr(), d_dst_offsets.data_ptr(),
                                                       d_status.data_ptr(), ctypes.byref(bad), _stream(stream)), "oxh_snappy_inflate_device")
+    return int(bad.value)
+
+
+# ---------------------------------------------------------------- Zstandard: frames inflated in one call (oxh_zstd_inflate_*)
+def _zstd_length(frame):
+    """The Frame_Content_Size a Zstandard frame's header carries, or None where it carries none (or is no header)."""
+    frame = bytes(frame[:14])
+    if len(frame) < 5 or frame[:4] != b"\x28\xb5\x2f\xfd":
+        return None
+    fhd = frame[4]
+    single, width = fhd >> 5 & 1, (1, 2, 4, 8)[fhd >> 6]
+    if fhd >> 6 == 0 and not single:
+        return None
+    at = 5 + (0 if single else 1) + (0, 1, 2, 4)[fhd & 3]
+    if len(frame) < at + width:
+        return None
+    return int.from_bytes(frame[at:at + width], "little") + (256 if width == 2 else 0)
+
+
+def zstd_inflate(blocks, sizes=None, ctx: Optional[_capi.Context] = None) -> list:
+    """oxh_zstd_inflate_host: every Zstandard frame (bytes) inflated on the device in one call, as a list of bytes.
+    sizes: the frames' expected lengths -- a frame without a content size (a streaming encoder's, polars' among them)
+    has no length of its own; None only when every frame carries one, read here. A malformed frame raises, naming
+    the first and its cause (include/oxen_hash.h "Zstandard")."""
+    blocks = [bytes(b) for b in blocks]
+    n = len(blocks)
+    if sizes is None:
+        sizes = [_zstd_length(b) for b in blocks]
+        if None in sizes:
+            raise _capi.OxenError(f"zstd inflate: block {sizes.index(None)} carries no content size: pass sizes", _capi.OXH_ERR_INVALID)
+    if len(sizes) != n:
+        raise _capi.OxenError("zstd inflate: one size a block", _capi.OXH_ERR_INVALID)
+    src = np.frombuffer(b"".join(blocks) or b"\0", dtype=np.uint8)
+    src_offsets = np.concatenate([[0], np.cumsum([len(b) for b in blocks])]).astype(np.uint64)
+    dst_offsets = np.concatenate([[0], np.cumsum([int(k) for k in sizes])]).astype(np.uint64)
+    dst, status, bad = np.zeros(max(int(dst_offsets[-1]), 1), dtype=np.uint8), np.zeros(max(n, 1), dtype=np.uint32), ctypes.c_uint64(0)
+    _capi.check(_capi.lib().oxh_zstd_inflate_host(_handle(ctx), n, src.ctypes.data, src_offsets.ctypes.data_as(_capi._u64p), dst.ctypes.data,
+                                                  dst_offsets.ctypes.data_as(_capi._u64p), status.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                                  ctypes.byref(bad)), "oxh_zstd_inflate_host")
+    if bad.value:
+        first = int(np.flatnonzero(status[:n])[0])
+        raise _capi.OxenError(f"zstd inflate: {bad.value} malformed block(s); block {first}: {_capi.OXH_ZSTD_CAUSES[int(status[first])]}",
+                              _capi.OXH_ERR_INVALID)
+    raw = dst.tobytes()
+    return [raw[int(dst_offsets[k]):int(dst_offsets[k + 1])] for k in range(n)]
+
+
+def zstd_inflate_device(d_src, d_src_offsets, d_dst, d_dst_offsets, d_status, ctx: Optional[_capi.Context] = None, stream=None) -> int:
+    """oxh_zstd_inflate_device over torch tensors on the device, as `snappy_inflate_device`: frame b of d_src fills d_dst
+    between d_dst_offsets[b] and [b + 1], the frame's expected length; d_status receives 0 or the cause. Returns the
+    number of malformed frames. Blocks."""
+    from .device import _require_cuda, _stream
+
+    for t in (d_src, d_src_offsets, d_dst, d_dst_offsets, d_status):
+        _require_cuda(t)
+        if not t.is_contiguous():
+            raise _capi.OxenError("the Zstandard tensors are contiguous", _capi.OXH_ERR_INVALID)
+    if d_src.element_size() != 1 or d_dst.element_size() != 1 or d_src_offsets.element_size() != 8 or d_dst_offsets.element_size() != 8 or d_status.element_size() != 4:
+        raise _capi.OxenError("uint8 bytes, 8-byte offsets and 4-byte statuses", _capi.OXH_ERR_INVALID)
+    n = d_status.numel()
+    if d_src_offsets.numel() != n + 1 or d_dst_offsets.numel() != n + 1:
+        raise _capi.OxenError("one more offset than blocks in both tables", _capi.OXH_ERR_INVALID)
+    bad = ctypes.c_uint64(0)
+    _capi.check(_capi.lib().oxh_zstd_inflate_device(_handle(ctx), n, d_src.data_ptr(), d_src_offsets.data_ptr(), d_dst.data_ptr(), d_dst_offsets.data_ptr(),
+                                                    d_status.data_ptr(), ctypes.byref(bad), _stream(stream)), "oxh_zstd_inflate_device")
     return int(bad.value)
 
 
