@@ -1212,12 +1212,35 @@ int oxh_write_json_host(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const uint
  *     uncompressed file, 32 + n / 6 + 5 bytes a page and 10 bytes for each size and offset of the footer --, not the
  *     size; a capacity below it is the "capacity below the need" error with nothing written; the writing call sets
  *     out_bytes and stats4[0] to the file's size. Working memory: the uncompressed file and 65 KiB per 64 KiB of it.
- *   Stated and not built: zstd; dictionary encoding; nested and narrower types; the `arrow`
- *     arm of `write_df`.
+ *   Dictionary encoding. With OXH_PARQUET_DICTIONARY (which may be combined with OXH_PARQUET_SNAPPY) a dictionary is
+ *     decided per column chunk, that is per (row group, column), by the data alone. A BOOLEAN chunk never gets one. An
+ *     INT64, DOUBLE or BYTE_ARRAY chunk gets one when its distinct values that are not null number at least 1 and at
+ *     most kDictMaxEntries = 65 536, its dictionary page body is at most 1 MiB, and no string cell is longer than
+ *     kDictMaxCell = 256 bytes (named constants of parquet_host.hpp); every other chunk is written exactly as without
+ *     the flag. Equality is on the stored bits: the 8 bytes of an INT64 or DOUBLE (-0.0 and +0.0, and NaN payloads,
+ *     stay distinct), length and bytes of a string. The entries stand in the order of each value's first occurrence
+ *     in the chunk's rows, so the bytes are the same on every run and in both forms. The dictionary page is the
+ *     chunk's first page: PageHeader type DICTIONARY_PAGE, DictionaryPageHeader{num_values, encoding PLAIN}, the
+ *     entries in PLAIN. The data pages stay DataPage V1 with encoding RLE_DICTIONARY and the levels as above; their
+ *     values are one byte w = max(1, ceil(log2(num_values))), the chunk's width, then one bit-packed run of the hybrid,
+ *     varint((ceil(valid / 8) << 1) | 1) and ceil(valid / 8) * w bytes, indices LSB first, pad indices 0; a page
+ *     without a valid row has the width byte and nothing else. Pages are cut as above with the index stream's bytes as
+ *     the values; the dictionary page is not counted. Chunk metadata: encodings [PLAIN, RLE, RLE_DICTIONARY],
+ *     dictionary_page_offset == the dictionary page's header, data_page_offset == the first data page's header, the
+ *     sizes include the dictionary page; statistics are unchanged. With OXH_PARQUET_SNAPPY the dictionary page's body
+ *     is one more Snappy block, and the capacity grows by 32 + n / 6 + 5 bytes for it as for every page. Working
+ *     memory, per INT64, DOUBLE or string column: a table of min(131 072, twice a row group's rows, as a power of two)
+ *     8-byte words per row group, and per row 4 bytes of table places, 8 of the first occurrences' scan and 4 to 6
+ *     of dense indices, which hold the first-occurrence flags before the plan (12 more for a string column's entry
+ *     lengths and their scan).
+ *   Stated and not built: zstd; RLE runs in the index stream, a fallback in the middle of a chunk, DataPage V2,
+ *     dictionaries for booleans and choosing the flag automatically; nested and narrower types; the `arrow` arm of
+ *     `write_df`.
  *
  * Inputs: as oxh_write_json_* (names and name_offsets are always read; host memory in both forms), then
- * rows_per_group, page_bytes and flags (0 or OXH_PARQUET_SNAPPY; bit 0 stays reserved). Outputs: the file's bytes in out (capacity bytes; device
- * memory in _device, host memory in _host); out_bytes = the file's size; stats4 = {bytes, row groups, pages, null
+ * rows_per_group, page_bytes and flags (0 or any of OXH_PARQUET_SNAPPY and OXH_PARQUET_DICTIONARY; anything outside 2 | 4
+ * is "unknown flags", bit 0 stays reserved). Outputs: the file's bytes in out (capacity bytes; device
+ * memory in _device, host memory in _host); out_bytes = the file's size; stats4 = {bytes, row groups, pages (dictionary pages too), null
  * cells}. With out NULL the call only measures. With a capacity below the need nothing is written to out, out_bytes
  * and stats4 are set and the call returns OXH_ERR_INVALID. nrows == 0 gives a valid file with the schema and no row
  * group. Both forms block until complete; stream orders the device form's work, the host form stages its columns
@@ -1234,6 +1257,7 @@ int oxh_write_json_host(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const uint
  * ordinal is an int16); then a capacity below the need.
  * A failed allocation is OXH_ERR_NOMEM with the outputs untouched. */
 #define OXH_PARQUET_SNAPPY 2u /* flags of oxh_write_parquet_*: SNAPPY pages */
+#define OXH_PARQUET_DICTIONARY 4u /* flags of oxh_write_parquet_*: RLE_DICTIONARY chunks where the data allow */
 int oxh_write_parquet_device(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const uint32_t* types, const uint32_t* kinds,
                              const void* const* d_values, const void* const* d_offsets, const uint8_t* const* d_validity,
                              const uint64_t* bit_offsets, const uint8_t* names, const uint64_t* name_offsets,

@@ -75,6 +75,7 @@ OXH_CSV_FLOAT32 = 7     # OXH_COL_FIXED4; oxh_parquet_columns_* only
 OXH_JSON_LINES = 0      # flags of oxh_write_json_*: one object per row and line
 OXH_JSON_ARRAY = 1      # one array of the rows' objects
 OXH_PARQUET_SNAPPY = 2   # flags of oxh_write_parquet_*: every page body one raw Snappy block
+OXH_PARQUET_DICTIONARY = 4  # flags of oxh_write_parquet_*: RLE_DICTIONARY chunks where the data allow
 OXH_PARQUET_INFLATE = 2  # flags of oxh_parquet_open_*: read SNAPPY chunks too
 OXH_PARQUET_INFLATE_ZSTD = 4  # flags of oxh_parquet_open_*: read ZSTD chunks too
 OXH_ZSTD_CAUSES = ("", "frame", "header", "input", "block", "literals", "table", "sequences", "offset", "overrun", "truncated", "range")   # OXH_ZSTD_* by number

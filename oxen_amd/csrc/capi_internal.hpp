@@ -61,6 +61,11 @@
 //                      groups, Thrift headers and the footer from that table (parquet_host.hpp); then a wave per tile
 //                      and column compacts the valid cells to their ranks through LDS -- mbcnt over validity ballots
 //                      -- and stores them in aligned 16-byte blocks behind the page's header and levels
+//   parquet_dict.hip   the writer's dictionary chunks (OXH_PARQUET_DICTIONARY): an exact distinct-value build per column chunk
+//                      in open-addressing tables of rows (compare-and-swap, the actual values compared, atomic min for
+//                      the first occurrence), the first occurrences ranked by the device-wide scan, the entries gathered
+//                      to the dictionary page, every row's index to a dense array and a wave per 512 indices bit-packing
+//                      them through LDS (parquet_device.hpp holds what it shares with parquet_write.hip)
 //   parquet_read.hip   an uncompressed, flat Parquet file to the same typed columns (oxh_parquet_*): the footer's plan on
 //                      the host (parquet_read_host.hpp, parquet_bits.hpp), a lane per chunk chasing page headers, a wave
 //                      per page for the levels' and indices' hybrid runs, a lane per output row for the gather, the

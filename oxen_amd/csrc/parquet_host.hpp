@@ -1,7 +1,8 @@
 // oxen_amd/csrc/parquet_host.hpp -- the host-only pieces of oxh_write_parquet_* (parquet_write.hip): the argument
 // checks that need no device, in the header's order; the Thrift compact encoder; the planner that turns the measure
 // kernel's tile table into pages, row groups, every PageHeader's bytes, every page's place in the file and the
-// footer; and the folding of the tiles' min / max partials into a column chunk's statistics. The format is stated in
+// footer; the folding of the tiles' min / max partials into a column chunk's statistics; and for OXH_PARQUET_DICTIONARY
+// the limits, the fallback decision, the index width and the index stream's bytes. The format is stated in
 // include/oxen_hash.h "Parquet". Plain C++ with no HIP in it, so that a stand-alone program can call it
 // (tests/native/parquet_host_test.cpp, which is also what a sanitizer build runs).
 #pragma once
@@ -24,6 +25,10 @@ constexpr uint64_t kMaxRows = 1ull << 40;
 constexpr uint64_t kMaxCell = 1ull << 32;            // a BYTE_ARRAY's length is a u32
 constexpr uint64_t kMaxPage = 0x7FFFFFFFull;         // PageHeader's sizes are i32
 constexpr uint32_t kFlagSnappy = 2;                  // OXH_PARQUET_SNAPPY: every page body is one raw Snappy block
+constexpr uint32_t kFlagDictionary = 4;              // OXH_PARQUET_DICTIONARY: RLE_DICTIONARY chunks where the data allow
+constexpr uint64_t kDictMaxEntries = 65536;          // a chunk of more distinct values stays PLAIN
+constexpr uint64_t kDictMaxCell = 256;               // so does a chunk with a longer string cell
+constexpr uint64_t kDictMaxPage = 1048576;           // and one whose dictionary page body is larger
 constexpr const char* kCreatedBy = "oxen_amd parquet writer (gfx950)";
 
 // What the measure kernel leaves per (tile, column), entry tile * ncols + column.
@@ -46,6 +51,18 @@ struct Page {
     uint32_t level_bytes;   // the bit-packed validity behind the head; 0 for a page without a null
     uint32_t tile0;         // its first tile
     uint32_t col;
+    // OXH_PARQUET_DICTIONARY. A data page of a dictionary chunk: the chunk's index width (0: PLAIN values), its
+    // dictionary page, and where its indices start in the call's dense index array (a multiple of 512). The dictionary
+    // page itself (rows == 0, the chunk's first page): dict_page names it, nvalid = its entries, values_bytes its body.
+    uint32_t dict_width, dict_page;
+    uint64_t dense_at;
+};
+
+// What the rank step leaves per (row group, column), entry group * ncols + column.
+struct ChunkDict {
+    uint64_t num_values;   // the distinct values of the chunk's rows that are not null
+    uint64_t dict_bytes;   // the dictionary page's body: 8 an entry, strings 4 + length
+    uint64_t overflow;     // not 0: more than kDictMaxEntries values or a cell above kDictMaxCell; the other two words mean nothing
 };
 
 struct Place {
@@ -117,7 +134,7 @@ struct Thrift {
     void end() { out.push_back(0), last.pop_back(); }
 };
 
-inline uint32_t varint_len(uint64_t v) {
+OXH_PQ_BOTH inline uint32_t varint_len(uint64_t v) {
     uint32_t n = 1;
     while (v >= 0x80) v >>= 7, ++n;
     return n;
@@ -156,7 +173,7 @@ inline std::string write_error(const Args& a, bool host) {
     if (!a.types || !a.kinds || !a.values || !a.offsets || !a.validity || !a.bit_offsets)
         return "types, kinds, values, offsets, validity or bit_offsets is NULL";
     if (a.ncols == 0) return "ncols is 0";
-    if (a.flags & ~kFlagSnappy) return "unknown flags";
+    if (a.flags & ~(kFlagSnappy | kFlagDictionary)) return "unknown flags";
     if (a.rows_per_group % kTileRows) return "rows_per_group is not a multiple of 1024";
     for (uint32_t c = 0; c < a.ncols; ++c)
         if (!known_type(a.types[c])) return "column " + std::to_string(c) + " has unknown type " + std::to_string(a.types[c]);
@@ -216,6 +233,7 @@ struct Plan {
     std::vector<uint8_t> footer;   // FileMetaData, its u32 length, "PAR1"
     uint64_t out_bytes = 0, row_groups = 0, null_cells = 0;
     uint64_t stored_bytes = 0, plain_bytes = 0;  // the row groups' total_compressed_size and total_byte_size, summed
+    uint64_t dense_indices = 0;    // OXH_PARQUET_DICTIONARY: the dense index array's u32 words
     std::string error;             // not empty: the file is refused
 };
 
@@ -225,13 +243,31 @@ inline uint64_t level_run_len(uint64_t rows, bool nulls) {
 }
 inline uint64_t values_len(uint32_t type, uint64_t valid, uint64_t bytes) { return type == OXH_CSV_BOOL ? (valid + 7) / 8 : bytes; }
 
+// OXH_PARQUET_DICTIONARY: whether a chunk is written with a dictionary (the three limits of the header; a chunk without
+// a value has none), the width of its indices, and the bytes of a page's index stream: the width byte, then one
+// bit-packed run of ceil(valid / 8) groups -- nothing behind the width for a page without a valid row.
+inline bool dict_chunk(uint32_t type, const ChunkDict& d) {
+    return type != OXH_CSV_BOOL && !d.overflow && d.num_values >= 1 && d.num_values <= kDictMaxEntries && d.dict_bytes <= kDictMaxPage;
+}
+inline uint32_t dict_width(uint64_t num_values) {
+    uint32_t w = 1;
+    while ((1ull << w) < num_values) ++w;
+    return w;
+}
+inline uint64_t index_stream_len(uint64_t valid, uint32_t w) {
+    const uint64_t groups = (valid + 7) / 8;
+    return groups ? 1 + varint_len((groups << 1) | 1) + groups * w : 1;
+}
+constexpr uint64_t kDenseBlock = 512;  // the indices one wave packs; a page's place in the dense array is a multiple of it
+
 inline void put_u32(std::vector<uint8_t>& out, uint32_t v) {
     for (int k = 0; k < 4; ++k) out.push_back((uint8_t)(v >> (8 * k)));
 }
 
 struct ChunkMeta {
-    uint64_t first_page_at = 0, bytes = 0, plain_bytes = 0, rows = 0, nulls = 0;  // bytes: as stored; plain_bytes: uncompressed
+    uint64_t first_page_at = 0, dict_page_at = 0, bytes = 0, plain_bytes = 0, rows = 0, nulls = 0;  // bytes: as stored; plain_bytes: uncompressed
     MinMax mm;
+    bool dict = false;
 };
 
 inline int32_t parquet_type(uint32_t t) { return t == OXH_CSV_INT64 ? 2 : t == OXH_CSV_FLOAT64 ? 5 : t == OXH_CSV_BOOL ? 0 : 6; }
@@ -242,8 +278,12 @@ inline int32_t parquet_type(uint32_t t) { return t == OXH_CSV_INT64 ? 2 : t == O
 // uncompressed bytes). Such a plan's pages name where the header goes (file_at, head_src, header_len) and how long
 // the stored body is (values_bytes); its chunks are codec SNAPPY, total_compressed_size the stored bytes and
 // total_uncompressed_size the headers as written plus the uncompressed bodies, the format's rule.
+// dicts: NULL without OXH_PARQUET_DICTIONARY; else ceil(nrows / group rows) * ncols entries. A chunk that dict_chunk()
+// accepts starts with its dictionary page -- one more entry of `pages` (and of `stored`), in the file's order -- and its
+// data pages are RLE_DICTIONARY, cut by the index stream's bytes; every other chunk is what it is without the flag.
 inline Plan make_plan(uint64_t nrows, uint32_t ncols, const uint32_t* types, const uint8_t* names, const uint64_t* name_offsets,
-                      uint64_t rows_per_group, uint64_t page_bytes, const Tile* tiles, const uint64_t* stored = nullptr) {
+                      uint64_t rows_per_group, uint64_t page_bytes, const Tile* tiles, const uint64_t* stored = nullptr,
+                      const ChunkDict* dicts = nullptr) {
     Plan p;
     const uint64_t group_rows = group_rows_of(rows_per_group), budget = page_bytes_of(page_bytes);
     const uint64_t ntiles = (nrows + kTileRows - 1) / kTileRows, group_tiles = group_rows / kTileRows;
@@ -259,6 +299,30 @@ inline Plan make_plan(uint64_t nrows, uint32_t ncols, const uint32_t* types, con
         Group g{std::min(nrows, t1 * kTileRows) - t0 * kTileRows, at, 0, 0, std::vector<ChunkMeta>(ncols)};
         for (uint32_t c = 0; c < ncols; ++c) {
             ChunkMeta& m = g.chunks[c];
+            m.dict = dicts && dict_chunk(types[c], dicts[groups.size() * ncols + c]);
+            const uint32_t width = m.dict ? dict_width(dicts[groups.size() * ncols + c].num_values) : 0;
+            const uint32_t dict_page = (uint32_t)p.pages.size();
+            const auto values_of = [&](uint64_t valid, uint64_t bytes) { return m.dict ? index_stream_len(valid, width) : values_len(types[c], valid, bytes); };
+            if (m.dict) {  // the dictionary page: its header, the entries behind it
+                const ChunkDict& d = dicts[groups.size() * ncols + c];
+                Page pg{};
+                pg.file_at = m.dict_page_at = at, pg.row0 = t0 * kTileRows, pg.tile0 = (uint32_t)t0, pg.col = c;
+                pg.nvalid = (uint32_t)d.num_values, pg.dict_width = width, pg.dict_page = dict_page;
+                const uint64_t kept = stored ? stored[p.pages.size()] : d.dict_bytes;
+                if (kept > kMaxPage) return p.error = "a compressed page of column " + std::to_string(c) + " has more than a PageHeader's int32", p;
+                Thrift th;
+                th.i32(1, 2);  // DICTIONARY_PAGE
+                th.i32(2, (int32_t)d.dict_bytes), th.i32(3, (int32_t)kept);
+                th.begin(7);
+                th.i32(1, (int32_t)d.num_values), th.i32(2, 0);  // PLAIN
+                th.end();
+                th.out.push_back(0);
+                p.header_len.push_back((uint32_t)th.out.size());
+                pg.head_src = p.blob.size(), pg.head_len = (uint32_t)th.out.size(), pg.values_bytes = kept;
+                p.blob.insert(p.blob.end(), th.out.begin(), th.out.end());
+                at += pg.head_len + kept, m.bytes += pg.head_len + kept, m.plain_bytes += pg.head_len + d.dict_bytes;
+                p.pages.push_back(pg);
+            }
             m.first_page_at = at;
             for (uint64_t t = t0; t < t1;) {
                 // one page: whole tiles until the levels and the values reach the budget
@@ -280,9 +344,9 @@ inline Plan make_plan(uint64_t nrows, uint32_t ncols, const uint32_t* types, con
                     rows += tile_rows, valid += tl.valid, bytes += tl.value_bytes;
                     m.mm.fold(tl, types[c]);
                     ++t;
-                } while (t < t1 && 4 + level_run_len(rows, valid < rows) + values_len(types[c], valid, bytes) < budget);
+                } while (t < t1 && 4 + level_run_len(rows, valid < rows) + values_of(valid, bytes) < budget);
                 const bool nulls = valid < rows;
-                const uint64_t run = level_run_len(rows, nulls), vbytes = values_len(types[c], valid, bytes);
+                const uint64_t run = level_run_len(rows, nulls), vbytes = values_of(valid, bytes);
                 const uint64_t body = 4 + run + vbytes;
                 if (body > kMaxPage || rows > kMaxPage)
                     return p.error = "a page of column " + std::to_string(c) + " has " + std::to_string(body) + " B: more than a PageHeader's int32", p;
@@ -292,7 +356,7 @@ inline Plan make_plan(uint64_t nrows, uint32_t ncols, const uint32_t* types, con
                 if (kept > kMaxPage) return p.error = "a compressed page of column " + std::to_string(c) + " has more than a PageHeader's int32", p;
                 th.i32(2, (int32_t)body), th.i32(3, (int32_t)kept);
                 th.begin(5);
-                th.i32(1, (int32_t)rows), th.i32(2, 0), th.i32(3, 3), th.i32(4, 3);  // PLAIN, RLE, RLE
+                th.i32(1, (int32_t)rows), th.i32(2, m.dict ? 8 : 0), th.i32(3, 3), th.i32(4, 3);  // PLAIN or RLE_DICTIONARY, RLE, RLE
                 th.end();
                 th.out.push_back(0);
                 p.header_len.push_back((uint32_t)th.out.size());
@@ -306,6 +370,10 @@ inline Plan make_plan(uint64_t nrows, uint32_t ncols, const uint32_t* types, con
                 pg.head_src = p.blob.size(), pg.head_len = (uint32_t)th.out.size();
                 pg.level_bytes = nulls ? (uint32_t)((rows + 7) / 8) : 0;
                 pg.values_bytes = vbytes, pg.rows = (uint32_t)rows, pg.nvalid = (uint32_t)valid;
+                if (m.dict) {
+                    pg.dict_width = width, pg.dict_page = dict_page, pg.dense_at = p.dense_indices;
+                    p.dense_indices += (valid + kDenseBlock - 1) / kDenseBlock * kDenseBlock;
+                }
                 p.blob.insert(p.blob.end(), th.out.begin(), th.out.end());
                 const uint64_t plain_whole = pg.head_len + pg.level_bytes + vbytes;  // == the header's bytes + body
                 const uint64_t whole = stored ? p.header_len.back() + kept : plain_whole;
@@ -348,11 +416,13 @@ inline Plan make_plan(uint64_t nrows, uint32_t ncols, const uint32_t* types, con
             f.i64(2, 0);  // file_offset: unused since the metadata sits in the footer
             f.begin(3);
             f.i32(1, parquet_type(types[c]));
-            f.list(2, kTI32, 2), f.varint(Thrift::zigzag(0)), f.varint(Thrift::zigzag(3));  // PLAIN, RLE
+            f.list(2, kTI32, m.dict ? 3 : 2), f.varint(Thrift::zigzag(0)), f.varint(Thrift::zigzag(3));  // PLAIN, RLE
+            if (m.dict) f.varint(Thrift::zigzag(8));  // RLE_DICTIONARY
             f.list(3, kTBinary, 1), f.raw_binary(names + name_offsets[c], name_offsets[c + 1] - name_offsets[c]);
             f.i32(4, stored ? 1 : 0);  // SNAPPY, UNCOMPRESSED
             f.i64(5, (int64_t)m.rows), f.i64(6, (int64_t)m.plain_bytes), f.i64(7, (int64_t)m.bytes);
             f.i64(9, (int64_t)m.first_page_at);
+            if (m.dict) f.i64(11, (int64_t)m.dict_page_at);
             f.begin(12);
             f.i64(3, (int64_t)m.nulls);
             if (m.mm.has) f.binary(5, &m.mm.max, 8), f.binary(6, &m.mm.min, 8);

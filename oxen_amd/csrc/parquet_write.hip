@@ -27,39 +27,16 @@
 // magic and footer), so the result does not depend on what the output or the scratch held. Every store is checked
 // against the page's own sizes first: columns that change during the call set the error word, they do not write
 // outside. No workgroup waits for another; launches order the steps.
-#include "capi_internal.hpp"
-#include "columns.hpp"
-#include "parquet_host.hpp"
+#include "parquet_device.hpp"
 
 using namespace oxh::capi;
 namespace pq = oxh::parquet;
 
 namespace oxh {
 
-constexpr uint32_t kPqSpanLds = 8192;      // a wave's LDS: one tile of 8-byte cells, or a run of string cells
 constexpr uint32_t kPqLongCell = 512;      // a string cell of this many bytes (its length word included) and more is the whole wave's
-constexpr unsigned kPqMaxGroups = 1024;    // workgroups of a launch (4 of 32 KiB LDS fill a CU); the rest by grid stride
-constexpr unsigned long long kPqErrCell = 4, kPqErrPlace = 8;  // beside kRowErrOffsets, kRowErrValues
-constexpr int kPqErr = 0, kPqCtrlWords = 8;
 static_assert(pq::kTileRows * 8 <= kPqSpanLds, "a tile of 8-byte cells fits the wave's LDS");
 
-struct PqCol {
-    RowCol c;
-    uint32_t type;  // OXH_CSV_*
-    uint32_t pad;
-};
-
-struct PqArgs {
-    const PqCol* cols;
-    uint64_t nrows, ntiles;
-    uint32_t ncols;
-};
-
-__device__ __forceinline__ bool pqw_present(const RowCol& c, uint64_t r) { return !c.validity || row_bit(c.validity, c.nbit + r); }
-// The set bits of a ballot below this lane.
-__device__ __forceinline__ uint32_t pqw_below(unsigned long long mask) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
-}
 __device__ __forceinline__ unsigned long long pqw_wave_sum(unsigned long long v) {
 #pragma unroll
     for (int off = 32; off; off >>= 1) v += (unsigned long long)__shfl_xor((long long)v, off, 64);
@@ -136,33 +113,6 @@ __global__ __launch_bounds__(256) void pqw_measure_kernel(const PqArgs a, pq::Ti
 }
 
 // ---------------------------------------------------------------- emit
-typedef uint32_t PqBlock16 __attribute__((ext_vector_type(4)));  // one 16-byte block
-// The output is global memory; saying so keeps the stores off the flat path.
-#define OXH_PQW_GLOBAL __attribute__((address_space(1)))
-
-// The emit kernel's LDS is private to a wave, whose LDS operations execute in order: the fences only keep the
-// compiler from moving them across (they emit no instruction).
-__device__ __forceinline__ void pqw_wave_lds_order() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// The n <= kPqSpanLds bytes staged from stage[d & 15] on to d[0 .. n): 16 bytes a lane on d's 16-byte grid, the
-// blocks that hold the span's head or tail byte by byte.
-__device__ __forceinline__ void pqw_store_span(uint8_t* d, uint64_t n, const uint8_t* stage, unsigned lane) {
-    const uintptr_t d0 = (uintptr_t)d, d1 = d0 + n, grid0 = d0 & ~(uintptr_t)15;
-    for (uint32_t b = 16 * lane; grid0 + b < d1; b += 16 * 64) {
-        const uintptr_t to = grid0 + b;
-        if (to >= d0 && to + 16 <= d1) {
-            *(OXH_PQW_GLOBAL PqBlock16*)to = *(const PqBlock16*)&stage[b];
-        } else {
-            for (uint32_t k = 0; k < 16; ++k)
-                if (to + k >= d0 && to + k < d1) *(OXH_PQW_GLOBAL uint8_t*)(to + k) = stage[b + k];
-        }
-    }
-}
-
 // n bytes from src (any alignment) to d, without LDS: each lane loads the 16 source bytes that fall on one block of
 // d's 16-byte grid and stores the block; the blocks that hold the span's head or tail go byte by byte.
 __device__ __forceinline__ void pqw_copy_span(uint8_t* d, const uint8_t* src, uint64_t n, unsigned lane) {
@@ -179,14 +129,6 @@ __device__ __forceinline__ void pqw_copy_span(uint8_t* d, const uint8_t* src, ui
         }
     }
 }
-
-struct PqEmit {
-    const pq::Page* pages;
-    const pq::Place* places;
-    const uint8_t* blob;
-    uint64_t npages;
-    uint8_t* out;
-};
 
 // One 64-row step of a tile: the rows that are not null, as the lane's flag and the wave's ballot; the step's 8
 // bytes of the page's bit-packed levels go to their place (`room`: the level bytes the tile owns; rows behind the
@@ -227,7 +169,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void p
         uint8_t* const vals = page_out + pg.head_len + pg.level_bytes;
         const uint32_t steps = a.nrows - r0 < pq::kTileRows ? (uint32_t)((a.nrows - r0 + 63) / 64) : 16u;
         bool live;
-        if ((pc.type == OXH_CSV_INT64 || pc.type == OXH_CSV_FLOAT64) && !pc.c.validity) {
+        if (pg.dict_width) {
+            // a page of a dictionary chunk (OXH_PARQUET_DICTIONARY): the levels here, and by the page's first tile the
+            // width byte and the run header of its index stream -- by the chunk's first tile the dictionary page's
+            // header too; the entries and the packed indices are parquet_dict.hip's
+            if (tile == pg.tile0) {
+                if (pl.page > 0 && pg.dict_page == pl.page - 1) {
+                    const pq::Page dp = e.pages[pg.dict_page];
+                    copy_span_wave(e.out + dp.file_at, e.blob + dp.head_src, dp.head_len, lane);
+                }
+                const uint64_t run = ((((uint64_t)pg.nvalid + 7) / 8) << 1) | 1;
+                const uint32_t nrun = pg.nvalid ? pq::varint_len(run) : 0;
+                if (1 + nrun > pg.values_bytes)
+                    bad |= kPqErrPlace;
+                else if (lane == 0)
+                    vals[0] = (uint8_t)pg.dict_width;
+                else if (lane <= nrun)
+                    vals[lane] = (uint8_t)(((run >> (7 * (lane - 1))) & 0x7F) | (lane < nrun ? 0x80 : 0));
+            }
+            for (uint32_t s = 0; s < steps && room; ++s) pqw_step(a, pc.c, r0 + 64 * s + lane, s, levels, room, lane, live);
+        } else if ((pc.type == OXH_CSV_INT64 || pc.type == OXH_CSV_FLOAT64) && !pc.c.validity) {
             // a column without validity: every row is its own rank, the tile is one straight shifted copy
             const uint64_t rows = a.nrows - r0 < pq::kTileRows ? a.nrows - r0 : pq::kTileRows;
             if (8ull * (pl.rank_base + rows) <= pg.values_bytes)
@@ -429,6 +390,11 @@ struct WriteCall {
     uint64_t at_tab = 0, at_sizes = 0, at_status = 0, at_heads = 0, at_blob = 0, nfrags = 0;
     int compress();
     int pack(uint8_t* d_out);
+    // OXH_PARQUET_DICTIONARY: the chunks' distinct values are built behind the measure kernel (parquet_dict.hip), what
+    // the planner reads of them comes down with the tile table, and emit() writes the dictionary chunks' values
+    // behind the emit kernel. The working memory lies in the lease behind the plan; it has no pinned mirror.
+    oxh::PqDict dict;
+    const pq::ChunkDict* dicts = nullptr;
 };
 
 int column_error(unsigned long long e) {
@@ -450,11 +416,17 @@ int WriteCall::measure(const pq::Args& a, const void* const* d_values, const voi
         const uint64_t tiles_at = small;
         plan_at = tiles_at + align256(items * sizeof(pq::Tile));
         plan_room = align256(items * (sizeof(pq::Place) + sizeof(pq::Page) + 64));  // a head is below 64 bytes
-        const uint64_t total = plan_at + plan_room;
+        // with dictionaries: the chunks' table behind the tiles, a dictionary page and its head more per chunk
+        const bool with_dict = a.flags & pq::kFlagDictionary;
+        const uint64_t group_rows = pq::group_rows_of(a.rows_per_group), nchunks = (n + group_rows - 1) / group_rows * a.ncols;
+        const uint64_t chunks_at = plan_at;
+        if (with_dict) plan_at += align256(nchunks * sizeof(pq::ChunkDict)), plan_room += align256(nchunks * (sizeof(pq::Page) + 64));
+        const uint64_t front = plan_at + plan_room, work = with_dict ? oxh::PqDict::work_bytes(n, a.ncols, a.types, group_rows) : 0;
+        const uint64_t total = front + work;
         void *lbase = nullptr, *pinned = nullptr;
-        if (lease.get(total, &lbase) != hipSuccess || lease.pinned(total, &pinned) != hipSuccess) {
+        if (lease.get(total, &lbase) != hipSuccess || lease.pinned(front, &pinned) != hipSuccess) {
             (void)hipGetLastError();
-            return fail(OXH_ERR_NOMEM, "parquet write: " + std::to_string(total) + " B of tile table and plan");
+            return fail(OXH_ERR_NOMEM, "parquet write: " + std::to_string(total) + " B of tile table, plan and dictionary tables");
         }
         d_base = (uint8_t*)lbase, h_base = (uint8_t*)pinned;
         memset(h_base, 0, cols_at);
@@ -472,7 +444,12 @@ int WriteCall::measure(const pq::Args& a, const void* const* d_values, const voi
         HIP_TRY(hipMemcpyAsync(d_base, h_base, small, hipMemcpyHostToDevice, st));
         oxh::pqw_measure_kernel<<<grid(), 256, 0, st>>>(args, (pq::Tile*)(d_base + tiles_at), d_ctrl);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(h_base + tiles_at, d_base + tiles_at, items * sizeof(pq::Tile), hipMemcpyDeviceToHost, st));
+        if (work) {
+            const int rc = dict.build(args, a.types, group_rows, d_base + front, (pq::ChunkDict*)(d_base + chunks_at), d_ctrl, st);
+            if (rc) return rc;
+            dicts = (const pq::ChunkDict*)(h_base + chunks_at);
+        }
+        HIP_TRY(hipMemcpyAsync(h_base + tiles_at, d_base + tiles_at, (work ? plan_at - tiles_at : items * sizeof(pq::Tile)), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(h_ctrl, d_ctrl, 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         const int rc = column_error(h_ctrl[oxh::kPqErr]);
@@ -481,7 +458,7 @@ int WriteCall::measure(const pq::Args& a, const void* const* d_values, const voi
     }
     static const pq::Tile none{};
     if (!tiles) tiles = &none;  // never read: there is no tile
-    plan = pq::make_plan(n, a.ncols, a.types, a.names, a.name_offsets, a.rows_per_group, a.page_bytes, tiles);
+    plan = pq::make_plan(n, a.ncols, a.types, a.names, a.name_offsets, a.rows_per_group, a.page_bytes, tiles, nullptr, dicts);
     if (!plan.error.empty()) return fail(OXH_ERR_INVALID, "parquet write: " + plan.error);
     STEP("parquet write: %llu rows x %u columns, %llu B, %llu row groups, %llu pages", (unsigned long long)n, a.ncols,
          (unsigned long long)plan.out_bytes, (unsigned long long)plan.row_groups, (unsigned long long)plan.pages.size());
@@ -505,6 +482,10 @@ int WriteCall::emit(uint8_t* d_out) {
         const oxh::PqEmit em{(const pq::Page*)(d + places_bytes), (const pq::Place*)d, d + places_bytes + pages_bytes, plan.pages.size(), d_out};
         oxh::pqw_emit_kernel<<<grid(), 256, 0, st>>>(args, em, d_ctrl);
         HIP_TRY(hipGetLastError());
+        if (dicts) {
+            const int rc = dict.write(args, em, plan, d_ctrl, st);
+            if (rc) return rc;
+        }
         HIP_TRY(hipMemcpyAsync(h_ctrl, d_ctrl, 8, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
@@ -550,7 +531,7 @@ int WriteCall::compress() {
         kept[k] = pq::varint_len(tab[np + k] - tab[k]);
         for (uint64_t f = frag0[k]; f < frag0[k + 1]; ++f) kept[k] += frag_size[f];
     }
-    stored = pq::make_plan(a.nrows, a.ncols, a.types, a.names, a.name_offsets, a.rows_per_group, a.page_bytes, tiles, kept.data());
+    stored = pq::make_plan(a.nrows, a.ncols, a.types, a.names, a.name_offsets, a.rows_per_group, a.page_bytes, tiles, kept.data(), dicts);
     if (!stored.error.empty()) return fail(OXH_ERR_INVALID, "parquet write: " + stored.error);
     if (stored.pages.size() != np) return fail(OXH_ERR_HIP, "parquet write: the SNAPPY plan has other pages than the uncompressed one");
     return OXH_OK;

@@ -2405,12 +2405,12 @@ class ParquetWriteStats(NamedTuple):
     nulls: int
 
 
-def _parquet_head(frame: Mapping, rows_per_group, page_bytes, types, compression=None):
+def _parquet_head(frame: Mapping, rows_per_group, page_bytes, types, compression=None, dictionary=False):
     # the columns, types and names as the CSV writer's call takes them; its own tail (separator, quote, header) is not used
     if compression not in (None, "none", "snappy"):
         raise _capi.OxenError(f"compression {compression!r}: None, 'none' or 'snappy'", _capi.OXH_ERR_INVALID)
     cols, type_words, name_bytes, name_offsets, _ = _write_head(frame, ",", '"', True, types)
-    flags = _capi.OXH_PARQUET_SNAPPY if compression == "snappy" else 0
+    flags = (_capi.OXH_PARQUET_SNAPPY if compression == "snappy" else 0) | (_capi.OXH_PARQUET_DICTIONARY if dictionary else 0)
     return cols, type_words, name_bytes, name_offsets, (int(rows_per_group or 0), int(page_bytes or 0), flags)
 
 
@@ -2420,16 +2420,18 @@ def _parquet_call(*args):
 
 
 def write_parquet(frame: Mapping, path=None, rows_per_group=None, page_bytes=None, types=None, ctx: Optional[_capi.Context] = None,
-                  with_stats: bool = False, compression=None):
+                  with_stats: bool = False, compression=None, dictionary: bool = False):
     """oxh_write_parquet_host: the frame (an ordered {name: Column}, or what `column` takes, in host memory) as the bytes
     of a Parquet file by the rules of include/oxen_hash.h "Parquet" -- uncompressed, PLAIN values, DataPage V1, what
     `write_df`'s parquet arm (core/df/tabular.rs:1508-1517) is for; polars, pyarrow and DuckDB read it. rows_per_group
     (None: 1 048 576; a multiple of 1 024) and page_bytes (None: 1 MiB) cut the row groups and pages. path, types and
     the key order are `write_csv`'s. compression: None or "none", or "snappy" (OXH_PARQUET_SNAPPY: every page body one raw
     Snappy block, compressed on the device; the first call then gives a capacity that suffices, the second the size).
+    dictionary: True sets OXH_PARQUET_DICTIONARY -- every INT64, DOUBLE and string column chunk within the header's three
+    limits gets a dictionary page and RLE_DICTIONARY data pages, built on the device; the others stay PLAIN.
     `write_df` itself still refuses `.parquet`: this is the entry."""
     frame = _as_frame(frame)
-    cols, type_words, name_bytes, name_offsets, tail = _parquet_head(frame, rows_per_group, page_bytes, types, compression)
+    cols, type_words, name_bytes, name_offsets, tail = _parquet_head(frame, rows_per_group, page_bytes, types, compression, dictionary)
     keep = []
 
     def ptr(a):
@@ -2453,16 +2455,16 @@ def write_parquet(frame: Mapping, path=None, rows_per_group=None, page_bytes=Non
 
 
 def write_parquet_device(frame: Mapping, rows_per_group=None, page_bytes=None, types=None, ctx: Optional[_capi.Context] = None,
-                         capacity: Optional[int] = None, stream=None, with_stats: bool = False, compression=None):
+                         capacity: Optional[int] = None, stream=None, with_stats: bool = False, compression=None, dictionary: bool = False):
     """oxh_write_parquet_device over device `Column`s; the file's bytes as a uint8 torch tensor on the device. It
     measures, allocates, then writes; a caller's `capacity` (bytes) skips the measure, and a capacity below the need is
-    the library's error. compression as `write_parquet`'s: with "snappy" the tensor is allocated at the bound and
+    the library's error. compression and dictionary as `write_parquet`'s: with "snappy" the tensor is allocated at the bound and
     returned sliced to the file's size. Blocks."""
     import torch
 
     from .device import _require_cuda, _stream
 
-    cols, type_words, name_bytes, name_offsets, tail = _parquet_head(frame, rows_per_group, page_bytes, types, compression)
+    cols, type_words, name_bytes, name_offsets, tail = _parquet_head(frame, rows_per_group, page_bytes, types, compression, dictionary)
     tensors = [t for c in cols for t in (c.values, c.offsets, c.validity) if t is not None]
     _require_cuda(*tensors)
     if any(not t.is_contiguous() for t in tensors):
