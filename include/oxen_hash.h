@@ -1373,7 +1373,8 @@ int oxh_jsonl_columns_host(void* jsonl, uint32_t nsel, const uint32_t* col_idx, 
  * `oxen df`, diff and workspace path once a file is committed as `.parquet`, and takes the height from the metadata
  * (ParquetReader::num_rows, :1445). oxh_parquet_* do it on the device: the bytes of an UNCOMPRESSED or, with
  * OXH_PARQUET_INFLATE, SNAPPY Parquet file with a FLAT schema in HBM to a page index (a handle), then to the typed columns oxh_csv_columns_* produce, which
- * every tabular entry above takes as they are and oxh_write_parquet_* writes back.
+ * every tabular entry above takes as they are and oxh_write_parquet_* writes back. Columns that are lists of numbers
+ * ("Lists" below) are read beside them, through oxh_parquet_lists_*.
  *   Read. Leaf columns directly under the root, REQUIRED or OPTIONAL (max definition level 0 or 1). Physical types:
  *     BOOLEAN -> OXH_COL_BOOL; INT32, FLOAT -> OXH_COL_FIXED4; INT64, DOUBLE -> OXH_COL_FIXED8; BYTE_ARRAY ->
  *     OXH_COL_BYTES32 or OXH_COL_BYTES64, the caller's choice. Logical and converted types are NOT interpreted: the
@@ -1397,10 +1398,28 @@ int oxh_jsonl_columns_host(void* jsonl, uint32_t nsel, const uint32_t* col_idx, 
  *     compressing it would not shrink it).
  *     Cost: the handle holds the inflated size of ALL compressed pages of the file in device memory until
  *     oxh_parquet_close, whichever columns are read later.
+ *   Lists. A column whose schema is the standard three-level LIST is read as Arrow's List / LargeList: an OPTIONAL
+ *     or REQUIRED group annotated LIST (converted or logical type), directly under the root, with exactly one REPEATED
+ *     group child, which has exactly one leaf child, OPTIONAL or REQUIRED, of physical type INT32, INT64, FLOAT or
+ *     DOUBLE; the middle group's and the element's names do not matter (list / element, bag / array_element, list /
+ *     item), and pyarrow writes fixed_size_list as exactly this shape. Max repetition level 1, max definition level 1
+ *     to 3. The column keeps the outer group's name and takes one chunk per row group, as a leaf. Its pages' level
+ *     entries are not rows: a row begins at every entry of repetition level 0 and may run on through the following
+ *     pages (nothing assumes that a page begins with a row, except a chunk's first); Arrow's offsets, the lists'
+ *     validity, the elements' validity and the values are found from the two level streams on the device (rank and
+ *     select over ballot words; parquet_lists.hip). A null list has no elements, a null element's value is 0. Levels:
+ *     RLE with any mix of RLE and bit-packed runs; values: PLAIN and the dictionary encodings, as above, read from
+ *     the file or from the image. Offsets are int32 (at most 2^31 - 1 elements a column, else OXH_ERR_INVALID naming
+ *     OXH_PARQUET_LIST64) or int64. Opening a file costs nothing more for its lists; a call holds, per 64 level
+ *     entries of the widest selected column, 44 bytes of words and counts and 256 bytes of dictionary indices.
+ *     Stated and not built: lists of strings, booleans, structs or lists; maps; the legacy two-level form.
  *   Refused at open, the message naming the column and the cause: a codec that is not read (the codec's number
  *     is named, so that a caller can route the file to the CPU; a V2 page's is_compressed flag means nothing without a
- *     codec and is ignored), nested fields, repeated fields, encrypted files. Refused at oxh_parquet_columns_* when the
- *     column is selected: INT96 and FIXED_LEN_BYTE_ARRAY (known from the footer: oxh_parquet_types says so), and what
+ *     codec and is ignored), nested fields (a struct, a map, a list of lists or of structs, a group that only looks like
+ *     a list: every group that is not the LIST above), repeated fields (the legacy two-level list, a bare REPEATED
+ *     leaf), encrypted files. Refused when the column is selected, at oxh_parquet_columns_* or oxh_parquet_lists_*:
+ *     INT96 and FIXED_LEN_BYTE_ARRAY, and a list whose elements are BOOLEAN, BYTE_ARRAY, INT96 or
+ *     FIXED_LEN_BYTE_ARRAY (known from the footer: oxh_parquet_types says so), and what
  *     only the pages show -- DELTA_* and BYTE_STREAM_SPLIT or any other value encoding, repetition levels, level
  *     encodings other than RLE, index pages. An unselected column of these does not stop the others.
  *   Stated and not built: gzip, lz4 and brotli; inflating only the columns that are read;
@@ -1425,7 +1444,8 @@ int oxh_jsonl_columns_host(void* jsonl, uint32_t nsel, const uint32_t* col_idx, 
  * footer that is no FileMetaData; an encrypted footer; a schema without a root; a nested field; a repeated field;
  * more than 2^40 rows; per row group, in order: a chunk count that is not the schema's, a chunk without plain
  * metadata, a codec other than UNCOMPRESSED (with OXH_PARQUET_INFLATE: other than that and SNAPPY; with OXH_PARQUET_INFLATE_ZSTD: and ZSTD), a chunk that is not inside the file in front of the footer, a
- * num_values that is not the group's rows; group rows that do not sum to num_rows. Chunks are NOT checked against
+ * num_values that is not the group's rows (a list's chunk counts level entries: one that is LESS than the group's
+ * rows); group rows that do not sum to num_rows. Chunks are NOT checked against
  * their neighbours: chunks that overlap are read as they stand (every load stays inside its own chunk). In the host form the footer is in
  * host memory and its refusals come BEFORE OXH_ERR_NODEVICE; in the device form it has to come down first, so
  * OXH_ERR_NODEVICE and a NULL ctx come before them. Then the page walk: a page header that runs past its chunk,
@@ -1439,12 +1459,32 @@ int oxh_jsonl_columns_host(void* jsonl, uint32_t nsel, const uint32_t* col_idx, 
  * oxh_parquet_close: NULL is OXH_OK.
  * oxh_parquet_names: the names, by the size-then-fill contract of oxh_csv_header.
  * oxh_parquet_types: per column, types4[4 c ..] = {the type word it is read as natively (0: none), its physical
- * type (the format's number), 1 if REQUIRED, 1 if this reader can read it}. OXH_ERR_INVALID: a NULL handle; NULL
- * types4 with columns.
+ * type (the format's number), 1 if REQUIRED, 1 if this reader can read it}; a list column: OXH_PARQUET_LIST | its
+ * element's native word, the element's physical type, whether the list itself is REQUIRED. stats8[6] counts no list
+ * this reader reads. OXH_ERR_INVALID: a NULL handle; NULL types4 with columns.
  * oxh_parquet_columns_*: the parameters, outputs, measure-only mode, size-then-fill contract and checks (in the same
  * order) of oxh_csv_columns_*, with OXH_CSV_INT32 and OXH_CSV_FLOAT32 known; then, per selection in order: a column
  * this reader cannot read (its cause named), a type word that does not fit the column's physical type. stats4 =
- * {nulls, dictionary-coded values, pages (data and dictionary), value bytes}. Messages start with "parquet columns:". */
+ * {nulls, dictionary-coded values, pages (data and dictionary), value bytes}. Messages start with "parquet columns:".
+ * A list column is OXH_ERR_INVALID here and names oxh_parquet_lists_*.
+ * oxh_parquet_lists_*: the list columns, by the same selection tables, measure-only mode (all four output tables NULL)
+ * and size-then-fill contract. types[k] = OXH_PARQUET_LIST | the element's word -- its native one, or
+ * OXH_CSV_INT64 on INT32 elements, OXH_CSV_FLOAT64 on FLOAT ones --, with OXH_PARQUET_LIST64 for int64 offsets. Per
+ * selection: values[k] the elements (4- or 8-byte cells, aligned to them), offsets[k] nrows + 1 int32 / int64 that
+ * count elements, validity[k] the lists' bitmap ((nrows + 7) / 8 bytes), child_validity[k] the elements' bitmap
+ * ((value_capacity[k] / the cell's bytes + 7) / 8 bytes at most); bits behind the last row or element are 0.
+ * value_capacity[k]: the bytes of values[k]; value_bytes[k] = elements x the cell's bytes, known from the measure; a
+ * column above its capacity is OXH_ERR_INVALID and writes nothing. stats4 = {null lists, null elements, pages (data
+ * and dictionary), elements}. OXH_ERR_INVALID, every message starting with "parquet lists:", in this order: a NULL or
+ * foreign handle; NULL col_idx or types; a column index beyond the file's; a type word that is not OXH_PARQUET_LIST on
+ * a fixed-width element's word; NULL value_bytes or stats4; only some output tables NULL; NULL value_capacity with
+ * outputs; per selection a NULL validity or offsets, offsets not aligned to its entries, a capacity without values
+ * or child_validity, values not aligned to its cells; then per selection a column this reader cannot read (its cause
+ * named), a column that is not a list (it names oxh_parquet_columns_*), an element word that does not fit the
+ * elements' physical type; then OXH_ERR_NODEVICE; then what only the pages show, per selection in order: level
+ * streams that are malformed, end early or hold a level above the column's maximum, or a chunk whose first entry is
+ * not a row's first; dictionary indices that are malformed; row starts that are not every row group's rows; more than
+ * 2^31 - 1 elements with int32 offsets; a capacity below the elements; a PLAIN page shorter than its values. */
 #define OXH_CSV_INT32 6   /* oxh_parquet_columns_* only */
 #define OXH_CSV_FLOAT32 7 /* oxh_parquet_columns_* only */
 #define OXH_PARQUET_INFLATE 2u /* flags of oxh_parquet_open_*: read SNAPPY chunks too */
@@ -1460,6 +1500,16 @@ int oxh_parquet_columns_device(void* parquet, uint32_t nsel, const uint32_t* col
 int oxh_parquet_columns_host(void* parquet, uint32_t nsel, const uint32_t* col_idx, const uint32_t* types, const uint64_t* value_capacity,
                              void* const* values, void* const* offsets, uint8_t* const* validity, uint64_t* value_bytes,
                              uint64_t* stats4);
+/* List columns (see "Lists" above): the type word of selection k is OXH_PARQUET_LIST | the element's word, with
+ * OXH_PARQUET_LIST64 for int64 offsets. */
+#define OXH_PARQUET_LIST 256   /* oxh_parquet_types, oxh_parquet_lists_*: a list of the word's low bits */
+#define OXH_PARQUET_LIST64 512 /* oxh_parquet_lists_* only, beside OXH_PARQUET_LIST: nrows + 1 int64 offsets */
+int oxh_parquet_lists_device(void* parquet, uint32_t nsel, const uint32_t* col_idx, const uint32_t* types, const uint64_t* value_capacity,
+                             void* const* d_values, void* const* d_offsets, uint8_t* const* d_validity, uint8_t* const* d_child_validity,
+                             uint64_t* value_bytes, uint64_t* stats4, void* stream);
+int oxh_parquet_lists_host(void* parquet, uint32_t nsel, const uint32_t* col_idx, const uint32_t* types, const uint64_t* value_capacity,
+                           void* const* values, void* const* offsets, uint8_t* const* validity, uint8_t* const* child_validity,
+                           uint64_t* value_bytes, uint64_t* stats4);
 
 /* ---------------------------------------------------------------- Snappy: many raw blocks inflated per call
  * What a SNAPPY Parquet page holds (pyarrow, pandas, Spark and DuckDB write that codec by default), and what

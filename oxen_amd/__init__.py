@@ -53,6 +53,7 @@ _FROM_TABULAR = ("KeyedDiff", "STATUS_NAMES", "keyed_diff_digests", "keyed_diff_
                  "write_jsonl_device", "write_json", "write_json_device", "ParquetWriteStats",
                  "write_parquet", "write_parquet_device", "JsonlStats", "JsonlFile", "read_jsonl", "read_jsonl_device",
                  "jsonl_shape", "jsonl_schema", "read_df", "ParquetStats", "ParquetColumnStats", "ParquetColumnType", "ParquetFile",
+                 "ListColumn", "ParquetListStats", "embedding_from_list",
                  "read_parquet", "read_parquet_device", "parquet_shape", "parquet_schema", "snappy_bound", "snappy_compress",
                  "snappy_compress_device")
 

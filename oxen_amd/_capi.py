@@ -78,6 +78,8 @@ OXH_PARQUET_SNAPPY = 2   # flags of oxh_write_parquet_*: every page body one raw
 OXH_PARQUET_DICTIONARY = 4  # flags of oxh_write_parquet_*: RLE_DICTIONARY chunks where the data allow
 OXH_PARQUET_INFLATE = 2  # flags of oxh_parquet_open_*: read SNAPPY chunks too
 OXH_PARQUET_INFLATE_ZSTD = 4  # flags of oxh_parquet_open_*: read ZSTD chunks too
+OXH_PARQUET_LIST = 256    # oxh_parquet_types, oxh_parquet_lists_*: a list of the word's low bits
+OXH_PARQUET_LIST64 = 512  # oxh_parquet_lists_* only, beside OXH_PARQUET_LIST: int64 offsets
 OXH_ZSTD_CAUSES = ("", "frame", "header", "input", "block", "literals", "table", "sequences", "offset", "overrun", "truncated", "range")   # OXH_ZSTD_* by number
 OXH_SNAPPY_CAUSES = ("", "preamble", "input", "offset zero", "offset beyond", "overrun", "truncated", "range")   # OXH_SNAPPY_* by number
 
@@ -250,6 +252,10 @@ SIGNATURES = {
                                           ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u64p, _u64p, _vp]),
     "oxh_parquet_columns_host": (_int, [_vp, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32), _u64p, ctypes.POINTER(_vp),
                                         ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u64p, _u64p]),
+    "oxh_parquet_lists_device": (_int, [_vp, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32), _u64p, ctypes.POINTER(_vp),
+                                        ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u64p, _u64p, _vp]),
+    "oxh_parquet_lists_host": (_int, [_vp, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32), _u64p, ctypes.POINTER(_vp),
+                                      ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u64p, _u64p]),
     "oxh_snappy_inflate_device": (_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64p, _vp]),
     "oxh_snappy_inflate_host": (_int, [_vp, _u64, _vp, _u64p, _vp, _u64p, ctypes.POINTER(_u32), _u64p]),
     "oxh_zstd_inflate_device": (_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64p, _vp]),

@@ -33,61 +33,24 @@
 //            word and ends the page. pq_strlen_kernel, a lane per row, gives every row its source and length (a null
 //            0); exclusive_scan_u32 gives the offsets, its total the measure's value bytes; pq_strcopy_kernel copies,
 //            a cell of 512 bytes and more by the whole wave.
+// List columns (repetition levels) are parquet_lists.hip's, over the same handle (parquet_read_device.hpp).
 // One writer per output byte; scratch that a malformed page cuts short is filled with zeros, so no result depends on
 // what scratch or the outputs held; every load is bounded by the page, run or window it belongs to.
-#include "capi_internal.hpp"
-#include "columns.hpp"
-#include "parquet_read_host.hpp"
+#include "parquet_read_device.hpp"
 
 using namespace oxh::capi;
 
 namespace oxh {
 
 namespace pqr {
-constexpr unsigned long long kErrLevels = 2, kErrIndex = 4, kErrValues = 8, kErrChain = 16, kErrPlace = 32;
-// ctrl words of one selected column
-constexpr int kColNulls = 0, kColDictValues = 1, kColBytes = 2, kColErr = 3, kColWords = 8;
 constexpr uint32_t kWindow = 1024;  // bytes of a page the chase looks at at once: 64 lanes x 16
 constexpr uint32_t kLongCell = csv::kLongCell;
 }  // namespace pqr
-
-// What the column kernels read of one column.
-struct PqColumn {
-    const uint8_t* bytes;
-    const uint8_t* image;  // the inflated bodies of the compressed pages (NULL: the file has none)
-    const pqr::DataPage* pages;
-    const pqr::DictPage* dicts;
-    uint64_t nrows;
-    uint32_t npages, ndicts, optional;
-    uint64_t* words;       // optional columns: the page-local validity words
-    uint32_t* prefix;      // per word: the page's valid rows in front of it
-    uint32_t* page_valid;  // per data page
-    uint32_t* idx;         // per row: at row0 + rank, the index (or RLE boolean) of the page's value of that rank
-    uint32_t *cell_at, *cell_len;  // PLAIN byte arrays: at row0 + rank, the cell in its page's body
-    uint32_t *dict_at, *dict_len;  // per dictionary entry: the cell in its page's body
-};
-
-// Where a page's body starts: in the file, or in the image once inflated.
-template <class Page>
-__device__ __forceinline__ const uint8_t* pq_body(const PqColumn& c, const Page& pg) {
-    return (pg.in_image ? c.image : c.bytes) + pg.body;
-}
-// The same for a place the length pass hands to the copy: the top bit says the image.
-constexpr uint64_t kPqInImage = 1ull << 63;
-template <class Page>
-__device__ __forceinline__ uint64_t pq_place(const Page& pg, uint64_t at) { return (pg.body + at) | (pg.in_image ? kPqInImage : 0); }
-__device__ __forceinline__ const uint8_t* pq_at(const PqColumn& c, uint64_t place) {
-    return (place & kPqInImage ? c.image : c.bytes) + (place & ~kPqInImage);
-}
 
 __device__ __forceinline__ void pq_wave_lds_order() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ void pq_store_word(uint8_t* bitmap, unsigned long long word, uint64_t row0, uint64_t n, unsigned lane) {
-    if (bitmap && lane < 8 && row0 + 8 * lane < n) bitmap[(row0 >> 3) + lane] = (uint8_t)(word >> (8 * lane));
 }
 
 // ---------------------------------------------------------------- open: the page walk
@@ -130,7 +93,8 @@ __global__ __launch_bounds__(64) void pq_walk_kernel(const uint8_t* __restrict__
                     r.flags |= pqr::kPageLevelsLater;  // the inflated body's: the open finishes the record
                 else
                     pqr::finish_v1_levels(r, pqr::le32(bytes + c.at + body));
-                if (h.def_enc != pqr::kEncRle) r.flags |= 2;
+                // a list's chunk (optional == 2): the length read here is its repetition stream's (pqr::ListPage)
+                if (h.def_enc != pqr::kEncRle || (c.optional == 2 && h.rep_enc != pqr::kEncRle)) r.flags |= 2;
             } else if (h.type == pqr::kPageDataV2) {
                 if (h.rep_len < 0 || h.def_len < 0) {
                     bad = true;
@@ -285,21 +249,6 @@ __global__ __launch_bounds__(256) void pq_index_kernel(const PqColumn c, unsigne
         if (coded) atomicAdd(&ctrl[pqr::kColDictValues], coded);
         if (bad) __hip_atomic_fetch_or(&ctrl[pqr::kColErr], bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-}
-
-// Where the value of rank `rank` of width W of page pg starts, NULL (and *bad) where its bytes are not the page's
-// or the dictionary's.
-template <uint32_t W>
-__device__ __forceinline__ const uint8_t* pq_fixed_source(const PqColumn& c, const pqr::DataPage& pg, uint32_t rank, bool& bad) {
-    if (pg.dict != ~0u) {
-        const pqr::DictPage& d = c.dicts[pg.dict];
-        const uint64_t k = c.idx[pg.row0 + rank];
-        if ((k + 1) * W > d.body_size) return bad = true, nullptr;
-        return pq_body(c, d) + k * W;
-    }
-    const uint64_t at = (uint64_t)pg.values_at + (uint64_t)rank * W;
-    if (at + W > pg.body_size) return bad = true, nullptr;
-    return pq_body(c, pg) + at;
 }
 
 // SRC: the bytes of a value in the file; DST: of a cell of `values`; a 4 -> 8 store sign-extends an integer and
@@ -535,6 +484,18 @@ __global__ __launch_bounds__(256) void pq_clear_kernel(unsigned long long* __res
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) words[i] = 0;
 }
 
+int pq_index_enqueue(const PqColumn& c, unsigned long long* d_ctrl, hipStream_t st) {
+    pq_index_kernel<<<pq_wave_grid(c.npages), 256, 0, st>>>(c, d_ctrl);
+    HIP_TRY(hipGetLastError());
+    return OXH_OK;
+}
+
+int pq_clear_enqueue(unsigned long long* d_words, uint64_t n, hipStream_t st) {
+    pq_clear_kernel<<<pq_cap_grid((n + 255) / 256), 256, 0, st>>>(d_words, n);
+    HIP_TRY(hipGetLastError());
+    return OXH_OK;
+}
+
 }  // namespace oxh
 
 namespace {
@@ -543,50 +504,13 @@ namespace csv = oxh::csv;
 namespace pqr = oxh::pqr;
 using oxh::PqColumn;
 
-constexpr uint64_t kParquetMagic = 0x4F58485051523031ull;  // "OXHPQR01"
+using oxh::ParquetHandle;
 
-struct ParquetHandle {
-    uint64_t magic = kParquetMagic;
-    oxh_ctx* ctx = nullptr;
-    int device = 0;
-    const uint8_t* d_bytes = nullptr;
-    uint8_t* owned = nullptr;  // the host form's device copy
-    uint8_t* image = nullptr;  // the inflated bodies of every compressed page, until close
-    uint64_t image_bytes = 0, pages_inflated = 0;
-    uint64_t nbytes = 0;
-    pqr::Footer footer;
-    std::vector<pqr::ColumnPages> columns;  // per column; `cause` where the reader cannot read it
-    std::vector<uint8_t> names;
-    std::vector<uint64_t> name_offsets;
-    uint64_t data_pages = 0, dict_pages = 0;
-    ~ParquetHandle() {
-        magic = 0;
-        if (owned) (void)hipFree(owned);
-        if (image) (void)hipFree(image);
-    }
-    uint64_t nrows() const { return footer.nrows; }
-    uint64_t ncols() const { return footer.leaves.size(); }
-};
-
-unsigned cap_grid(uint64_t groups) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>(groups, 1), 2048); }
-unsigned row_grid(uint64_t n) { return cap_grid((n + 255) / 256); }
-// The page kernels, a wave per page: at most 512 waves, the rest by grid stride. A page's work is a serial chase of run
-// headers or lengths, and a column of more than 512 pages of the usual MiB is half a GiB: the rounds are not what it
-// waits for. (Files cut into many small pages pay for it; not measured.)
-unsigned wave_grid(uint64_t jobs) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>((jobs + 3) / 4, 1), 128); }
-
-ParquetHandle* handle_of(void* p) {
-    ParquetHandle* h = (ParquetHandle*)p;
-    return h && h->magic == kParquetMagic ? h : nullptr;
-}
-
-int device_enter(oxh_ctx* ctx) {
-    int rc = check_device(ctx ? ctx->device : 0);  // there is no CPU path
-    if (rc) return rc;
-    if (!ctx) return fail(OXH_ERR_INVALID, "ctx is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
-    return OXH_OK;
-}
+unsigned cap_grid(uint64_t groups) { return oxh::pq_cap_grid(groups); }
+unsigned row_grid(uint64_t n) { return oxh::pq_row_grid(n); }
+unsigned wave_grid(uint64_t jobs) { return oxh::pq_wave_grid(jobs); }
+ParquetHandle* handle_of(void* p) { return oxh::pq_handle_of(p); }
+int device_enter(oxh_ctx* ctx) { return oxh::pq_device_enter(ctx); }
 
 void take_footer(ParquetHandle& h, pqr::Footer&& f) {
     h.footer = std::move(f);
@@ -720,7 +644,8 @@ int open_run(ParquetHandle& h, uint64_t* stats8, hipStream_t st) {
     const uint64_t ncols = h.ncols(), nchunks = f.chunks.size();
     std::vector<pqr::ChunkDesc> chunks(nchunks);
     for (uint64_t k = 0; k < nchunks; ++k)
-        chunks[k] = pqr::ChunkDesc{f.chunks[k].at, f.chunks[k].bytes, f.chunks[k].num_values, f.leaves[k % ncols].required ? 0u : 1u, 0, f.chunks[k].codec, 0};
+        chunks[k] = pqr::ChunkDesc{f.chunks[k].at, f.chunks[k].bytes, f.chunks[k].num_values, f.leaves[k % ncols].list ? 2u : f.leaves[k % ncols].required ? 0u : 1u,
+                                   0, f.chunks[k].codec, 0};
     std::vector<uint32_t> counts(nchunks, 0);
     std::vector<pqr::PageRec> recs;
     if (nchunks) {
@@ -793,7 +718,7 @@ int open_run(ParquetHandle& h, uint64_t* stats8, hipStream_t st) {
     h.columns.resize(ncols);
     for (uint64_t c = 0; c < ncols; ++c) {
         if (f.leaves[c].cause.empty())
-            h.columns[c] = pqr::column_pages(f, c, chunks, counts, recs);
+            h.columns[c] = (f.leaves[c].list ? pqr::list_pages : pqr::column_pages)(f, c, chunks, counts, recs);
         else
             h.columns[c].cause = f.leaves[c].cause;
         unreadable += !h.columns[c].cause.empty();
@@ -959,6 +884,7 @@ int columns_enter(void* handle, const csv::ColumnsArgs& a, ParquetHandle*& h, bo
         const pqr::Leaf& leaf = h->footer.leaves[a.col_idx[k]];
         const std::string col = "selection " + std::to_string(k) + ", column '" + leaf.name + "': ";
         if (!h->columns[a.col_idx[k]].cause.empty()) return fail(OXH_ERR_INVALID, "parquet columns: " + col + h->columns[a.col_idx[k]].cause);
+        if (leaf.list) return fail(OXH_ERR_INVALID, "parquet columns: " + col + "a list column: oxh_parquet_lists_* read it");
         if (!pqr::type_fits(leaf.physical, a.types[k]))
             return fail(OXH_ERR_INVALID, "parquet columns: " + col + "physical type " + pqr::physical_name(leaf.physical) + " is not read as type " + std::to_string(a.types[k]));
     }
@@ -1090,7 +1016,8 @@ int oxh_parquet_types(void* parquet, uint32_t* types4) {
     if (h->ncols() && !types4) return fail(OXH_ERR_INVALID, "parquet types: types4 is NULL");
     for (uint64_t c = 0; c < h->ncols(); ++c) {
         const pqr::Leaf& leaf = h->footer.leaves[c];
-        types4[4 * c] = pqr::native_type(leaf.physical), types4[4 * c + 1] = (uint32_t)leaf.physical, types4[4 * c + 2] = leaf.required;
+        types4[4 * c] = pqr::native_type(leaf.physical) | (leaf.list && pqr::list_element_read(leaf.physical) ? OXH_PARQUET_LIST : 0u);
+        types4[4 * c + 1] = (uint32_t)leaf.physical, types4[4 * c + 2] = leaf.required;
         types4[4 * c + 3] = h->columns[c].cause.empty();
     }
     return OXH_OK;

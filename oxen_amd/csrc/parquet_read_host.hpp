@@ -42,13 +42,29 @@ inline bool type_fits(int32_t physical, uint32_t type) {
     return (physical == kInt32 && type == OXH_CSV_INT64) || (physical == kFloat && type == OXH_CSV_FLOAT64) ||
            (physical == kByteArray && type == OXH_CSV_STRING64);
 }
+// A list column's type word: OXH_PARQUET_LIST, with or without OXH_PARQUET_LIST64, on its element's word.
+constexpr uint32_t kListBits = OXH_PARQUET_LIST | OXH_PARQUET_LIST64;
+inline bool is_list_word(uint32_t type) { return (type & OXH_PARQUET_LIST) && !(type & ~(kListBits | 7u)); }
+inline uint32_t element_word(uint32_t type) { return type & ~kListBits; }
+inline bool list_element_read(int32_t physical) { return physical == kInt32 || physical == kInt64 || physical == kFloat || physical == kDouble; }
 
 struct Leaf {
     std::string name;
     int32_t physical = -1;
     bool required = false;
     std::string cause;  // not empty: why this reader cannot read the column
+    // A three-level LIST directly under the root: the leaf is its element, `name` and `required` are the list's.
+    // An entry of definition level d: d >= def_list, the row's list is not null; d >= def_slot, an element is there,
+    // null or not; d == max_def, it has a value. Max repetition level 1.
+    bool list = false;
+    uint32_t def_list = 0, def_slot = 0, max_def = 0;
 };
+// Bits of a level of at most `max` (the format's bit_width).
+inline uint32_t level_width(uint32_t max) {
+    uint32_t w = 0;
+    while (max >> w) ++w;
+    return w;
+}
 
 struct Chunk {
     uint64_t at = 0, bytes = 0, num_values = 0;
@@ -99,6 +115,7 @@ namespace detail {
 struct Element {
     std::string name;
     int32_t type = -1, repetition = 0, children = -1;
+    bool is_list = false;  // converted type LIST (3) or logical type LIST (the union's field 3)
 };
 
 inline std::string binary(Span& s) {
@@ -123,7 +140,16 @@ inline Element schema_element(Span& s) {
             e.name = binary(s);
         else if (id == 5 && type == kTI32)
             e.children = i32_field(s);
-        else if (type != kTTrue && type != kTFalse)
+        else if (id == 6 && type == kTI32)
+            e.is_list |= i32_field(s) == 3;
+        else if (id == 10 && type == kTStruct) {
+            int32_t l2 = 0, i2;
+            uint32_t t2;
+            while (next_field(s, l2, i2, t2)) {
+                e.is_list |= i2 == 3;
+                if (t2 != kTTrue && t2 != kTFalse) skip_value(s, t2, st);
+            }
+        } else if (type != kTTrue && type != kTFalse)
             skip_value(s, type, st);
     }
     return e;
@@ -170,10 +196,11 @@ inline ChunkMeta column_chunk(Span& s) {
 
 // The plan of the file whose footer is the `len` bytes at `meta`, themselves at `meta_at` of the nbytes of the file.
 // Refusals, in this order: a footer that is no FileMetaData; an encrypted footer; a schema without a root or whose
-// elements are not the root's children (a nested field, named); a repeated field; more than 2^40 rows; and per
+// elements are not the root's children (a nested field, named -- a three-level LIST of one leaf is a column, see
+// Leaf); a repeated field; more than 2^40 rows; and per
 // row group, in order: a column count that is not the schema's, a chunk without metadata or with encrypted
 // metadata, a codec other than UNCOMPRESSED -- with `inflate` (OXH_PARQUET_INFLATE) other than that and SNAPPY, with
-// `zstd` (OXH_PARQUET_INFLATE_ZSTD) and ZSTD -- (its number named), a chunk outside the file's pages, a num_values that is not the group's rows; then group rows that do
+// `zstd` (OXH_PARQUET_INFLATE_ZSTD) and ZSTD -- (its number named), a chunk outside the file's pages, a num_values that is not the group's rows (a list's chunk: less than them); then group rows that do
 // not sum to num_rows.
 inline Footer read_footer(const uint8_t* meta, uint64_t len, uint64_t meta_at, uint64_t nbytes, bool inflate = false, bool zstd = false) {
     using namespace detail;
@@ -230,20 +257,33 @@ inline Footer read_footer(const uint8_t* meta, uint64_t len, uint64_t meta_at, u
     if (s.bad || !has_schema || num_rows < 0) return f.error = "the footer is not a FileMetaData (Thrift compact) with a schema and num_rows", f;
     if (encrypted) return f.error = "an encrypted file (the footer names an encryption algorithm)", f;
     if (elements.empty() || elements[0].children < 0) return f.error = "the schema has no root group", f;
-    if ((uint64_t)elements[0].children != elements.size() - 1) {
-        for (size_t k = 1; k < elements.size(); ++k)
-            if (elements[k].children > 0) return f.error = "column '" + elements[k].name + "' is a nested field (a group of " + std::to_string(elements[k].children) + ")", f;
-        return f.error = "the schema's root names " + std::to_string(elements[0].children) + " children, the schema has " + std::to_string(elements.size() - 1), f;
-    }
-    for (size_t k = 1; k < elements.size(); ++k) {
+    // The root's children in order: a leaf, or the three elements of a LIST (group, REPEATED group, leaf). Any other
+    // group stops the file, whether or not the root's count fits.
+    uint64_t children = 0;
+    for (size_t k = 1; k < elements.size(); ++children) {
         const Element& e = elements[k];
-        if (e.children > 0) return f.error = "column '" + e.name + "' is a nested field (a group of " + std::to_string(e.children) + ")", f;
+        if (e.children > 0) {
+            const bool shaped = e.is_list && e.repetition != 2 && e.children == 1 && k + 2 < elements.size() && elements[k + 1].repetition == 2 &&
+                                elements[k + 1].children == 1 && elements[k + 2].children <= 0 && elements[k + 2].repetition != 2;
+            if (!shaped) return f.error = "column '" + e.name + "' is a nested field (a group of " + std::to_string(e.children) + ")", f;
+            const Element& el = elements[k + 2];
+            Leaf leaf;
+            leaf.name = e.name, leaf.physical = el.type, leaf.required = e.repetition == 0, leaf.list = true;
+            leaf.def_list = e.repetition == 1, leaf.def_slot = leaf.def_list + 1, leaf.max_def = leaf.def_slot + (el.repetition == 1);
+            if (!list_element_read(el.type)) leaf.cause = std::string("a list of ") + physical_name(el.type) + " is not read";
+            f.leaves.push_back(std::move(leaf));
+            k += 3;
+            continue;
+        }
         if (e.repetition == 2) return f.error = "column '" + e.name + "' is a repeated field (repetition levels are not read)", f;
         Leaf leaf;
         leaf.name = e.name, leaf.physical = e.type, leaf.required = e.repetition == 0;
         if (!native_type(e.type)) leaf.cause = std::string(physical_name(e.type)) + " is not read";
         f.leaves.push_back(std::move(leaf));
+        ++k;
     }
+    if ((uint64_t)elements[0].children != children)
+        return f.error = "the schema's root names " + std::to_string(elements[0].children) + " children, the schema has " + std::to_string(children), f;
     if ((uint64_t)num_rows > kMaxRows) return f.error = "more than 2^40 rows", f;
     f.nrows = (uint64_t)num_rows;
     const uint64_t ncols = f.leaves.size();
@@ -266,8 +306,10 @@ inline Footer read_footer(const uint8_t* meta, uint64_t len, uint64_t meta_at, u
             if (first < 4 || m.compressed < 0 || (uint64_t)first > meta_at || (uint64_t)m.compressed > meta_at - (uint64_t)first)
                 return f.error = col + ": its chunk (" + std::to_string(m.compressed) + " bytes at " + std::to_string(first) + ") is not inside the file's " +
                                  std::to_string(nbytes) + " bytes in front of the footer", f;
-            if (m.num_values != group_rows[g])
-                return f.error = col + ": num_values " + std::to_string(m.num_values) + " is not the group's " + std::to_string(group_rows[g]) + " rows", f;
+            // a list's chunk counts level entries: every row has one at least
+            if (f.leaves[c].list ? m.num_values < group_rows[g] : m.num_values != group_rows[g])
+                return f.error = col + ": num_values " + std::to_string(m.num_values) + (f.leaves[c].list ? " is less than the group's " : " is not the group's ") +
+                                 std::to_string(group_rows[g]) + " rows", f;
             f.chunks.push_back(Chunk{(uint64_t)first, (uint64_t)m.compressed, (uint64_t)m.num_values, (uint32_t)m.codec});
         }
         f.group_rows.push_back((uint64_t)group_rows[g]);
@@ -339,8 +381,22 @@ struct DictPage {
     uint32_t in_image, pad;
 };
 
+// A data page of a list column (parquet_lists.hip). Its num_values are level entries, not rows: `word0` is its first
+// word of the column's level words, 64 entries a word, and word0 * 64 its first cell of the column's index array.
+// V2: both streams' places are the header's. V1 (def_at == ~0u): the repetition stream's length led the body; the
+// definition stream's own 4-byte length is at `values_at`, and the level kernel reads it, bounded by body_size.
+struct ListPage {
+    uint64_t body, word0;
+    uint32_t num_values, body_size;
+    uint32_t rep_at, rep_bytes, def_at, def_bytes, values_at;
+    uint32_t encoding, dict, in_image;
+    uint32_t first;  // its chunk's first data page: its first entry must start a row
+    uint32_t group;  // its row group
+};
+
 struct ColumnPages {
     std::vector<DataPage> data;
+    std::vector<ListPage> lists;  // a list column's data pages; `data` is then empty
     std::vector<DictPage> dicts;
     uint64_t words = 0, entries = 0;
     bool indices = false;  // a page whose values are indices or RLE booleans
@@ -389,6 +445,99 @@ inline ColumnPages column_pages(const Footer& f, uint64_t c, const std::vector<C
     }
     if (row0 != f.nrows) return out.cause = "its pages hold " + std::to_string(row0) + " values, the file " + std::to_string(f.nrows) + " rows", out;
     return out;
+}
+
+// The same for a list column: its pages carry repetition levels, and nothing says where a row starts but they. A
+// page may begin in the middle of a row, except its chunk's first.
+inline ColumnPages list_pages(const Footer& f, uint64_t c, const std::vector<ChunkDesc>& chunks, const std::vector<uint32_t>& counts,
+                              const std::vector<PageRec>& recs) {
+    ColumnPages out;
+    const uint64_t ncols = f.leaves.size();
+    for (size_t g = 0; g < f.group_rows.size(); ++g) {
+        const size_t ch = g * ncols + c;
+        uint32_t dict = ~0u;
+        bool first = true;
+        for (uint32_t k = 0; k < counts[ch]; ++k) {
+            const PageRec& r = recs[chunks[ch].page0 + k];
+            const std::string where = "row group " + std::to_string(g) + ", page " + std::to_string(k);
+            if (r.values_at > r.body_size || r.def_at > r.values_at || r.def_bytes > r.values_at - r.def_at)
+                return out.cause = where + ": its levels do not fit its " + std::to_string(r.body_size) + " bytes", out;
+            if (r.kind == (uint32_t)kPageDict) {
+                if (k != 0) return out.cause = where + ": a dictionary page that is not its chunk's first page", out;
+                if (r.encoding != (uint32_t)kEncPlain && r.encoding != (uint32_t)kEncPlainDict)
+                    return out.cause = where + ": dictionary encoding " + std::to_string(r.encoding) + " is not read", out;
+                dict = (uint32_t)out.dicts.size();
+                out.dicts.push_back(DictPage{r.body, out.entries, r.body_size, r.num_values, r.flags & kPageInImage ? 1u : 0u, 0});
+                out.entries += r.num_values;
+                continue;
+            }
+            if (r.kind != (uint32_t)kPageData && r.kind != (uint32_t)kPageDataV2) return out.cause = where + ": page type " + std::to_string(r.kind) + " is not read", out;
+            if (r.flags & 2) return out.cause = where + ": levels that are not RLE", out;
+            const bool indexed = r.encoding == (uint32_t)kEncPlainDict || r.encoding == (uint32_t)kEncRleDict;
+            if (r.encoding != (uint32_t)kEncPlain && !indexed)
+                return out.cause = where + ": value encoding " + std::to_string(r.encoding) + " is not read (PLAIN, the dictionary encodings)", out;
+            if (indexed && dict == ~0u) return out.cause = where + ": dictionary-coded values without a dictionary page", out;
+            out.indices |= indexed;
+            const bool v1 = r.kind == (uint32_t)kPageData;  // the walk left the repetition stream where a flat page has its definition levels
+            out.lists.push_back(ListPage{r.body, out.words, r.num_values, r.body_size, v1 ? 4u : 0u, v1 ? r.def_bytes : r.def_at, v1 ? ~0u : r.def_at,
+                                         v1 ? 0u : r.def_bytes, r.values_at, r.encoding, indexed ? dict : ~0u, r.flags & kPageInImage ? 1u : 0u,
+                                         first ? 1u : 0u, (uint32_t)g});
+            out.words += ((uint64_t)r.num_values + 63) / 64, first = false;
+        }
+    }
+    return out;
+}
+
+// oxh_parquet_lists_*'s arguments (after the handle itself was checked): "" when they are well formed, else what is
+// wrong with them, in the header's order. All four output tables NULL: the call only measures.
+struct ListsArgs {
+    uint64_t nrows, ncols;  // of the handle
+    uint32_t nsel;
+    const uint32_t* col_idx;
+    const uint32_t* types;
+    const uint64_t* value_capacity;
+    void* const* values;
+    void* const* offsets;
+    uint8_t* const* validity;
+    uint8_t* const* child_validity;
+    uint64_t* value_bytes;
+    uint64_t* stats4;
+};
+inline uint32_t list_cell_bytes(uint32_t type) { return csv::is_narrow(element_word(type)) ? 4 : 8; }
+inline std::string lists_error(const ListsArgs& a) {
+    if (a.nsel && (!a.col_idx || !a.types)) return "col_idx or types is NULL";
+    for (uint32_t k = 0; k < a.nsel; ++k)
+        if (a.col_idx[k] >= a.ncols) return "selection " + std::to_string(k) + " names column " + std::to_string(a.col_idx[k]) + " of " + std::to_string(a.ncols);
+    for (uint32_t k = 0; k < a.nsel; ++k) {
+        const uint32_t e = element_word(a.types[k]);
+        if (!is_list_word(a.types[k]) || (e != OXH_CSV_INT64 && e != OXH_CSV_FLOAT64 && e != OXH_CSV_INT32 && e != OXH_CSV_FLOAT32))
+            return "selection " + std::to_string(k) + " has type " + std::to_string(a.types[k]) + ", which is not OXH_PARQUET_LIST on a fixed-width element's word";
+    }
+    if (a.nsel && (!a.value_bytes || !a.stats4)) return "value_bytes or stats4 is NULL";
+    const bool measure = !a.values && !a.offsets && !a.validity && !a.child_validity;
+    if (measure || !a.nsel) return "";
+    if (!a.values || !a.offsets || !a.validity || !a.child_validity) return "only some of values, offsets, validity and child_validity are NULL";
+    if (!a.value_capacity) return "value_capacity is NULL with outputs";
+    if (!a.nrows) return "";
+    for (uint32_t k = 0; k < a.nsel; ++k) {
+        const std::string col = "selection " + std::to_string(k);
+        if (!a.validity[k]) return col + " has no validity buffer";
+        if (!a.offsets[k]) return col + " has no offsets";
+        if ((uintptr_t)a.offsets[k] & (a.types[k] & OXH_PARQUET_LIST64 ? 7 : 3)) return col + ": offsets is not aligned to its entries";
+        if (a.value_capacity[k] && (!a.values[k] || !a.child_validity[k])) return col + " has a capacity but no values or no child_validity";
+        if ((uintptr_t)a.values[k] & (list_cell_bytes(a.types[k]) - 1)) return col + ": values is not aligned to its cells";
+    }
+    return "";
+}
+
+// "" when the pages' row starts (one count per page of cp.lists) are every row group's rows.
+inline std::string list_rows_error(const Footer& f, const ColumnPages& cp, const uint32_t* starts) {
+    std::vector<uint64_t> rows(f.group_rows.size(), 0);
+    for (size_t p = 0; p < cp.lists.size(); ++p) rows[cp.lists[p].group] += starts[p];
+    for (size_t g = 0; g < rows.size(); ++g)
+        if (rows[g] != f.group_rows[g])
+            return "row group " + std::to_string(g) + ": its pages start " + std::to_string(rows[g]) + " rows, the group has " + std::to_string(f.group_rows[g]);
+    return "";
 }
 
 }  // namespace oxh::pqr

@@ -2705,6 +2705,31 @@ class ParquetColumnType(NamedTuple):
     readable: bool
 
 
+class ListColumn(NamedTuple):
+    """One list column of `ParquetFile.lists`, Arrow's List / LargeList: values (the elements, a null's 0), offsets
+    (nrows + 1, int32 or int64, counting elements), validity (the lists' bitmap, uint8) and child_validity (the
+    elements' bitmap)."""
+    values: Any
+    offsets: Any
+    validity: Any
+    child_validity: Any
+
+
+class ParquetListStats(NamedTuple):
+    """stats4 of one selected column of oxh_parquet_lists_*."""
+    null_lists: int
+    null_elements: int
+    pages: int
+    elements: int
+
+
+for _word, _name in list(PARQUET_TYPE_NAMES.items()):   # polars' names of the list words: List[Int64], LargeList[Int64], ...
+    if _word in (_capi.OXH_CSV_INT64, _capi.OXH_CSV_FLOAT64, _capi.OXH_CSV_INT32, _capi.OXH_CSV_FLOAT32):
+        PARQUET_TYPE_NAMES[_word | _capi.OXH_PARQUET_LIST] = f"List[{_name}]"
+        PARQUET_TYPE_NAMES[_word | _capi.OXH_PARQUET_LIST | _capi.OXH_PARQUET_LIST64] = f"LargeList[{_name}]"
+_PARQUET_TYPE_OF = {name: code for code, name in PARQUET_TYPE_NAMES.items()}
+
+
 def _parquet_type(t) -> int:
     if isinstance(t, str):
         if t not in _PARQUET_TYPE_OF:
@@ -2719,7 +2744,8 @@ class ParquetFile:
     copy), or with device=True a uint8 torch tensor on the device, which the object keeps alive. The rules are
     include/oxen_hash.h's "Parquet: the file's bytes": uncompressed and, with inflate (OXH_PARQUET_INFLATE and
     OXH_PARQUET_INFLATE_ZSTD, the default), SNAPPY and ZSTD files with a flat schema, the physical bits. The handle holds the inflated size of every
-    compressed page on the device until `close`; `stats.pages_inflated` counts them."""
+    compressed page on the device until `close`; `stats.pages_inflated` counts them. A column that is a three-level
+    LIST of numbers reports OXH_PARQUET_LIST on its element's word in `types` and is read by `lists`, not `columns`."""
 
     def __init__(self, data, ctx: Optional[_capi.Context] = None, device: bool = False, stream=None, inflate: bool = True):
         self.device = device
@@ -2851,6 +2877,77 @@ class ParquetFile:
         return (out, stats) if with_stats else out
 
 
+    def _lists_call(self, nsel, col_idx, type_words, capacity, values, offsets, validity, child_validity):
+        value_bytes, stats = np.zeros(max(nsel, 1), dtype=np.uint64), np.zeros(4 * max(nsel, 1), dtype=np.uint64)
+        L = _capi.lib()
+        args = (self.handle, nsel, col_idx, type_words, None if capacity is None else capacity.ctypes.data_as(_capi._u64p), values, offsets,
+                validity, child_validity, value_bytes.ctypes.data_as(_capi._u64p), stats.ctypes.data_as(_capi._u64p))
+        if self.device:
+            from .device import _stream
+
+            _capi.check(L.oxh_parquet_lists_device(*args, _stream(self.stream)), "oxh_parquet_lists_device")
+        else:
+            _capi.check(L.oxh_parquet_lists_host(*args), "oxh_parquet_lists_host")
+        return ([int(x) for x in value_bytes[:nsel]], [ParquetListStats(*(int(x) for x in stats[4 * k:4 * k + 4])) for k in range(nsel)])
+
+    def lists(self, cols, types=None, with_stats: bool = False):
+        """The selected list columns (indices) as `ListColumn`s: numpy arrays in the host form, torch tensors on the
+        device in the device form. types: per column OXH_PARQUET_LIST on the element's word (with OXH_PARQUET_LIST64
+        for int64 offsets) or a name such as "List[Int64]" / "LargeList[Float64]"; None: the native words. Measures
+        first (the element counts size the buffers), then fills."""
+        native = self.types()
+        types = [native[int(c)].type for c in cols] if types is None else types
+        cols, types, col_idx, type_words = self._selection(cols, types)
+        nsel, n = len(cols), self.stats.rows
+        sizes, _ = self._lists_call(nsel, col_idx, type_words, None, None, None, None, None)
+        if self.device:
+            import torch
+
+            dev = self.data.device
+            make = lambda count, dtype: torch.empty(count, dtype=getattr(torch, dtype), device=dev)   # noqa: E731
+            ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None                    # noqa: E731
+        else:
+            make = lambda count, dtype: np.zeros(count, dtype=dtype)                                 # noqa: E731
+            ptr = lambda a: a.ctypes.data if a is not None and a.size else None                      # noqa: E731
+        fixed = {_capi.OXH_CSV_INT64: ("int64", 8), _capi.OXH_CSV_FLOAT64: ("float64", 8), _capi.OXH_CSV_INT32: ("int32", 4),
+                 _capi.OXH_CSV_FLOAT32: ("float32", 4)}
+        out = []
+        for k, t in enumerate(types):
+            dtype, width = fixed[t & 7]
+            count = sizes[k] // width
+            offsets = make(n + 1, "int64" if t & _capi.OXH_PARQUET_LIST64 else "int32")
+            if n == 0:
+                offsets[:] = 0
+            out.append(ListColumn(make(count, dtype), offsets, make((n + 7) // 8, "uint8"), make((count + 7) // 8, "uint8")))
+        m = max(nsel, 1)
+        tables = [(ctypes.c_void_p * m)(*[ptr(getattr(c, field)) for c in out]) for field in ("values", "offsets", "validity", "child_validity")]
+        _, stats = self._lists_call(nsel, col_idx, type_words, np.array(sizes + [0] * (m - nsel), dtype=np.uint64), *tables)
+        return (out, stats) if with_stats else out
+
+
+def embedding_from_list(col: "ListColumn", dim: Optional[int] = None) -> Embedding:
+    """The `Embedding` over a float32 `ListColumn`'s own buffers (nothing is copied; host or device as the column
+    is): layout OXH_EMB_LIST32 / OXH_EMB_LIST64 by the offsets' width, or OXH_EMB_FIXED when every row is valid and
+    has `dim` elements (dim None: the first row's length). A null element is refused: the embedding entries have no
+    element validity."""
+    is_np = isinstance(col.values, np.ndarray)
+    if str(col.values.dtype) not in ("float32", "torch.float32"):
+        raise _capi.OxenError(f"an embedding holds float32 values, not {col.values.dtype} (the reference's ExpectedF32)", _capi.OXH_ERR_INVALID)
+    host = lambda a: a if is_np else a.cpu().numpy()   # noqa: E731  the checks read the small buffers, and the elements' bitmap
+    offsets, n, count = host(col.offsets).astype(np.int64), len(col.offsets) - 1, len(col.values)
+    if count and not np.unpackbits(host(col.child_validity), bitorder="little")[:count].all():
+        raise _capi.OxenError("null elements inside a vector are not supported", _capi.OXH_ERR_INVALID)
+    present = np.unpackbits(host(col.validity), bitorder="little")[:n].astype(bool)
+    lengths = np.diff(offsets)
+    d = int(dim) if dim is not None else (int(lengths[present][0]) if present.any() else 1)
+    if d < 1:
+        raise _capi.OxenError("an embedding has at least one element per row", _capi.OXH_ERR_INVALID)
+    if present.all() and (lengths == d).all():
+        return Embedding(_capi.OXH_EMB_FIXED, d, n, col.values, None, None, 0)
+    wide = str(col.offsets.dtype) in ("int64", "torch.int64")
+    return Embedding(_capi.OXH_EMB_LIST64 if wide else _capi.OXH_EMB_LIST32, d, n, col.values, col.offsets, col.validity, 0)
+
+
 def _parquet_frame(f: ParquetFile, schema, columns) -> dict:
     names = f.names
     if columns is None:
@@ -2867,7 +2964,13 @@ def _parquet_frame(f: ParquetFile, schema, columns) -> dict:
         given = None if schema is None else (schema.get(names[c]) if isinstance(schema, Mapping) else schema[c])
         # a column this reader cannot read has no native word: any known one lets the library name the cause
         types.append((native[c].type or _capi.OXH_CSV_INT64) if given is None else _parquet_type(given))
-    return dict(zip([names[c] for c in picked], f.columns(picked, types)))
+    # the list columns go through their own entry, the flat ones through theirs; the frame keeps the picked order
+    listed = [k for k, c in enumerate(picked) if native[c].type & _capi.OXH_PARQUET_LIST]
+    flat = [k for k in range(len(picked)) if k not in listed]
+    got = dict(zip(flat, f.columns([picked[k] for k in flat], [types[k] for k in flat])))
+    if listed:
+        got.update(zip(listed, f.lists([picked[k] for k in listed], [types[k] for k in listed])))
+    return {names[c]: got[k] for k, c in enumerate(picked)}
 
 
 def read_parquet(path_or_bytes, schema=None, columns=None, ctx: Optional[_capi.Context] = None, inflate: bool = True) -> dict:
@@ -2877,7 +2980,9 @@ def read_parquet(path_or_bytes, schema=None, columns=None, ctx: Optional[_capi.C
     OXH_CSV_* words) widens an INT32 column to "Int64", a FLOAT column to "Float64", or picks "LargeString"; a column
     without one is read as its physical type (`ParquetFile.types`). SNAPPY pages are inflated on the device at open
     (inflate=False refuses them as any other codec); a file of another codec raises with the codec's number: that one
-    goes to the CPU. `read_df` still refuses `.parquet`: this is the entry."""
+    goes to the CPU. A list column (`list<...>` / `fixed_size_list<...>` of numbers) comes back as a `ListColumn`
+    beside the flat `Column`s; its schema word is "List[...]" or, for int64 offsets, "LargeList[...]". `read_df` still
+    refuses `.parquet`: this is the entry."""
     data, _ = _csv_bytes(path_or_bytes)
     with ParquetFile(data, ctx=ctx, inflate=inflate) as f:
         return _parquet_frame(f, schema, columns)
