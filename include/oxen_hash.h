@@ -1233,9 +1233,34 @@ int oxh_write_json_host(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const uint
  *     8-byte words per row group, and per row 4 bytes of table places, 8 of the first occurrences' scan and 4 to 6
  *     of dense indices, which hold the first-occurrence flags before the plan (12 more for a string column's entry
  *     lengths and their scan).
+ *   List columns (oxh_write_parquet_lists_*). A column whose type word is OXH_PARQUET_LIST | the element's word
+ *     (OXH_CSV_INT64, OXH_CSV_FLOAT64, OXH_CSV_INT32 or OXH_CSV_FLOAT32; OXH_PARQUET_LIST64 beside it for int64
+ *     offsets: the words oxh_parquet_types and oxh_parquet_lists_* report) is an Arrow List / LargeList of numbers:
+ *     values[c] the elements, offsets[c] the nrows + 1 list offsets (aligned to their width; offsets[0] need not be
+ *     0), validity[c] and bit_offsets[2 c + 1] the lists' bitmap, child_validity[c] and child_bit_offsets[c] the
+ *     elements' bitmap (NULL: no null element). kinds[c] must be the element's width, OXH_COL_FIXED4 or
+ *     OXH_COL_FIXED8; anything else is the "kind does not fit its type" error. The schema is the standard three
+ *     levels directly under the root, OPTIONAL group <name> (LIST) { REPEATED group list { OPTIONAL <T> element } },
+ *     converted type LIST and logical type LIST, path_in_schema [name, "list", "element"], physical type INT32,
+ *     INT64, FLOAT or DOUBLE, max repetition level 1, max definition level 3. Level entries: a null list is one
+ *     entry (rep 0, def 0), an empty list one entry (rep 0, def 1), a list of n elements n entries, rep 0 then 1s,
+ *     def 2 for a null element and 3 otherwise. Elements under a null list are never written or read, also when its
+ *     offsets span some. Row groups and page cuts are as above with both level streams and the values as a page's
+ *     bytes, so every page begins with a row; a page above INT32_MAX bytes or entries is refused before anything is
+ *     written. num_values of a page and of a chunk counts entries, not rows. A page body is a 4-byte length and the
+ *     repetition stream at width 1, a 4-byte length and the definition stream at width 2, then the PLAIN values of
+ *     the entries with def 3, 4 or 8 bytes each. Each stream is one run, its form decided by counts alone:
+ *     repetition is one RLE run of 0 (varint(n << 1), the byte 0) when the page's entries equal its rows, else one
+ *     bit-packed run; definition is one RLE run of 3 when the page's values equal its entries, else one bit-packed
+ *     run (varint((ceil(n / 8) << 1) | 1), LSB first, pad entries 0). A list chunk's encodings are [PLAIN, RLE] and
+ *     it has no statistics; stats4[3] counts null lists beside the flat columns' null cells, null elements are not
+ *     counted. OXH_PARQUET_SNAPPY applies unchanged (a list page's body is one more block); with
+ *     OXH_PARQUET_DICTIONARY a list chunk stays PLAIN. Working memory, per list column: 12 bytes a row and, per level
+ *     entry, half a byte of level bits and 20 bytes per 64 entries of value counts and ranks, in two blocks the call
+ *     allocates; the call synchronises once more, because the entry totals size the second.
  *   Stated and not built: zstd; RLE runs in the index stream, a fallback in the middle of a chunk, DataPage V2,
- *     dictionaries for booleans and choosing the flag automatically; nested and narrower types; the `arrow` arm of
- *     `write_df`.
+ *     dictionaries for booleans and choosing the flag automatically; flat INT32 and FLOAT columns, lists of strings,
+ *     booleans or lists, statistics for list chunks; the `arrow` arm of `write_df`.
  *
  * Inputs: as oxh_write_json_* (names and name_offsets are always read; host memory in both forms), then
  * rows_per_group, page_bytes and flags (0 or any of OXH_PARQUET_SNAPPY and OXH_PARQUET_DICTIONARY; anything outside 2 | 4
@@ -1255,7 +1280,18 @@ int oxh_write_json_host(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const uint
  * measure and before anything is written: a pair of offsets that is negative or decreases, a byte column with bytes
  * and no values, a string cell of 2^32 bytes or more, a page above INT32_MAX bytes, more than 32 767 row groups (a RowGroup's
  * ordinal is an int16); then a capacity below the need.
- * A failed allocation is OXH_ERR_NOMEM with the outputs untouched. */
+ * A failed allocation is OXH_ERR_NOMEM with the outputs untouched.
+ *
+ * oxh_write_parquet_lists_* take the same parameters in the same order and, behind them, child_validity (one pointer
+ * per column, device memory in _device as d_validity is; the table or an entry NULL: no null element) and
+ * child_bit_offsets (one word per column: the bit of element 0; NULL: all 0). oxh_write_parquet_* forward to them
+ * with both NULL; without a list column the file is byte for byte the same. Their argument errors take these places
+ * in the order above: a list word on an element that is not int64, float64, int32 or float32, where the unknown type
+ * stands; a list column whose kind is not its element's width, with the kinds; with rows, per column, where the byte
+ * column's checks stand: a list column without offsets, offsets not aligned to their width, and in the host form a
+ * list that is not null whose pair of offsets is negative or decreases, then an element column without values while
+ * it has elements. In the device form those last two, and a list of more than INT32_MAX elements, are found after
+ * the measure, with the byte columns' pairs. */
 #define OXH_PARQUET_SNAPPY 2u /* flags of oxh_write_parquet_*: SNAPPY pages */
 #define OXH_PARQUET_DICTIONARY 4u /* flags of oxh_write_parquet_*: RLE_DICTIONARY chunks where the data allow */
 int oxh_write_parquet_device(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const uint32_t* types, const uint32_t* kinds,
@@ -1268,6 +1304,18 @@ int oxh_write_parquet_host(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const u
                            const uint64_t* bit_offsets, const uint8_t* names, const uint64_t* name_offsets,
                            uint64_t rows_per_group, uint64_t page_bytes, uint32_t flags, uint8_t* out, uint64_t capacity,
                            uint64_t* out_bytes, uint64_t* stats4);
+int oxh_write_parquet_lists_device(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const uint32_t* types, const uint32_t* kinds,
+                                   const void* const* d_values, const void* const* d_offsets, const uint8_t* const* d_validity,
+                                   const uint64_t* bit_offsets, const uint8_t* names, const uint64_t* name_offsets,
+                                   uint64_t rows_per_group, uint64_t page_bytes, uint32_t flags, uint8_t* d_out, uint64_t capacity,
+                                   uint64_t* out_bytes, uint64_t* stats4, void* stream, const uint8_t* const* d_child_validity,
+                                   const uint64_t* child_bit_offsets);
+int oxh_write_parquet_lists_host(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const uint32_t* types, const uint32_t* kinds,
+                                 const void* const* values, const void* const* offsets, const uint8_t* const* validity,
+                                 const uint64_t* bit_offsets, const uint8_t* names, const uint64_t* name_offsets,
+                                 uint64_t rows_per_group, uint64_t page_bytes, uint32_t flags, uint8_t* out, uint64_t capacity,
+                                 uint64_t* out_bytes, uint64_t* stats4, const uint8_t* const* child_validity,
+                                 const uint64_t* child_bit_offsets);
 
 /* ---------------------------------------------------------------- JSON Lines: record index and typed Arrow columns
  * The reference has a JSON Lines arm in every reader: read_df_jsonl (core/df/tabular.rs:73-82), scan_df_jsonl

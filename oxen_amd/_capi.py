@@ -234,6 +234,12 @@ SIGNATURES = {
     "oxh_write_parquet_host": (_int, [_vp, _u64, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_vp),
                                       ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u64p, _vp, _u64p, _u64, _u64, _u32, _vp, _u64,
                                       _u64p, _u64p]),
+    "oxh_write_parquet_lists_device": (_int, [_vp, _u64, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_vp),
+                                              ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u64p, _vp, _u64p, _u64, _u64, _u32, _vp, _u64,
+                                              _u64p, _u64p, _vp, ctypes.POINTER(_vp), _u64p]),
+    "oxh_write_parquet_lists_host": (_int, [_vp, _u64, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_vp),
+                                            ctypes.POINTER(_vp), ctypes.POINTER(_vp), _u64p, _vp, _u64p, _u64, _u64, _u32, _vp, _u64,
+                                            _u64p, _u64p, ctypes.POINTER(_vp), _u64p]),
     "oxh_jsonl_open_device": (_int, [_vp, _vp, _u64, _u64, _u32, ctypes.POINTER(_vp), _u64p, _vp]),
     "oxh_jsonl_open_host": (_int, [_vp, _vp, _u64, _u64, _u32, ctypes.POINTER(_vp), _u64p]),
     "oxh_jsonl_close": (_int, [_vp]),

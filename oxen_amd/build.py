@@ -18,7 +18,7 @@ SOURCES = [os.path.join(CSRC, f) for f in (
     "xxh3_kernels.hip", "capi_dispatch.hip", "capi_context.hip", "staging.hip", "large_items.hip", "xxh3_stream.hip",
     "engine.hip", "modified.hip", "publish.hip", "fastcdc.hip", "fastcdc_scan.hip", "fastcdc_walk.hip", "dedup_index.hip",
     "row_hash.hip", "keyed_diff.hip", "take_columns.hip", "concat_columns.hip", "sort_rows.hip", "group_rows.hip", "filter_rows.hip",
-    "embedding.hip", "csv_read.hip", "csv_write.hip", "json_write.hip", "jsonl_read.hip", "parquet_write.hip", "parquet_dict.hip", "parquet_read.hip", "parquet_lists.hip", "snappy_inflate.hip", "snappy_compress.hip", "zstd_inflate.hip", "reader_pool.cpp", "comm.cpp", "fastcdc_host.cpp")]
+    "embedding.hip", "csv_read.hip", "csv_write.hip", "json_write.hip", "jsonl_read.hip", "parquet_write.hip", "parquet_dict.hip", "parquet_write_lists.hip", "parquet_read.hip", "parquet_lists.hip", "snappy_inflate.hip", "snappy_compress.hip", "zstd_inflate.hip", "reader_pool.cpp", "comm.cpp", "fastcdc_host.cpp")]
 DEPS = SOURCES + [os.path.join(CSRC, h) for h in ("capi_internal.hpp", "xxh3_device.hpp", "fastcdc_gear.h", "fastcdc_plan.hpp",
                                                  "fastcdc_device.hpp", "pool.hpp", "scratch.hpp", "reader_pool.hpp",
                                                  "env.hpp", "keyed_diff_host.hpp", "columns.hpp",
@@ -97,6 +97,8 @@ PARQUET_DICT_TEST_SRC = os.path.join(ROOT, "tests", "native", "parquet_dict_host
 PARQUET_DICT_TEST = os.path.join(ROOT, "tests", "native", "parquet_dict_host_test")  # tests only: the Parquet writer's plan with dictionary chunks
 PARQUET_LISTS_TEST_SRC = os.path.join(ROOT, "tests", "native", "parquet_lists_host_test.cpp")
 PARQUET_LISTS_TEST = os.path.join(ROOT, "tests", "native", "parquet_lists_host_test")  # tests only: the Parquet reader's plan of list columns
+PARQUET_WRITE_LISTS_TEST_SRC = os.path.join(ROOT, "tests", "native", "parquet_write_lists_host_test.cpp")
+PARQUET_WRITE_LISTS_TEST = os.path.join(ROOT, "tests", "native", "parquet_write_lists_host_test")  # tests only: the Parquet writer's plan of list columns
 ZSTD_TABLES_TEST_SRC =os.path.join(ROOT, "tests", "native", "zstd_tables_test.cpp")
 ZSTD_TABLES_TEST = os.path.join(ROOT, "tests", "native", "zstd_tables_test")  # tests only: the Zstandard inflate's bit reader and table builders
 FAKE_RCCL_SRC = os.path.join(ROOT, "tests", "native", "fake_rccl.cpp")
@@ -128,7 +130,8 @@ def build_host(force: bool = False, verbose: bool = False) -> str:
     (tests/native/parquet_read_host_test.cpp) with what OXH_PARQUET_INFLATE adds to it
     (tests/native/parquet_inflate_host_test.cpp), and of the Parquet writer's plan with stored (SNAPPY) page sizes
     (tests/native/parquet_snappy_host_test.cpp) and with dictionary chunks (tests/native/parquet_dict_host_test.cpp), of the Parquet reader's plan of list columns
-    (tests/native/parquet_lists_host_test.cpp), and of the Zstandard inflate's table builders
+    (tests/native/parquet_lists_host_test.cpp), of the Parquet writer's plan of list columns and their level heads
+    (tests/native/parquet_write_lists_host_test.cpp), and of the Zstandard inflate's table builders
     (tests/native/zstd_tables_test.cpp)."""
     hdr = os.path.join(ROOT, "include", "oxen_hash.h")
     steps = [
@@ -197,6 +200,8 @@ def build_host(force: bool = False, verbose: bool = False) -> str:
         (PARQUET_LISTS_TEST, [PARQUET_LISTS_TEST_SRC, os.path.join(CSRC, "parquet_host.hpp"), os.path.join(CSRC, "parquet_read_host.hpp"),
                               os.path.join(CSRC, "parquet_bits.hpp"), os.path.join(CSRC, "csv_host.hpp"), os.path.join(CSRC, "columns.hpp"), hdr],
          ["g++", "-std=c++17", "-O2", "-Wall", "-o", PARQUET_LISTS_TEST + ".tmp", PARQUET_LISTS_TEST_SRC]),
+        (PARQUET_WRITE_LISTS_TEST, [PARQUET_WRITE_LISTS_TEST_SRC, os.path.join(CSRC, "parquet_host.hpp"), os.path.join(CSRC, "columns.hpp"), hdr],
+         ["g++", "-std=c++17", "-O2", "-Wall", "-o", PARQUET_WRITE_LISTS_TEST + ".tmp", PARQUET_WRITE_LISTS_TEST_SRC]),
         (ZSTD_TABLES_TEST, [ZSTD_TABLES_TEST_SRC, os.path.join(CSRC, "zstd_tables.hpp"), os.path.join(CSRC, "parquet_read_host.hpp"),
                             os.path.join(CSRC, "parquet_bits.hpp"), os.path.join(CSRC, "csv_host.hpp"), os.path.join(CSRC, "columns.hpp"), hdr],
          ["g++", "-std=c++17", "-O2", "-Wall", "-o", ZSTD_TABLES_TEST + ".tmp", ZSTD_TABLES_TEST_SRC]),

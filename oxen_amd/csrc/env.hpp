@@ -137,7 +137,8 @@ inline bool split_reads() {
 // ---------------------------------------------------------------- diagnostics and test hooks, not for callers
 // OXH_TRACE (set = on): per-call stage times on stderr (host-side wall clock). Read here on every call:
 // the host-buffer, engine and large-item calls and a publisher read it per call, the FastCDC entries
-// latch it at their first call.
+// latch it at their first call. The Parquet writer's list steps (parquet_write_lists.hip) read it per call and time
+// themselves by events.
 inline bool trace() { return text("OXH_TRACE") != nullptr; }
 // OXH_DEBUG_STEPS (set = on): one stderr line per runtime step (locating stalls without a debugger).
 // Read once, when the library is loaded (capi_internal.hpp g_steps).

@@ -442,7 +442,7 @@ void PqDict::layout(uint64_t nrows, uint32_t ncols, const uint32_t* types, uint6
     group_rows = rows_per_group, ngroups = (nrows + group_rows - 1) / group_rows;
     ncand = nstr = 0;
     for (uint32_t c = 0; c < ncols; ++c)
-        if (types[c] != OXH_CSV_BOOL) ++ncand, nstr += pq::is_string(types[c]);
+        if (pq::dict_candidate(types[c])) ++ncand, nstr += pq::is_string(types[c]);
     const uint64_t chunk_rows = std::min(group_rows, nrows), ntiles = (nrows + pq::kTileRows - 1) / pq::kTileRows;
     slots = 64;
     while (slots < 2 * pq::kDictMaxEntries && slots < 2 * chunk_rows) slots *= 2;
@@ -490,7 +490,7 @@ int PqDict::build(const PqArgs& args, const uint32_t* types, uint64_t rows_per_g
     if (!ncand) return OXH_OK;
     cand.assign(2 * (size_t)ncand, kPqdNone);
     for (uint32_t c = 0, k = 0, ks = 0; c < args.ncols; ++c) {
-        if (types[c] == OXH_CSV_BOOL) continue;
+        if (!pq::dict_candidate(types[c])) continue;
         cand[k] = c;
         if (pq::is_string(types[c])) cand[ncand + k] = ks++;
         ++k;

@@ -2,7 +2,9 @@
 // checks that need no device, in the header's order; the Thrift compact encoder; the planner that turns the measure
 // kernel's tile table into pages, row groups, every PageHeader's bytes, every page's place in the file and the
 // footer; the folding of the tiles' min / max partials into a column chunk's statistics; and for OXH_PARQUET_DICTIONARY
-// the limits, the fallback decision, the index width and the index stream's bytes. The format is stated in
+// the limits, the fallback decision, the index width and the index stream's bytes; and for the list columns of
+// oxh_write_parquet_lists_* (parquet_write_lists.hip) their argument checks, the level streams' heads, their pages cut
+// by level entries and their three schema elements. The format is stated in
 // include/oxen_hash.h "Parquet". Plain C++ with no HIP in it, so that a stand-alone program can call it
 // (tests/native/parquet_host_test.cpp, which is also what a sanitizer build runs).
 #pragma once
@@ -56,6 +58,13 @@ struct Page {
     // page itself (rows == 0, the chunk's first page): dict_page names it, nvalid = its entries, values_bytes its body.
     uint32_t dict_width, dict_page;
     uint64_t dense_at;
+    // A list column's page (parquet_write_lists.hip). Its head is the PageHeader, the repetition stream's length and
+    // run header; the definition stream's length and run header, def_head_len bytes, lie behind it in the blob and
+    // behind the repetition bits in the file; level_bytes = the repetition bits + def_head_len + the definition bits;
+    // nvalid = its values (the entries of definition level 3). entry0, value0: the page's first entry in the
+    // column's entry space, and the values in front of it.
+    uint64_t entry0, value0;
+    uint32_t entries, def_head_len;
 };
 
 // What the rank step leaves per (row group, column), entry group * ncols + column.
@@ -158,15 +167,63 @@ struct Args {
     uint64_t capacity;
     uint64_t* out_bytes;
     uint64_t* stats4;
+    const uint8_t* const* child_validity = nullptr;  // oxh_write_parquet_lists_*: the elements' bitmaps; NULL: none
+    const uint64_t* child_bit_offsets = nullptr;     // per column the bit of element 0 in its child_validity
 };
+
+// A list column's type word: OXH_PARQUET_LIST on the element's word, with OXH_PARQUET_LIST64 for int64 offsets.
+OXH_PQ_BOTH inline bool is_list(uint32_t t) { return (t & OXH_PARQUET_LIST) != 0; }
+inline uint32_t list_element(uint32_t t) { return t & ~(uint32_t)(OXH_PARQUET_LIST | OXH_PARQUET_LIST64); }
+inline bool list_element_known(uint32_t e) { return e == OXH_CSV_INT64 || e == OXH_CSV_FLOAT64 || e == OXH_CSV_INT32 || e == OXH_CSV_FLOAT32; }
+inline uint32_t element_width(uint32_t t) { return list_element(t) == OXH_CSV_INT32 || list_element(t) == OXH_CSV_FLOAT32 ? 4 : 8; }
+inline uint32_t list_offset_width(uint32_t t) { return t & OXH_PARQUET_LIST64 ? 8 : 4; }
+inline bool dict_candidate(uint32_t t) { return !is_list(t) && t != OXH_CSV_BOOL; }  // OXH_PARQUET_DICTIONARY: a list chunk stays PLAIN
 
 inline bool known_type(uint32_t t) { return t >= OXH_CSV_INT64 && t <= OXH_CSV_STRING64; }
 inline bool is_string(uint32_t t) { return t == OXH_CSV_STRING || t == OXH_CSV_STRING64; }
 inline uint32_t kind_of(uint32_t type) {
+    if (is_list(type)) return element_width(type) == 4 ? OXH_COL_FIXED4 : OXH_COL_FIXED8;  // what its values table holds
     return type == OXH_CSV_BOOL ? OXH_COL_BOOL : type == OXH_CSV_STRING ? OXH_COL_BYTES32 : type == OXH_CSV_STRING64 ? OXH_COL_BYTES64 : OXH_COL_FIXED8;
 }
 inline uint64_t group_rows_of(uint64_t rows_per_group) { return rows_per_group ? rows_per_group : kDefaultGroupRows; }
 inline uint64_t page_bytes_of(uint64_t page_bytes) { return page_bytes ? page_bytes : kDefaultPageBytes; }
+
+inline bool bit_at(const uint8_t* p, uint64_t bit) { return (p[bit >> 3] >> (bit & 7)) & 1; }
+
+// Host form: the elements [lo, hi) that the lists which are not null name; lo == hi when they name none. `bad_row`:
+// the first list that is not null whose pair of offsets is negative or decreases (nrows: none).
+struct ListSpan {
+    uint64_t lo = 0, hi = 0, bad_row = 0;
+};
+inline ListSpan list_span(const Args& a, uint32_t c) {
+    ListSpan s;
+    s.bad_row = a.nrows;
+    const bool wide = (a.types[c] & OXH_PARQUET_LIST64) != 0;
+    bool any = false;
+    for (uint64_t r = 0; r < a.nrows; ++r) {
+        if (a.validity[c] && !bit_at(a.validity[c], a.bit_offsets[2 * c + 1] + r)) continue;
+        const int64_t b = wide ? ((const int64_t*)a.offsets[c])[r] : ((const int32_t*)a.offsets[c])[r];
+        const int64_t e = wide ? ((const int64_t*)a.offsets[c])[r + 1] : ((const int32_t*)a.offsets[c])[r + 1];
+        if (b < 0 || e < b) return s.bad_row = r, s;
+        if (e == b) continue;
+        s.lo = any ? std::min<uint64_t>(s.lo, (uint64_t)b) : (uint64_t)b, s.hi = any ? std::max<uint64_t>(s.hi, (uint64_t)e) : (uint64_t)e;
+        any = true;
+    }
+    return s;
+}
+
+// What is wrong with a list column of nrows > 0 rows: no offsets; offsets not aligned to their width; host (the offsets
+// can be read): a list that is not null with a negative or decreasing pair, elements without values.
+inline std::string list_error(const std::string& col, const Args& a, uint32_t c, bool host) {
+    if (!a.offsets[c]) return col + " is a list column without offsets";
+    const uint32_t ow = list_offset_width(a.types[c]);
+    if ((uintptr_t)a.offsets[c] % ow) return col + ": list offsets are not aligned to " + std::to_string(ow) + " bytes";
+    if (!host) return "";  // the offsets are on the device: the kernels check them
+    const ListSpan s = list_span(a, c);
+    if (s.bad_row < a.nrows) return col + ": list offsets decrease or are negative at row " + std::to_string(s.bad_row);
+    if (!a.values[c] && s.hi > s.lo) return col + " has elements but no values";
+    return "";
+}
 
 // "" when the arguments are well formed, else what is wrong with them, in the header's order.
 inline std::string write_error(const Args& a, bool host) {
@@ -175,8 +232,11 @@ inline std::string write_error(const Args& a, bool host) {
     if (a.ncols == 0) return "ncols is 0";
     if (a.flags & ~(kFlagSnappy | kFlagDictionary)) return "unknown flags";
     if (a.rows_per_group % kTileRows) return "rows_per_group is not a multiple of 1024";
-    for (uint32_t c = 0; c < a.ncols; ++c)
-        if (!known_type(a.types[c])) return "column " + std::to_string(c) + " has unknown type " + std::to_string(a.types[c]);
+    for (uint32_t c = 0; c < a.ncols; ++c) {
+        if (is_list(a.types[c]) && !list_element_known(list_element(a.types[c])))
+            return "column " + std::to_string(c) + " is a list of element type " + std::to_string(list_element(a.types[c])) + ": not int64, float64, int32 or float32";
+        if (!is_list(a.types[c]) && !known_type(a.types[c])) return "column " + std::to_string(c) + " has unknown type " + std::to_string(a.types[c]);
+    }
     for (uint32_t c = 0; c < a.ncols; ++c)
         if (a.kinds[c] != kind_of(a.types[c]))
             return "column " + std::to_string(c) + " of type " + std::to_string(a.types[c]) + " has kind " + std::to_string(a.kinds[c]) +
@@ -188,7 +248,8 @@ inline std::string write_error(const Args& a, bool host) {
     if (!a.out_bytes || !a.stats4) return "out_bytes or stats4 is NULL";
     if (a.nrows > kMaxRows) return "more than 2^40 rows";
     for (uint32_t c = 0; c < a.ncols && a.nrows; ++c) {
-        const std::string what = oxh::cols::column_error("column " + std::to_string(c), a.kinds[c], a.values[c], a.offsets[c], a.nrows, host);
+        const std::string col = "column " + std::to_string(c);
+        const std::string what = is_list(a.types[c]) ? list_error(col, a, c, host) : oxh::cols::column_error(col, a.kinds[c], a.values[c], a.offsets[c], a.nrows, host);
         if (!what.empty()) return what;
     }
     return "";
@@ -247,7 +308,7 @@ inline uint64_t values_len(uint32_t type, uint64_t valid, uint64_t bytes) { retu
 // a value has none), the width of its indices, and the bytes of a page's index stream: the width byte, then one
 // bit-packed run of ceil(valid / 8) groups -- nothing behind the width for a page without a valid row.
 inline bool dict_chunk(uint32_t type, const ChunkDict& d) {
-    return type != OXH_CSV_BOOL && !d.overflow && d.num_values >= 1 && d.num_values <= kDictMaxEntries && d.dict_bytes <= kDictMaxPage;
+    return dict_candidate(type) && !d.overflow && d.num_values >= 1 && d.num_values <= kDictMaxEntries && d.dict_bytes <= kDictMaxPage;
 }
 inline uint32_t dict_width(uint64_t num_values) {
     uint32_t w = 1;
@@ -264,13 +325,89 @@ inline void put_u32(std::vector<uint8_t>& out, uint32_t v) {
     for (int k = 0; k < 4; ++k) out.push_back((uint8_t)(v >> (8 * k)));
 }
 
+// ---------------------------------------------------------------- a list page's level streams
+// One stream of n >= 1 entries at `width` bits is one run of the hybrid. RLE (every entry is `value`): varint(n << 1)
+// and the value's byte. Bit-packed: varint((ceil(n / 8) << 1) | 1), then ceil(n / 8) * width bytes, LSB first, the
+// pad entries 0. Which form depends on counts alone: repetition (width 1) is RLE of 0 when the page's entries equal
+// its rows, definition (width 2) RLE of 3 when its values equal its entries.
+inline uint64_t level_packed_bytes(uint64_t n, uint32_t width, bool rle) { return rle ? 0 : (n + 7) / 8 * width; }
+inline uint64_t level_stream_len(uint64_t n, uint32_t width, bool rle) {
+    return rle ? varint_len(n << 1) + 1 : varint_len((((n + 7) / 8) << 1) | 1) + level_packed_bytes(n, width, false);
+}
+// The stream's head as the page carries it: the run's u32 length, its header and, for RLE, the value byte. The
+// packed bytes behind a bit-packed head are the emit kernel's.
+inline void put_level_head(Thrift& th, uint64_t n, uint32_t width, bool rle, uint8_t value) {
+    put_u32(th.out, (uint32_t)level_stream_len(n, width, rle));
+    if (rle) {
+        th.varint(n << 1);
+        th.out.push_back(value);
+    } else {
+        th.varint((((n + 7) / 8) << 1) | 1);
+    }
+}
+// Bytes of a list page's body: both streams with their lengths, then the PLAIN values.
+inline uint64_t list_body_len(uint64_t rows, uint64_t entries, uint64_t values, uint32_t width) {
+    return 8 + level_stream_len(entries, 1, entries == rows) + level_stream_len(entries, 2, values == entries) + values * width;
+}
+
 struct ChunkMeta {
     uint64_t first_page_at = 0, dict_page_at = 0, bytes = 0, plain_bytes = 0, rows = 0, nulls = 0;  // bytes: as stored; plain_bytes: uncompressed
     MinMax mm;
     bool dict = false;
 };
 
-inline int32_t parquet_type(uint32_t t) { return t == OXH_CSV_INT64 ? 2 : t == OXH_CSV_FLOAT64 ? 5 : t == OXH_CSV_BOOL ? 0 : 6; }
+inline int32_t parquet_type(uint32_t t) {
+    if (is_list(t)) return list_element(t) == OXH_CSV_INT64 ? 2 : list_element(t) == OXH_CSV_FLOAT64 ? 5 : list_element(t) == OXH_CSV_INT32 ? 1 : 4;
+    return t == OXH_CSV_INT64 ? 2 : t == OXH_CSV_FLOAT64 ? 5 : t == OXH_CSV_BOOL ? 0 : 6;
+}
+
+// One page of a list column's chunk from tile t on (t < t1 afterwards): whole tiles until both level streams and the
+// values reach the budget. A list column's tile: min = its level entries, value_bytes = its values' bytes, valid = its
+// lists that are not null. pg comes with file_at, row0, tile0 and col set; false: p.error says why the file is refused.
+inline bool plan_list_page(Plan& p, Page pg, ChunkMeta& m, uint64_t& at, uint64_t& t, uint64_t t1, uint64_t nrows, uint32_t ncols, uint32_t c,
+                           uint32_t type, const Tile* tiles, const uint64_t* stored, uint64_t budget, uint64_t& entry_at, uint64_t& value_at) {
+    const uint32_t w = element_width(type);
+    uint64_t rows = 0, valid = 0, bytes = 0, entries = 0;
+    do {
+        const Tile& tl = tiles[t * ncols + c];
+        const uint64_t tile_rows = std::min(nrows - t * kTileRows, kTileRows);
+        if (tl.valid > tile_rows || tl.min < tile_rows || tl.value_bytes % w || tl.value_bytes / w > tl.min)
+            return p.error = "a tile of a list column counts what it cannot hold", false;
+        p.places[t * ncols + c] = Place{(uint32_t)p.pages.size(), 0, 0};
+        rows += tile_rows, valid += tl.valid, bytes += tl.value_bytes, entries += tl.min;
+        ++t;
+    } while (t < t1 && list_body_len(rows, entries, bytes / w, w) < budget);
+    const uint64_t values = bytes / w, body = list_body_len(rows, entries, values, w);
+    if (body > kMaxPage || entries > kMaxPage)
+        return p.error = "a page of column " + std::to_string(c) + " has " + std::to_string(body) + " B and " + std::to_string(entries) +
+                         " level entries: more than a PageHeader's int32", false;
+    const uint64_t kept = stored ? stored[p.pages.size()] : body;
+    if (kept > kMaxPage) return p.error = "a compressed page of column " + std::to_string(c) + " has more than a PageHeader's int32", false;
+    Thrift th;
+    th.i32(1, 0);  // DATA_PAGE
+    th.i32(2, (int32_t)body), th.i32(3, (int32_t)kept);
+    th.begin(5);
+    th.i32(1, (int32_t)entries), th.i32(2, 0), th.i32(3, 3), th.i32(4, 3);  // num_values counts entries; PLAIN, RLE, RLE
+    th.end();
+    th.out.push_back(0);
+    p.header_len.push_back((uint32_t)th.out.size());
+    const bool rep_rle = entries == rows, def_rle = values == entries;
+    put_level_head(th, entries, 1, rep_rle, 0);
+    pg.head_src = p.blob.size(), pg.head_len = (uint32_t)th.out.size();
+    put_level_head(th, entries, 2, def_rle, 3);
+    pg.def_head_len = (uint32_t)th.out.size() - pg.head_len;
+    pg.level_bytes = (uint32_t)(level_packed_bytes(entries, 1, rep_rle) + pg.def_head_len + level_packed_bytes(entries, 2, def_rle));
+    pg.values_bytes = bytes, pg.rows = (uint32_t)rows, pg.nvalid = (uint32_t)values, pg.entries = (uint32_t)entries;
+    pg.entry0 = entry_at, pg.value0 = value_at;
+    entry_at += entries, value_at += values;
+    p.blob.insert(p.blob.end(), th.out.begin(), th.out.end());
+    const uint64_t plain_whole = p.header_len.back() + body;
+    const uint64_t whole = stored ? p.header_len.back() + kept : plain_whole;
+    if (stored) pg.values_bytes = kept;
+    at += whole, m.bytes += whole, m.plain_bytes += plain_whole, m.rows += entries, m.nulls += rows - valid;
+    p.pages.push_back(pg);
+    return true;
+}
 
 // tiles: ceil(nrows / 1024) * ncols entries. The names are read as write_error() left them.
 // stored: NULL for an uncompressed file; else the plan of the SNAPPY file whose page k's body is stored in stored[k]
@@ -294,6 +431,7 @@ inline Plan make_plan(uint64_t nrows, uint32_t ncols, const uint32_t* types, con
         std::vector<ChunkMeta> chunks;
     };
     std::vector<Group> groups;
+    std::vector<uint64_t> entry_at(ncols, 0), value_at(ncols, 0);  // list columns: the entries and values of the pages so far
     for (uint64_t t0 = 0; t0 < ntiles; t0 += group_tiles) {
         const uint64_t t1 = std::min(ntiles, t0 + group_tiles);
         Group g{std::min(nrows, t1 * kTileRows) - t0 * kTileRows, at, 0, 0, std::vector<ChunkMeta>(ncols)};
@@ -330,6 +468,10 @@ inline Plan make_plan(uint64_t nrows, uint32_t ncols, const uint32_t* types, con
                 pg.file_at = at, pg.row0 = t * kTileRows, pg.tile0 = (uint32_t)t, pg.col = c;
                 uint64_t rows = 0, valid = 0, bytes = 0;
                 uint32_t carry = 0;  // booleans: bool_tail of the page so far
+                if (is_list(types[c])) {
+                    if (!plan_list_page(p, pg, m, at, t, t1, nrows, ncols, c, types[c], tiles, stored, budget, entry_at[c], value_at[c])) return p;
+                    continue;
+                }
                 do {
                     const Tile& tl = tiles[t * ncols + c];
                     const uint64_t tile_rows = std::min(nrows - t * kTileRows, kTileRows);
@@ -390,11 +532,26 @@ inline Plan make_plan(uint64_t nrows, uint32_t ncols, const uint32_t* types, con
     // the footer
     Thrift f;
     f.i32(1, 1);
-    f.list(2, kTStruct, ncols + 1);
+    uint32_t nlists = 0;
+    for (uint32_t c = 0; c < ncols; ++c) nlists += is_list(types[c]);
+    f.list(2, kTStruct, ncols + 1 + 2ull * nlists);
     f.begin();
     f.i32(3, 0), f.binary(4, "schema", 6), f.i32(5, (int32_t)ncols);
     f.end();
     for (uint32_t c = 0; c < ncols; ++c) {
+        if (is_list(types[c])) {  // OPTIONAL group <name> (LIST) { REPEATED group list { OPTIONAL <T> element } }
+            f.begin();
+            f.i32(3, 1), f.binary(4, names + name_offsets[c], name_offsets[c + 1] - name_offsets[c]), f.i32(5, 1), f.i32(6, 3);  // converted type LIST
+            f.begin(10), f.begin(3), f.end(), f.end();  // LogicalType.LIST
+            f.end();
+            f.begin();
+            f.i32(3, 2), f.binary(4, "list", 4), f.i32(5, 1);  // REPEATED
+            f.end();
+            f.begin();
+            f.i32(1, parquet_type(types[c])), f.i32(3, 1), f.binary(4, "element", 7);
+            f.end();
+            continue;
+        }
         f.begin();
         f.i32(1, parquet_type(types[c])), f.i32(3, 1);  // OPTIONAL
         f.binary(4, names + name_offsets[c], name_offsets[c + 1] - name_offsets[c]);
@@ -418,15 +575,18 @@ inline Plan make_plan(uint64_t nrows, uint32_t ncols, const uint32_t* types, con
             f.i32(1, parquet_type(types[c]));
             f.list(2, kTI32, m.dict ? 3 : 2), f.varint(Thrift::zigzag(0)), f.varint(Thrift::zigzag(3));  // PLAIN, RLE
             if (m.dict) f.varint(Thrift::zigzag(8));  // RLE_DICTIONARY
-            f.list(3, kTBinary, 1), f.raw_binary(names + name_offsets[c], name_offsets[c + 1] - name_offsets[c]);
+            f.list(3, kTBinary, is_list(types[c]) ? 3 : 1), f.raw_binary(names + name_offsets[c], name_offsets[c + 1] - name_offsets[c]);
+            if (is_list(types[c])) f.raw_binary("list", 4), f.raw_binary("element", 7);
             f.i32(4, stored ? 1 : 0);  // SNAPPY, UNCOMPRESSED
-            f.i64(5, (int64_t)m.rows), f.i64(6, (int64_t)m.plain_bytes), f.i64(7, (int64_t)m.bytes);
+            f.i64(5, (int64_t)m.rows), f.i64(6, (int64_t)m.plain_bytes), f.i64(7, (int64_t)m.bytes);  // num_values: a list chunk's entries
             f.i64(9, (int64_t)m.first_page_at);
             if (m.dict) f.i64(11, (int64_t)m.dict_page_at);
-            f.begin(12);
-            f.i64(3, (int64_t)m.nulls);
-            if (m.mm.has) f.binary(5, &m.mm.max, 8), f.binary(6, &m.mm.min, 8);
-            f.end();
+            if (!is_list(types[c])) {  // a list chunk has no statistics
+                f.begin(12);
+                f.i64(3, (int64_t)m.nulls);
+                if (m.mm.has) f.binary(5, &m.mm.max, 8), f.binary(6, &m.mm.min, 8);
+                f.end();
+            }
             f.end();
             f.end();
         }

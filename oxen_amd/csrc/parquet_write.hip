@@ -50,6 +50,7 @@ __global__ __launch_bounds__(256) void pqw_measure_kernel(const PqArgs a, pq::Ti
     unsigned long long bad = 0;
     for (uint64_t item = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); item < items; item += nwaves) {  // uniform in the wave
         const PqCol& pc = a.cols[item % a.ncols];
+        if (pq::is_list(pc.type)) continue;  // parquet_write_lists.hip fills a list column's tiles
         const uint64_t r0 = (item / a.ncols) * pq::kTileRows;
         uint32_t valid = 0;
         unsigned long long bytes = 0;
@@ -113,23 +114,6 @@ __global__ __launch_bounds__(256) void pqw_measure_kernel(const PqArgs a, pq::Ti
 }
 
 // ---------------------------------------------------------------- emit
-// n bytes from src (any alignment) to d, without LDS: each lane loads the 16 source bytes that fall on one block of
-// d's 16-byte grid and stores the block; the blocks that hold the span's head or tail go byte by byte.
-__device__ __forceinline__ void pqw_copy_span(uint8_t* d, const uint8_t* src, uint64_t n, unsigned lane) {
-    const uintptr_t d0 = (uintptr_t)d, d1 = d0 + n, grid0 = d0 & ~(uintptr_t)15;
-    for (uint64_t b = 16 * lane; grid0 + b < d1; b += 16 * 64) {
-        const uintptr_t to = grid0 + b;
-        if (to >= d0 && to + 16 <= d1) {
-            PqBlock16 v;
-            __builtin_memcpy(&v, src + (to - d0), 16);
-            *(OXH_PQW_GLOBAL PqBlock16*)to = v;
-        } else {
-            for (uint32_t k = 0; k < 16; ++k)
-                if (to + k >= d0 && to + k < d1) *(OXH_PQW_GLOBAL uint8_t*)(to + k) = src[to + k - d0];
-        }
-    }
-}
-
 // One 64-row step of a tile: the rows that are not null, as the lane's flag and the wave's ballot; the step's 8
 // bytes of the page's bit-packed levels go to their place (`room`: the level bytes the tile owns; rows behind the
 // frame's last are 0 bits, the pad).
@@ -149,6 +133,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void p
     unsigned long long bad = 0;
     for (uint64_t item = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); item < items; item += nwaves) {  // uniform in the wave
         const PqCol& pc = a.cols[item % a.ncols];
+        if (pq::is_list(pc.type)) continue;  // parquet_write_lists.hip writes a list column's pages
         const uint64_t tile = item / a.ncols, r0 = tile * pq::kTileRows;
         const pq::Place pl = e.places[item];
         if (pl.page >= e.npages) {
@@ -376,7 +361,7 @@ struct WriteCall {
 
     unsigned grid() const { return (unsigned)std::min<uint64_t>((args.ntiles * args.ncols + 3) / 4, oxh::kPqMaxGroups); }
     int measure(const pq::Args& a, const void* const* d_values, const void* const* d_offsets, const uint8_t* const* d_validity,
-                const uint64_t* bits);
+                const uint64_t* bits, const uint8_t* const* d_child, const uint64_t* child_bits, const uint64_t* elem_lo);
     int emit(uint8_t* d_out);
     // OXH_PARQUET_SNAPPY, after measure(): compress() emits the uncompressed file into an image the call owns,
     // compresses every page body -- one raw Snappy block each, snappy_compress.hip -- into the fragments' slots and
@@ -395,18 +380,24 @@ struct WriteCall {
     // behind the emit kernel. The working memory lies in the lease behind the plan; it has no pinned mirror.
     oxh::PqDict dict;
     const pq::ChunkDict* dicts = nullptr;
+    // List columns (parquet_write_lists.hip): their tiles are counted behind the measure kernel, their pages written
+    // behind the emit kernel, in working memory of their own.
+    oxh::PqLists lists;
 };
 
 int column_error(unsigned long long e) {
     if (e & oxh::kRowErrOffsets) return fail(OXH_ERR_INVALID, "parquet write: a byte column's offsets decrease or are negative");
     if (e & oxh::kRowErrValues) return fail(OXH_ERR_INVALID, "parquet write: a byte column has bytes but no values");
     if (e & oxh::kPqErrCell) return fail(OXH_ERR_INVALID, "parquet write: a string cell has 2^32 bytes or more");
+    if (e & oxh::kPqErrListOffsets) return fail(OXH_ERR_INVALID, "parquet write: a list column's offsets decrease or are negative");
+    if (e & oxh::kPqErrListValues) return fail(OXH_ERR_INVALID, "parquet write: a list column has elements but no values");
+    if (e & oxh::kPqErrListLong) return fail(OXH_ERR_INVALID, "parquet write: a list has more than INT32_MAX elements, more than a page's int32 holds");
     if (e) return fail(OXH_ERR_HIP, "parquet write: a tile's values are not what was measured (did the columns change during the call?)");
     return OXH_OK;
 }
 
 int WriteCall::measure(const pq::Args& a, const void* const* d_values, const void* const* d_offsets, const uint8_t* const* d_validity,
-                       const uint64_t* bits) {
+                       const uint64_t* bits, const uint8_t* const* d_child, const uint64_t* child_bits, const uint64_t* elem_lo) {
     const uint64_t n = a.nrows, ntiles = (n + pq::kTileRows - 1) / pq::kTileRows, items = ntiles * a.ncols;
     this->a = a;
     tiles = nullptr;
@@ -433,7 +424,7 @@ int WriteCall::measure(const pq::Args& a, const void* const* d_values, const voi
         oxh::PqCol* h_cols = (oxh::PqCol*)(h_base + cols_at);
         for (uint32_t c = 0; c < a.ncols; ++c) {
             h_cols[c].c.values = (const uint8_t*)d_values[c];
-            h_cols[c].c.offsets = is_bytes(a.kinds[c]) ? (const uint8_t*)d_offsets[c] : nullptr;
+            h_cols[c].c.offsets = is_bytes(a.kinds[c]) || pq::is_list(a.types[c]) ? (const uint8_t*)d_offsets[c] : nullptr;
             h_cols[c].c.validity = d_validity[c];
             h_cols[c].c.vbit = bits[2 * c], h_cols[c].c.nbit = bits[2 * c + 1];
             h_cols[c].c.kind = a.kinds[c], h_cols[c].c.order = 0;
@@ -444,6 +435,10 @@ int WriteCall::measure(const pq::Args& a, const void* const* d_values, const voi
         HIP_TRY(hipMemcpyAsync(d_base, h_base, small, hipMemcpyHostToDevice, st));
         oxh::pqw_measure_kernel<<<grid(), 256, 0, st>>>(args, (pq::Tile*)(d_base + tiles_at), d_ctrl);
         HIP_TRY(hipGetLastError());
+        {
+            const int rc = lists.measure(args, a.types, h_cols, d_child, child_bits, elem_lo, (pq::Tile*)(d_base + tiles_at), d_ctrl, h_ctrl, st);
+            if (rc) return rc;
+        }
         if (work) {
             const int rc = dict.build(args, a.types, group_rows, d_base + front, (pq::ChunkDict*)(d_base + chunks_at), d_ctrl, st);
             if (rc) return rc;
@@ -486,6 +481,8 @@ int WriteCall::emit(uint8_t* d_out) {
             const int rc = dict.write(args, em, plan, d_ctrl, st);
             if (rc) return rc;
         }
+        const int rc = lists.emit(em, plan, d_ctrl, st);
+        if (rc) return rc;
         HIP_TRY(hipMemcpyAsync(h_ctrl, d_ctrl, 8, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
@@ -592,14 +589,23 @@ int oxh_write_parquet_device(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const
                              const uint64_t* bit_offsets, const uint8_t* names, const uint64_t* name_offsets, uint64_t rows_per_group,
                              uint64_t page_bytes, uint32_t flags, uint8_t* d_out, uint64_t capacity, uint64_t* out_bytes, uint64_t* stats4,
                              void* stream) {
+    return oxh_write_parquet_lists_device(ctx, nrows, ncols, types, kinds, d_values, d_offsets, d_validity, bit_offsets, names, name_offsets,
+                                          rows_per_group, page_bytes, flags, d_out, capacity, out_bytes, stats4, stream, nullptr, nullptr);
+}
+
+int oxh_write_parquet_lists_device(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const uint32_t* types, const uint32_t* kinds,
+                                   const void* const* d_values, const void* const* d_offsets, const uint8_t* const* d_validity,
+                                   const uint64_t* bit_offsets, const uint8_t* names, const uint64_t* name_offsets, uint64_t rows_per_group,
+                                   uint64_t page_bytes, uint32_t flags, uint8_t* d_out, uint64_t capacity, uint64_t* out_bytes,
+                                   uint64_t* stats4, void* stream, const uint8_t* const* d_child_validity, const uint64_t* child_bit_offsets) {
     const pq::Args a{nrows, ncols, types, kinds, d_values, d_offsets, d_validity, bit_offsets, names, name_offsets,
-                     rows_per_group, page_bytes, flags, d_out, capacity, out_bytes, stats4};
+                     rows_per_group, page_bytes, flags, d_out, capacity, out_bytes, stats4, d_child_validity, child_bit_offsets};
     const std::string what = pq::write_error(a, false);
     if (!what.empty()) return fail(OXH_ERR_INVALID, "parquet write: " + what);
     int rc = device_enter(ctx);
     if (rc) return rc;
     WriteCall call((hipStream_t)stream);
-    if ((rc = call.measure(a, d_values, d_offsets, d_validity, bit_offsets))) return rc;
+    if ((rc = call.measure(a, d_values, d_offsets, d_validity, bit_offsets, d_child_validity, child_bit_offsets, nullptr))) return rc;
     const bool snappy = flags & pq::kFlagSnappy;
     // with the flag the size is known only after compressing: `need` is a capacity that always suffices
     const uint64_t need = snappy ? pq::snappy_capacity(call.plan, ncols) : call.plan.out_bytes;
@@ -618,8 +624,17 @@ int oxh_write_parquet_host(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const u
                            const void* const* values, const void* const* offsets, const uint8_t* const* validity,
                            const uint64_t* bit_offsets, const uint8_t* names, const uint64_t* name_offsets, uint64_t rows_per_group,
                            uint64_t page_bytes, uint32_t flags, uint8_t* out, uint64_t capacity, uint64_t* out_bytes, uint64_t* stats4) {
+    return oxh_write_parquet_lists_host(ctx, nrows, ncols, types, kinds, values, offsets, validity, bit_offsets, names, name_offsets, rows_per_group,
+                                        page_bytes, flags, out, capacity, out_bytes, stats4, nullptr, nullptr);
+}
+
+int oxh_write_parquet_lists_host(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const uint32_t* types, const uint32_t* kinds,
+                                 const void* const* values, const void* const* offsets, const uint8_t* const* validity,
+                                 const uint64_t* bit_offsets, const uint8_t* names, const uint64_t* name_offsets, uint64_t rows_per_group,
+                                 uint64_t page_bytes, uint32_t flags, uint8_t* out, uint64_t capacity, uint64_t* out_bytes, uint64_t* stats4,
+                                 const uint8_t* const* child_validity, const uint64_t* child_bit_offsets) {
     const pq::Args a{nrows, ncols, types, kinds, values, offsets, validity, bit_offsets, names, name_offsets,
-                     rows_per_group, page_bytes, flags, out, capacity, out_bytes, stats4};
+                     rows_per_group, page_bytes, flags, out, capacity, out_bytes, stats4, child_validity, child_bit_offsets};
     const std::string what = pq::write_error(a, true);
     if (!what.empty()) return fail(OXH_ERR_INVALID, "parquet write: " + what);
     int rc = device_enter(ctx);
@@ -628,8 +643,24 @@ int oxh_write_parquet_host(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const u
     // One device block for the inputs: of every column only what its rows name (columns.hpp).
     oxh::cols::Staging staging;
     std::vector<oxh::cols::Staged> staged(ncols);
-    for (uint32_t c = 0; c < ncols && nrows; ++c)
-        staged[c] = staging.add_column(kinds[c], values[c], offsets[c], validity[c], bit_offsets[2 * c], bit_offsets[2 * c + 1], nrows);
+    // a list column: its offsets, its lists' bitmap, and of its elements and their bitmap the span [lo, hi) that the
+    // lists which are not null name -- the kernels subtract lo (elem_lo) from an element's index
+    std::vector<int64_t> child_piece(ncols, -1);
+    std::vector<uint64_t> child_bits(ncols, 0), elem_lo(ncols, 0);
+    for (uint32_t c = 0; c < ncols && nrows; ++c) {
+        if (!pq::is_list(types[c])) {
+            staged[c] = staging.add_column(kinds[c], values[c], offsets[c], validity[c], bit_offsets[2 * c], bit_offsets[2 * c + 1], nrows);
+            continue;
+        }
+        const pq::ListSpan span = pq::list_span(a, c);
+        const uint32_t w = pq::element_width(types[c]);
+        elem_lo[c] = span.lo;
+        staged[c].offsets = staging.add(offsets[c], (nrows + 1) * pq::list_offset_width(types[c]));
+        if (span.hi > span.lo) staged[c].values = staging.add((const uint8_t*)values[c] + w * span.lo, w * (span.hi - span.lo));
+        if (validity[c]) staged[c].validity = staging.add_bits(validity[c], bit_offsets[2 * c + 1], nrows, staged[c].nbit);
+        if (child_validity && child_validity[c] && span.hi > span.lo)
+            child_piece[c] = staging.add_bits(child_validity[c], (child_bit_offsets ? child_bit_offsets[c] : 0) + span.lo, span.hi - span.lo, child_bits[c]);
+    }
     uint8_t *d_in = nullptr, *d_out = nullptr;
     if (staging.total && hipMalloc(&d_in, staging.total) != hipSuccess) {
         (void)hipGetLastError();
@@ -642,16 +673,17 @@ int oxh_write_parquet_host(oxh_ctx* ctx, uint64_t nrows, uint32_t ncols, const u
         for (const oxh::cols::Piece& p : staging.pieces)
             if (p.bytes) HIP_TRY(hipMemcpyAsync(d_in + p.at, p.src, p.bytes, hipMemcpyHostToDevice, st));
         std::vector<const void*> d_values(ncols, nullptr), d_offsets(ncols, nullptr);
-        std::vector<const uint8_t*> d_validity(ncols, nullptr);
+        std::vector<const uint8_t*> d_validity(ncols, nullptr), d_child(ncols, nullptr);
         std::vector<uint64_t> bits(2 * (size_t)ncols, 0);
         for (uint32_t c = 0; c < ncols && nrows; ++c) {
             d_values[c] = staging.values_at(d_in, staged[c]);
             d_offsets[c] = staging.offsets_at(d_in, staged[c]);
             d_validity[c] = staging.validity_at(d_in, staged[c]);
             bits[2 * c] = staged[c].vbit, bits[2 * c + 1] = staged[c].nbit;
+            if (child_piece[c] >= 0) d_child[c] = d_in + staging.pieces[child_piece[c]].at;
         }
         WriteCall call(st);
-        int r = call.measure(a, d_values.data(), d_offsets.data(), d_validity.data(), bits.data());
+        int r = call.measure(a, d_values.data(), d_offsets.data(), d_validity.data(), bits.data(), d_child.data(), child_bits.data(), elem_lo.data());
         if (r) return r;
         const bool snappy = flags & pq::kFlagSnappy;
         need = snappy ? pq::snappy_capacity(call.plan, ncols) : call.plan.out_bytes;

@@ -2405,10 +2405,61 @@ class ParquetWriteStats(NamedTuple):
     nulls: int
 
 
+_LIST_ELEMENT = {"int64": _capi.OXH_CSV_INT64, "float64": _capi.OXH_CSV_FLOAT64, "int32": _capi.OXH_CSV_INT32, "float32": _capi.OXH_CSV_FLOAT32}
+
+
+class _ListCells(NamedTuple):
+    """A `ListColumn` as the writer's tables take it: the fields of a `Column` (kind: the element's width), then the
+    elements' bitmap and the bit of element 0 in it."""
+    kind: int
+    nrows: int
+    values: Any
+    offsets: Any
+    validity: Any
+    value_bit: int
+    validity_bit: int
+    child_validity: Any
+    child_bit: int = 0
+
+
+def _parquet_frame_cells(frame: Mapping, types):
+    """The frame with every `ListColumn` as `_ListCells`, and `types` with their words: OXH_PARQUET_LIST on the
+    element's word by the values' dtype, OXH_PARQUET_LIST64 by the offsets'."""
+    cells, words = {}, {}
+    for k, (name, c) in enumerate(frame.items()):
+        if isinstance(c, (ListColumn, _ListCells)):
+            dtype = lambda a: str(a.dtype).replace("torch.", "")   # noqa: E731
+            if dtype(c.values) not in _LIST_ELEMENT or dtype(c.offsets) not in ("int32", "int64"):
+                raise _capi.OxenError(f"list column {name!r}: elements of {c.values.dtype} with {c.offsets.dtype} offsets; the writer takes int64, "
+                                      "float64, int32 and float32 elements and int32 or int64 offsets", _capi.OXH_ERR_INVALID)
+            words[name] = _capi.OXH_PARQUET_LIST | _LIST_ELEMENT[dtype(c.values)] | (_capi.OXH_PARQUET_LIST64 if dtype(c.offsets) == "int64" else 0)
+            if isinstance(c, ListColumn):
+                c = _ListCells(c.values.dtype.itemsize, len(c.offsets) - 1, c.values, c.offsets, c.validity, 0, 0, c.child_validity)
+        else:
+            given = None if types is None else (types.get(name) if isinstance(types, Mapping) else types[k])
+            if given is not None:
+                words[name] = given
+        cells[name] = c
+    return cells, words
+
+
+def _parquet_tables(cols, ptr):
+    """`_tables`, with a list column's offsets, and behind them the two tables of oxh_write_parquet_lists_*."""
+    kinds, values, offsets, validity, bits = _tables(cols, ptr)
+    n = max(len(cols), 1)
+    child, child_bits = (ctypes.c_void_p * n)(), (ctypes.c_uint64 * n)()
+    for k, c in enumerate(cols):
+        if isinstance(c, _ListCells):
+            offsets[k], child[k], child_bits[k] = ptr(c.offsets), ptr(c.child_validity), int(c.child_bit)
+    return (kinds, values, offsets, validity, bits), (child, child_bits)
+
+
 def _parquet_head(frame: Mapping, rows_per_group, page_bytes, types, compression=None, dictionary=False):
     # the columns, types and names as the CSV writer's call takes them; its own tail (separator, quote, header) is not used
     if compression not in (None, "none", "snappy"):
         raise _capi.OxenError(f"compression {compression!r}: None, 'none' or 'snappy'", _capi.OXH_ERR_INVALID)
+    if any(isinstance(c, (ListColumn, _ListCells)) for c in frame.values()):
+        frame, types = _parquet_frame_cells(frame, types)
     cols, type_words, name_bytes, name_offsets, _ = _write_head(frame, ",", '"', True, types)
     flags = (_capi.OXH_PARQUET_SNAPPY if compression == "snappy" else 0) | (_capi.OXH_PARQUET_DICTIONARY if dictionary else 0)
     return cols, type_words, name_bytes, name_offsets, (int(rows_per_group or 0), int(page_bytes or 0), flags)
@@ -2429,8 +2480,11 @@ def write_parquet(frame: Mapping, path=None, rows_per_group=None, page_bytes=Non
     Snappy block, compressed on the device; the first call then gives a capacity that suffices, the second the size).
     dictionary: True sets OXH_PARQUET_DICTIONARY -- every INT64, DOUBLE and string column chunk within the header's three
     limits gets a dictionary page and RLE_DICTIONARY data pages, built on the device; the others stay PLAIN.
+    A `ListColumn` in the frame (as `read_parquet` returns one: int64, float64, int32 or float32 elements, int32 or int64
+    offsets) is written as a three-level LIST by oxh_write_parquet_lists_host; its schema word is not taken from types.
     `write_df` itself still refuses `.parquet`: this is the entry."""
-    frame = _as_frame(frame)
+    lists = {name for name, c in frame.items() if isinstance(c, (ListColumn, _ListCells))}   # `_parquet_head` converts them
+    frame = {**frame, **_as_frame({name: c for name, c in frame.items() if name not in lists})}
     cols, type_words, name_bytes, name_offsets, tail = _parquet_head(frame, rows_per_group, page_bytes, types, compression, dictionary)
     keep = []
 
@@ -2441,11 +2495,11 @@ def write_parquet(frame: Mapping, path=None, rows_per_group=None, page_bytes=Non
         keep.append(a)
         return a.ctypes.data if a.size else None
 
-    tables = _tables(cols, ptr)
-    head = (_capi.lib().oxh_write_parquet_host, "oxh_write_parquet_host", ctx, cols, type_words, tables, name_bytes, name_offsets, tail)
-    need, _ = _parquet_call(*head, None, 0)
+    tables, child = _parquet_tables(cols, ptr)
+    head = (_capi.lib().oxh_write_parquet_lists_host, "oxh_write_parquet_lists_host", ctx, cols, type_words, tables, name_bytes, name_offsets, tail)
+    need, _ = _parquet_call(*head, None, 0, *child)
     out = np.zeros(max(need, 1), dtype=np.uint8)
-    need, stats = _parquet_call(*head, out.ctypes.data, need)
+    need, stats = _parquet_call(*head, out.ctypes.data, need, *child)
     data = out[:need].tobytes()
     if path is not None:
         from .version_store import AtomicFile
@@ -2459,24 +2513,25 @@ def write_parquet_device(frame: Mapping, rows_per_group=None, page_bytes=None, t
     """oxh_write_parquet_device over device `Column`s; the file's bytes as a uint8 torch tensor on the device. It
     measures, allocates, then writes; a caller's `capacity` (bytes) skips the measure, and a capacity below the need is
     the library's error. compression and dictionary as `write_parquet`'s: with "snappy" the tensor is allocated at the bound and
-    returned sliced to the file's size. Blocks."""
+    returned sliced to the file's size. A device `ListColumn` is written as `write_parquet` writes a host one, by
+    oxh_write_parquet_lists_device. Blocks."""
     import torch
 
     from .device import _require_cuda, _stream
 
     cols, type_words, name_bytes, name_offsets, tail = _parquet_head(frame, rows_per_group, page_bytes, types, compression, dictionary)
-    tensors = [t for c in cols for t in (c.values, c.offsets, c.validity) if t is not None]
+    tensors = [t for c in cols for t in (c.values, c.offsets, c.validity, getattr(c, "child_validity", None)) if t is not None]
     _require_cuda(*tensors)
     if any(not t.is_contiguous() for t in tensors):
         raise _capi.OxenError("column tensors must be contiguous", _capi.OXH_ERR_INVALID)
     device = tensors[0].device if tensors else "cuda"
     ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()  # noqa: E731
-    tables = _tables(cols, ptr)
-    head = (_capi.lib().oxh_write_parquet_device, "oxh_write_parquet_device", ctx, cols, type_words, tables, name_bytes, name_offsets, tail)
+    tables, child = _parquet_tables(cols, ptr)
+    head = (_capi.lib().oxh_write_parquet_lists_device, "oxh_write_parquet_lists_device", ctx, cols, type_words, tables, name_bytes, name_offsets, tail)
     if capacity is None:
-        capacity, _ = _parquet_call(*head, None, 0, _stream(stream))
+        capacity, _ = _parquet_call(*head, None, 0, _stream(stream), *child)
     out = torch.empty(max(int(capacity), 1), dtype=torch.uint8, device=device)
-    need, stats = _parquet_call(*head, out.data_ptr(), int(capacity), _stream(stream))
+    need, stats = _parquet_call(*head, out.data_ptr(), int(capacity), _stream(stream), *child)
     return (out[:need], stats) if with_stats else out[:need]
 
 
